@@ -112,7 +112,39 @@ def parse():
                     help="frames a process has enqueued before anything is timed (the settle phase runs at least until "
                          "then; see RUNTIME_WARM_FRAMES)")
     ap.add_argument("--planes", type=int, default=5, help="cull planes used (5 = forward.rs:268; fewer only for triage)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the LAST timed step computed — the buffers a caller of the step receives — as "
+                         "DIR/<name>.npy (float64), taken right behind the timed region: every buffer's header words "
+                         "(<name>_header) and the records they count, one row of fields each (<name>); a list larger than "
+                         "its share of 64 MB is a fixed, seeded sample of rows whose indices are in <name>_rows")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: all files together, .npy headers included
+
+
+def last_step_outputs(buffers, max_bytes=DUMP_MAX_BYTES):
+    """{name: float64 array} of the given output buffers — (name, byte tensor, header bytes, record dtype) each: the header
+    as u32 words, and the records its first word counts as rows of their fields.  Every buffer gets an equal share of
+    `max_bytes`; a longer list is a sample of rows drawn with a fixed seed (the same rows for the same count), written
+    with their indices.  Reads the buffers only: the caller synchronizes first."""
+    from numpy.lib import recfunctions as rfn
+
+    out = {}
+    share = max_bytes // max(len(buffers), 1) - 1024  # (the header words and three .npy headers)
+    for name, buf, hdr, rec in buffers:
+        head = buf[:hdr].cpu().numpy().view("<u4")
+        out[f"{name}_header"] = head.astype(np.float64)
+        n = min(int(head[0]), (buf.numel() - hdr) // rec.itemsize)
+        recs = buf[hdr:hdr + rec.itemsize * n].view(n, rec.itemsize)
+        cap = max(share // (8 * (len(rec.names) + 1)), 1)
+        if n > cap:
+            rows = np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+            recs = recs[torch.from_numpy(rows).to(recs.device)]
+            out[f"{name}_rows"] = rows.astype(np.float64)
+        host = np.ascontiguousarray(recs.cpu().numpy()).reshape(-1).view(rec)
+        out[name] = rfn.structured_to_unstructured(host, dtype=np.float64)
+    return out
 
 
 def spawn_ranks(args):
@@ -523,6 +555,27 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before anything behind the region reuses these buffers: the slot it
+        # culled in (dispatch records, its list buffer) and, N > 1, the gathered list its exchange delivered + the shard's
+        # own commands
+        if use_graph:  # replay i: graph i % 2 = cull into list i % 2 || exchange of the other list
+            s_last, k_last = slots[0], (args.steps - 1) % 2
+            wire_last = recv_bufs[1 - k_last]
+        else:
+            s_last = slots[(step_no[0] - 1) % F]
+            k_last = (s_last.uses - 1) % len(s_last.lists)
+            wire_last = recv_bufs[(x_count[0] - 1) % len(recv_bufs)] if do_gather else None
+        dump = [("dispatch", s_last.disp, L.DISPATCH_HEADER, L.MESHLET_DISPATCH)]
+        if do_gather:
+            dump.append(("visible_records", wire_last, L.VISIBLE_HEADER, L.VISIBLE_RECORD))
+            if own_expand:
+                dump.append(("draw_commands", s_last.own_cmds, L.DRAW_HEADER, L.MESHLET_DRAW_COMMAND))
+        else:
+            dump.append(("draw_commands", s_last.lists[k_last], L.DRAW_HEADER, L.MESHLET_DRAW_COMMAND))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in last_step_outputs(dump).items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), a)
     # N > 1: the intervals between the completions of consecutive steps' exchanges inside the timed region (HIP events on
     # the exchange stream) — the steady-state step time without whatever a single slow step adds to wall / K
     step_intervals = None
@@ -1003,7 +1056,7 @@ def dry_ranks(args, rank, world, json_fd):
     allr = [torch.zeros(2, dtype=torch.int64) for _ in range(world)]
     if world > 1:
         dist.all_gather(allr, mine)
-        dist.barrier()
+        dist.monitored_barrier()  # host-side: dist.barrier() would bring up the GPU runtime to find the accelerator
     else:
         allr = [mine]
     if rank == 0:

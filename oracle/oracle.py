@@ -7,6 +7,7 @@ All arguments are host numpy arrays; outputs are fresh numpy arrays.
 import ctypes as C
 import os
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -21,17 +22,20 @@ def build(force=False):
         subprocess.run(["make", "-C", _HERE, "-s"], check=True)
 
 
-NATIVE_LIB_PATH = os.path.join(_HERE, "liborbit_oracle_native.so")
 NATIVE_CFLAGS = "-O3 -march=native -ffp-contract=off -fno-fast-math -fopenmp"  # oracle/Makefile NATIVE_CFLAGS
 _native = None
 
 
 def lib_native():
-    """The same sources built -O3 -march=native ON THIS HOST (cpu_baseline of bench.py; SURVEY.md §8d flags)."""
+    """The same sources built -O3 -march=native ON THIS HOST (cpu_baseline of bench.py; SURVEY.md §8d flags).  Built
+    afresh by every process, for the CPU it runs on, in a private temporary directory (the checkout may not be
+    writable by whoever runs the bench) that is gone again once the library is loaded."""
     global _native
     if _native is None:
-        subprocess.run(["make", "-C", _HERE, "-s", "-B", "native"], check=True)  # always for this host's CPU
-        _native = C.CDLL(NATIVE_LIB_PATH)
+        with tempfile.TemporaryDirectory(prefix="orbit_oracle_native_") as d:
+            out = os.path.join(d, "liborbit_oracle_native.so")
+            subprocess.run(["make", "-C", _HERE, "-s", "-B", "native", f"NATIVE_OUT={out}"], check=True)
+            _native = C.CDLL(out)
     return _native
 
 

@@ -17,6 +17,15 @@ import torch
 import torch.distributed as dist
 
 
+def _setup_barrier(group, device):
+    """A barrier of the exchange's set-up.  Over host buffers (a CPU device: gloo) it is the host-side one — dist.barrier()
+    asks for the machine's accelerator first, which brings up the GPU runtime in a process that uses no GPU."""
+    if torch.device(device).type == "cpu":
+        dist.monitored_barrier(group=group)
+    else:
+        dist.barrier(group=group)
+
+
 def shard_ranges(entity_draw_count, world):
     """[begin, end) per rank, cut at multiples of 32 so entity-bitset words are rank-private.
     Mirrors orbit_shard_range() of the C ABI (pure integer math, no device needed)."""
@@ -69,7 +78,7 @@ class P2PExchange:
         # in the next collective): failure anywhere raises everywhere
         self.out, self.peers = self._shared(nbytes, "the exchange buffer")
         self.ctrl, self.ctrls = self._shared(self.CTRL_BYTES, "the control block")  # mapped like the output buffers
-        dist.barrier(group=group)  # every peer has mapped every buffer before the first scatter
+        _setup_barrier(group, device)  # every peer has mapped every buffer before the first scatter
         if probe_on_init:
             status = engine.status if engine is not None else None
             if not self.probe(check_status=status):  # agreed on by all ranks inside probe()
@@ -79,7 +88,7 @@ class P2PExchange:
                         status()  # clear what the failed probe latched (a poll that ran out)
                     except Exception:  # noqa: BLE001
                         pass
-                dist.barrier(group=group)
+                _setup_barrier(group, device)
 
     def _shared(self, nbytes, what):
         err = None

@@ -4,7 +4,7 @@ level by level), spirv_compact.npz (`compact`: active_cluster_compaction.comp.sp
 (`contracted`: the cull cases with Dot / matrix products / Length as fma chains): inputs and OUTPUTS OF THE
 REFERENCE'S OWN COMPILED SHADERS.
 
-Run in the build container only (it reads /root/reference/shaders/{entity_cull,meshlet_cull}.comp.spv,
+Run after build() has copied the reference's binaries (oracle/Makefile `ref`; it reads oracle/_ref/shaders/{entity_cull,meshlet_cull}.comp.spv,
 forward/forward_depth_prepass.task.spv and light_cluster/{mark_active,light_culling}.comp.spv, which do not travel): `python tests/golden/make_spirv_vectors.py`.  The binaries are executed by oracle/spirv_vm.py; what the
 interpreter decides itself is listed in its header (operation order inside Dot / MatrixTimesVector, log2, the ReduceMin
 sampler, invocation order of atomics — the oracle's documented canonical choices, passed in from the oracle).  Every
@@ -30,7 +30,7 @@ import scenes as sc  # noqa: E402
 from oracle import oracle, spirv_vm as vm  # noqa: E402
 from orbit_amd import layouts as L  # noqa: E402
 
-REF = "/root/reference/shaders/"
+REF = os.path.join(ROOT, "oracle", "_ref", "shaders", "")  # the reference's binaries, as build() copies them
 F = np.float32
 W, H = 320, 180
 ORTHO = dict(p00=1.0 / 16, p11=1.0 / 16, z_near=0.7, z_far=61.3)

@@ -55,6 +55,33 @@ def test_bench_line_has_the_contract_fields(source):
     assert tp["pass1_draws"] + tp["pass2_draws"] > 0 and tp["visible_meshlets"] > 0
 
 
+def test_bench_dump_outputs_are_the_last_steps_buffers(tmp_path):
+    """--dump-outputs: the dispatch records and draw commands of the last timed step as float64 arrays — the counts the
+    JSON line reports, the same arrays from a run with another number of steps (the scene and the step are the same)."""
+    import numpy as np
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    runs = []
+    for steps in ("3", "5"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", "1",
+                            "--entities", "6000", "--cpu-sample-entities", "0", "--settle-ms", "0",
+                            "--dump-outputs", str(tmp_path / steps)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
+        assert d["steps"] == int(steps) and d["ms_per_step"] > 0
+        names = sorted(os.listdir(tmp_path / steps))
+        assert names == ["dispatch.npy", "dispatch_header.npy", "draw_commands.npy", "draw_commands_header.npy"], names
+        a = {n[:-4]: np.load(tmp_path / steps / n) for n in names}
+        assert all(x.dtype == np.float64 for x in a.values())
+        assert sum(os.path.getsize(tmp_path / steps / n) for n in names) <= 64_000_000
+        assert a["draw_commands_header"][0] == d["config"]["survivors"] == len(a["draw_commands"]) > 0
+        assert a["dispatch"][:, 2].sum() == d["config"]["meshlets_into_meshlet_cull"] == 6000 * 256
+        runs.append(a)
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+
+
 def _run_ranks(extra, env):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--entities", "6000",
                         "--settle-ms", "5"] + extra, capture_output=True, text=True, timeout=900,
@@ -66,14 +93,15 @@ def _run_ranks(extra, env):
 
 
 @pytest.mark.parametrize("expand", ["own", "none"])
-def test_bench_two_ranks_on_one_device_whole_device_path(expand):
+def test_bench_two_ranks_on_one_device_whole_device_path(tmp_path, expand):
     """`bench.py --gpus 2` as the driver starts it (bench.py spawns its ranks), both ranks on the box's one GPU: the
     real exchange — HIP IPC mappings of the peers' buffers and control blocks, the scatter kernel, counts and completion
     signalled on the device (the process group over gloo: RCCL cannot put two ranks on one device) — then every rank's
     segment check, the check of its own command buffer and the cross-rank checksum of the gathered list inside bench.py
     (it exits non-zero if they fail); behind the timed region the OTHER transport's leg (the all-gather of fixed-capacity
     segments + compaction), whose list must be the main transport's byte for byte."""
-    d = _run_ranks(["--gpus", "2", "--expand", expand], dict(ORBIT_BENCH_ONE_DEVICE="1", ORBIT_BENCH_BACKEND="gloo"))
+    d = _run_ranks(["--gpus", "2", "--expand", expand, "--dump-outputs", str(tmp_path)],
+                   dict(ORBIT_BENCH_ONE_DEVICE="1", ORBIT_BENCH_BACKEND="gloo"))
     c = d["config"]
     assert d["n_gpus"] == 2 and c["world_size"] == 2 and c["gather"] is True and c["transport"] == "p2p"
     assert c["exchange"] == "records" and c["backend"] == "gloo" and c["signalling"] == "device"
@@ -87,16 +115,46 @@ def test_bench_two_ranks_on_one_device_whole_device_path(expand):
     ta = d["transport_alt"]
     assert ta["name"] == "rccl" and ta["signalling"] == "rccl-allgather" and ta["ms_per_step"] > 0
     assert ta["list_identical_to_main_transport"] is True and ta["steps"] == 4
+    # --dump-outputs (rank 0): the gathered record list of the last timed step names every survivor of both ranks; with
+    # --expand own, rank 0's own command buffer holds its shard's survivors
+    import numpy as np
+
+    recs, head = np.load(tmp_path / "visible_records.npy"), np.load(tmp_path / "visible_records_header.npy")
+    assert recs.dtype == np.float64 and head[0] == len(recs) > 0
+    masks = recs[:, 2].astype(np.uint32)
+    assert int(np.unpackbits(masks.view(np.uint8)).sum()) == c["survivors"]
+    assert os.path.exists(tmp_path / "draw_commands.npy") == (expand == "own")
+    if expand == "own":
+        own = np.load(tmp_path / "draw_commands.npy")
+        assert np.load(tmp_path / "draw_commands_header.npy")[0] == pr["survivors"][0] == len(own)
+
+
+# A process that has a GPU open holds part of it; at most six may share one device, this test's own process among them.
+# Up to five ranks therefore stack on device 0; a larger world runs one rank per device, as the driver runs it, and needs
+# as many GPUs as ranks.
+RANKS_ON_ONE_DEVICE_MAX = 5
+
+
+def _rank_placement(world):
+    """bench.py's environment for `world` ranks on this box; skips (before any work) when it has too few GPUs."""
+    import torch
+
+    if world <= RANKS_ON_ONE_DEVICE_MAX:
+        return dict(ORBIT_BENCH_ONE_DEVICE="1")
+    n = torch.cuda.device_count()
+    if n < world:
+        pytest.skip(f"needs {world} GPUs, found {n}: more than {RANKS_ON_ONE_DEVICE_MAX} ranks do not share one device")
+    return {}
 
 
 @pytest.mark.parametrize("world,transport", [(8, "p2p"), (5, "p2p"), (8, "rccl")])
 def test_bench_at_the_world_size_north_star_names_on_one_device(world, transport):
     """`ORBIT_BENCH_ONE_DEVICE=1 bench.py --gpus 8` (and 5: not a power of two): the whole N > 1 bench path — spawn, shard
-    ranges, eight contexts' culls and eight device-signalled exchanges sharing the box's one GPU, two frames in flight —
-    at the world size the driver's scaling run ends with.  bench.py checks every rank's segment of the gathered list, its
-    own command buffer and the cross-rank checksum; --verify-single-rank additionally holds the gathered list against ONE
-    rank culling the whole scene (from the Meshlet buffer: another evaluation path), and the other transport's leg must
-    deliver the same bytes."""
+    ranges, eight contexts' culls and eight device-signalled exchanges (five sharing one GPU; eight on eight GPUs, one
+    each), two frames in flight — at the world size the driver's scaling run ends with.  bench.py checks every rank's
+    segment of the gathered list, its own command buffer and the cross-rank checksum; --verify-single-rank additionally
+    holds the gathered list against ONE rank culling the whole scene (from the Meshlet buffer: another evaluation path),
+    and the other transport's leg must deliver the same bytes."""
     # (with the all-gather as the MAIN transport every step of this one-device configuration stages its fixed-capacity
     # segments through gloo and the host — seconds per step at eight ranks, and no number of this run is a measurement:
     # a third of the entities and no settle phase there, so that the test stays minutes away from the bench's own deadline
@@ -104,7 +162,7 @@ def test_bench_at_the_world_size_north_star_names_on_one_device(world, transport
     entities = 24000 if transport == "p2p" else 8000
     d = _run_ranks(["--gpus", str(world), "--entities", str(entities), "--transport", transport, "--verify-single-rank",
                     "--cpu-sample-entities", "0"] + ([] if transport == "p2p" else ["--settle-ms", "0"]),
-                   dict(ORBIT_BENCH_ONE_DEVICE="1", ORBIT_BENCH_BACKEND="gloo"))
+                   dict(_rank_placement(world), ORBIT_BENCH_BACKEND="gloo"))
     c = d["config"]
     assert d["n_gpus"] == world and c["world_size"] == world and c["transport"] == transport and c["transport_fallback"] is None
     assert c["signalling"] == ("device" if transport == "p2p" else "rccl-allgather")

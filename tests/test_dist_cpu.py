@@ -158,6 +158,8 @@ def _compact_segments_numpy(segments, world, segment_capacity, out, out_capacity
     out[:4].view(torch.int32)[0] = min(sum(counts), out_capacity)
 
 
+# (the ranks' barriers are gloo's host-side monitored_barrier: dist.barrier() asks for the machine's accelerator first,
+# which would bring up the GPU runtime in every rank of this CPU test)
 def _p2p_worker(rank, world, port, seed, n_entities, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -182,13 +184,13 @@ def _p2p_worker(rank, world, port, seed, n_entities, out_dir):
         ex = P2PExchange(None, capacity, header, stride, torch.device("cpu"), transport=t)
         assert ex.fallback is None and ex.signalling == "device"
         ex.out[:] = 0x55
-        dist.barrier()
+        dist.monitored_barrier()
         for step in range(4):  # the buffers are reused step after step: epochs 2 .. 5 behind the probe's, both count slots
             out = ex.exchange(torch.from_numpy(local.copy()))
         assert t.timeouts == 0
-        dist.barrier()
+        dist.monitored_barrier()
         np.save(os.path.join(out_dir, f"p2p_{name}_{rank}.npy"), out.numpy().copy())
-        dist.barrier()
+        dist.monitored_barrier()
         ex.close()
     # north_star's transport: the record list as ONE all-gather of fixed-capacity segments + the compaction — the same
     # capacity on every rank (the largest shard's records), this rank's list in a buffer of a whole segment
@@ -202,7 +204,7 @@ def _p2p_worker(rank, world, port, seed, n_entities, out_dir):
     ag.out[:] = 0x55
     for step in range(2):
         out = ag.exchange(torch.from_numpy(local.copy()))
-        dist.barrier()
+        dist.monitored_barrier()
     np.save(os.path.join(out_dir, f"allgather_rec_{rank}.npy"), out.numpy().copy())
     dist.destroy_process_group()
 

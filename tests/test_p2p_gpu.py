@@ -1,8 +1,8 @@
 """The exchange with no host in the step (orbit_p2p_* + orbit_exchange_list, dist.P2PExchange) with its REAL transport:
-2, 3, 5 and 8 processes that share the test box's one GPU map each other's exchange buffers and control blocks through
-HIP IPC and scatter their shard's list into every peer's buffer with the HIP kernels — counts and completion signalled
-on the device.  torch.distributed (gloo: RCCL refuses several ranks on one device) only carries the set-up and the
-test's own barriers; the all-gather transport's compaction is fed by the ranks' real segments."""
+2, 3 and 5 processes that share one GPU (8: one per GPU, on a box with eight) map each other's exchange buffers and
+control blocks through HIP IPC and scatter their shard's list into every peer's buffer with the HIP kernels — counts and
+completion signalled on the device.  torch.distributed (gloo: RCCL refuses several ranks on one device) only carries the
+set-up and the test's own barriers; the all-gather transport's compaction is fed by the ranks' real segments."""
 import os
 import socket
 
@@ -23,6 +23,11 @@ def _free_port():
     return port
 
 
+# A process that has a GPU open holds part of it; at most six may share one device, this test's own process among them.
+# Up to five ranks therefore share device 0; a larger world puts one rank on each device and needs as many GPUs as ranks.
+RANKS_ON_ONE_DEVICE_MAX = 5
+
+
 def _worker(rank, world, port, seed, n_entities, out_dir):
     import torch
     import torch.distributed as dist
@@ -31,14 +36,15 @@ def _worker(rank, world, port, seed, n_entities, out_dir):
     from orbit_amd.engine import Engine
 
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
+    d = 0 if world <= RANKS_ON_ONE_DEVICE_MAX else rank
+    torch.cuda.set_device(d)
+    dev = torch.device("cuda", d)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     scene = sc.make_scene(seed, n_entities, n_meshes=60)
     cam = sc.default_camera()
     ci = sc.make_cull_info(cam.view, cam.planes)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
-    eng = Engine(0)
+    eng = Engine(d)
     b, e = shard_ranges(scene.entity_draw_count, world)[rank]
     disp_cap, cap = scene.max_dispatches() + 8, scene.lod0_meshlets + 8
     disp = torch.zeros(L.DISPATCH_HEADER + 16 * disp_cap, dtype=torch.uint8, device=dev)
@@ -111,8 +117,12 @@ def test_p2p_exchange_processes_sharing_one_gpu(tmp_path, oracle, world, n_entit
     step has no collective in it and is also replayed from a captured graph.  Worlds up to the 8 north_star names (and 5:
     not a power of two; 200 entity-draws over 8 ranks: an empty shard): eight writers per control block, seven
     destinations per scatter, twelve eager epochs + five replays on top of the constructor's probe."""
+    import torch
     import torch.multiprocessing as mp
 
+    if world > RANKS_ON_ONE_DEVICE_MAX and torch.cuda.device_count() < world:
+        pytest.skip(f"needs {world} GPUs, found {torch.cuda.device_count()}: more than {RANKS_ON_ONE_DEVICE_MAX} ranks "
+                    "do not share one device")
     seed = 35
     mp.spawn(_worker, args=(world, _free_port(), seed, n_entities, str(tmp_path)), nprocs=world, join=True)
     scene = sc.make_scene(seed, n_entities, n_meshes=60)

@@ -1,5 +1,5 @@
 """The SPIR-V interpreter (oracle/spirv_vm.py) itself: its fused multiply-add is exactly rounded, and — where the
-reference's shader binaries are present (the build container; they do not travel) — re-running them reproduces the
+reference's shader binaries are present (copied into oracle/_ref/shaders by build()) — re-running them reproduces the
 committed vectors byte for byte, i.e. tests/golden/spirv_*.npz are the interpreter's output on the reference's binaries,
 not hand-made data."""
 import os
@@ -11,7 +11,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
-REF = "/root/reference/shaders/meshlet_cull.comp.spv"
+REF = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "shaders", "meshlet_cull.comp.spv")  # oracle/Makefile `ref`
 
 
 def _round_f32(q):
@@ -33,7 +33,7 @@ def test_vm_fma32_is_correctly_rounded():
         assert float(got[k]) == want, (k, a[k], b[k], c[k])
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not on this machine")
+@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not in oracle/_ref")
 @pytest.mark.parametrize("occlusion_pass,ortho,knife", [(0, False, True), (1, True, False), (2, True, True), (2, False, False)])
 def test_rerunning_the_binaries_reproduces_the_committed_cull_vectors(occlusion_pass, ortho, knife):
     import make_spirv_vectors as gen
@@ -47,7 +47,7 @@ def test_rerunning_the_binaries_reproduces_the_committed_cull_vectors(occlusion_
                               np.ascontiguousarray(stored[f"{name}/{k}"]).view(np.uint8).reshape(-1)), (name, k)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not on this machine")
+@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not in oracle/_ref")
 @pytest.mark.parametrize("S,ortho,knife", [(64, False, True), (128, True, False)])
 def test_rerunning_the_binaries_at_another_dispatch_size_reproduces_the_committed_vectors(S, ortho, knife):
     """tests/golden/spirv_cull_dispatch_sizes.npz: the two cull binaries with spec constant 0 = 64 / 128, pass 0."""
@@ -62,7 +62,7 @@ def test_rerunning_the_binaries_at_another_dispatch_size_reproduces_the_committe
                               np.ascontiguousarray(stored[f"{name}/{k}"]).view(np.uint8).reshape(-1)), (name, k)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not on this machine")
+@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not in oracle/_ref")
 @pytest.mark.parametrize("occlusion_pass,ortho,knife", [(0, False, True), (2, False, True), (1, True, False)])
 def test_rerunning_the_binaries_contracted_reproduces_the_committed_vectors(occlusion_pass, ortho, knife):
     """tests/golden/spirv_cull_contracted.npz: the same binaries with Dot / matrix products / Length as fma chains."""
@@ -77,7 +77,7 @@ def test_rerunning_the_binaries_contracted_reproduces_the_committed_vectors(occl
                               np.ascontiguousarray(stored[f"{name}/{k}"]).view(np.uint8).reshape(-1)), (name, k)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not on this machine")
+@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not in oracle/_ref")
 def test_rerunning_the_binaries_reproduces_a_committed_cluster_vector():
     import make_spirv_vectors as gen
 
@@ -88,7 +88,7 @@ def test_rerunning_the_binaries_reproduces_a_committed_cluster_vector():
                               np.ascontiguousarray(stored[f"s2/{k}"]).view(np.uint8).reshape(-1)), k
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not on this machine")
+@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not in oracle/_ref")
 def test_the_compaction_binary_marks_the_same_clusters_with_the_same_header(oracle):
     """active_cluster_compaction.comp.spv (integer-only; a 4x4x4-workgroup dispatch; the last workgroup writes the
     indirect-dispatch header): the header {ceil(n / 256), 1, 1, n} and the SET of cluster indices equal the oracle's.
@@ -113,7 +113,7 @@ def test_the_compaction_binary_marks_the_same_clusters_with_the_same_header(orac
         assert sorted(B[2][16:16 + 4 * n].view(np.uint32).tolist()) == ou[16:16 + 4 * n].view(np.uint32).tolist()
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not on this machine")
+@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not in oracle/_ref")
 @pytest.mark.parametrize("shader", ["forward/forward.task.spv", "shadow/shadow.task.spv"])
 def test_the_other_task_shaders_compute_the_same_task_records(shader):
     """forward.task and shadow.task cull with the same functions as forward_depth_prepass.task (the one the committed
@@ -129,7 +129,7 @@ def test_the_other_task_shaders_compute_the_same_task_records(shader):
          5: g("cull_info").view(np.uint8).reshape(-1).copy(), 7: g("mvis_in").view(np.uint8).reshape(-1).copy(),
          8: g("meshlets").view(np.uint8).reshape(-1).copy(), 10: g("materials").view(np.uint8).reshape(-1).copy(),
          12: np.zeros(64, np.uint8), 13: np.zeros(64, np.uint8)}
-    mod = vm.Module("/root/reference/shaders/" + shader, spec={0: 32})
+    mod = vm.Module(gen.REF + shader, spec={0: 32})
     # the registry indices go where the binary's own push-constant block has the members of those names
     index = {"draw_command_buffer": 3, "cull_info_buffer": 5, "vertex_buffer": 12, "meshlet_buffer": 8,
              "meshlet_data_buffer": 13, "entity_buffer": 4, "materials_buffer": 10}
@@ -150,7 +150,7 @@ def test_the_other_task_shaders_compute_the_same_task_records(shader):
         assert [int(x) & 0xFF for x in pay[2]] == want[k]["meshlet_indices"].tolist()
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not on this machine")
+@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not in oracle/_ref")
 @pytest.mark.parametrize("placement", ["model", "mesh"])
 def test_config1_bitset_is_what_the_entity_cull_binary_keeps(placement):
     """BASELINE config 1 (8 192 spheres, frustum only): the fixture's visibility bitset — generated by the oracle — is
@@ -177,7 +177,7 @@ def test_config1_bitset_is_what_the_entity_cull_binary_keeps(placement):
     assert bool((recs["meshlet_count"] == 1).all()) and np.array_equal(recs["meshlet_offset"], want)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not on this machine")
+@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not in oracle/_ref")
 def test_rerunning_the_depth_reduce_binary_reproduces_the_committed_pyramids():
     import make_spirv_vectors as gen
 
