@@ -35,6 +35,10 @@ pub struct OrbitFrameLate {
     pub pyramid_count: u32, pub late_view_count: u32, pub cascade_view_count: u32, pub _pad: u32,
 }
 
+/// scene.rs Transform as orbit_scene_update_entities reads it (40 B; quaternion x, y, z, w)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitEntityTransform { pub position: [f32; 3], pub orientation: [f32; 4], pub scale: [f32; 3] }
+
 /// push-constant order of shaders/entity_cull.comp:17-23 (== draw_gen.rs:372-376)
 #[repr(C)]
 pub struct OrbitEntityCullBufs {
@@ -192,6 +196,11 @@ extern "C" {
     pub fn orbit_compact_segments(ctx: *mut OrbitCtx, segments: *const c_void, world: u32, segment_capacity: u32,
                                   out_list: *mut c_void, out_capacity: u32, header_bytes: u32, stride: u32,
                                   stream: *mut c_void) -> i32;
+    /// SceneData::update_scene's EntityData rows computed on the device from the entities' transforms: all of them
+    /// (instance_indices null, count <= entity_capacity) or only the rows named by a DEVICE list of instance indices.
+    pub fn orbit_scene_update_entities(ctx: *mut OrbitCtx, transforms: *const OrbitEntityTransform,
+                                       instance_indices: *const u32, count: u32, entity_data: *mut c_void,
+                                       entity_capacity: u32, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

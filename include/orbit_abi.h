@@ -74,7 +74,8 @@ enum {
     ORBIT_E_MISSING = -7,  /* a resource the CullInfo declares present was passed as NULL
                               (.unwrap() at draw_gen.rs:123-133) */
     ORBIT_E_COMM = -8,     /* RCCL is not loadable in this process or one of its calls failed */
-    ORBIT_E_RANGE = -9,    /* a culled / expanded meshlet lies outside the bound meshlet stream (latched on device) */
+    ORBIT_E_RANGE = -9,    /* a culled / expanded meshlet lies outside the bound meshlet stream, or a scene update
+                              named an instance index >= entity_capacity (latched on device) */
     ORBIT_E_STALE = -10    /* the bound meshlet stream no longer mirrors the meshlet buffer it was derived from
                               (orbit_meshlet_stream_validate, or any cull with caps.validate_streams; latched) */
 };

@@ -12,7 +12,8 @@
  *   - the late half of a frame with its independent chains side by side (orbit_frame_late),
  *   - the sharded engine: the shard cull, the record list, its device-side exchanges (HIP-IPC stores; RCCL all-gather)
  *     and the expansion of a gathered list,
- *   - the measurement hook of bench.py.
+ *   - the measurement hook of bench.py,
+ *   - the scene update: model and normal matrices computed on the device from entity transforms.
  * A build that only needs the drop-in includes orbit_abi.h alone; liborbit_cull.so exports both sets.
  */
 #ifndef ORBIT_ABI_EXT_H
@@ -432,6 +433,44 @@ int32_t orbit_allgather_list(OrbitCtx *ctx, void *nccl_comm, uint32_t rank, uint
 int32_t orbit_compact_segments(OrbitCtx *ctx, const void *segments, uint32_t world, uint32_t segment_capacity,
                                void *out_list, uint32_t out_capacity, uint32_t header_bytes, uint32_t stride,
                                void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* Scene update on the device.  SceneData::update_scene (src/scene.rs:404-492) */
+/* builds every entity's EntityData on the CPU each frame: the model matrix    */
+/* Mat4::from_scale_rotation_translation of its Transform, the normal matrix   */
+/* the upper 3x3 of model.inverse().transpose() (identity elsewhere), and     */
+/* uploads all 128-B rows again.  This entry point computes the rows from the */
+/* 40-B transforms instead, bit for bit what the host mirror's               */
+/* EntityData::entity_gpu_data gives (scalar cofactor inverse, the products   */
+/* in the host's association, correctly rounded 1/det, f32 denormals kept).   */
+/*   dense   instance_indices == NULL: entity_data[i] for i < count; count >  */
+/*           entity_capacity is refused (ORBIT_E_INVALID)                     */
+/*   sparse  instance_indices != NULL (DEVICE, count u32): only the rows      */
+/*           entity_data[instance_indices[i]] are written, every other byte   */
+/*           stays as it was.  An index >= entity_capacity writes nothing and */
+/*           latches ORBIT_E_RANGE (orbit_ctx_status); the other rows are     */
+/*           still written.  With duplicate indices one of the writers wins,  */
+/*           which one is unspecified.                                        */
+/* transforms is a DEVICE array of `count` entries (4-B alignment suffices;   */
+/* 16 B is faster), entity_data a DEVICE array of entity_capacity rows,       */
+/* 16-B aligned.  count == 0 is ORBIT_OK with no launch; a NULL transforms or */
+/* entity_data with count > 0 is ORBIT_E_INVALID.  Stream semantics are those */
+/* of the other entry points.  The call allocates nothing, uses no scratch    */
+/* and never synchronises the host, so it can be captured into a graph on its */
+/* very first call.  OrbitCaps.arith_profile does not apply: this arithmetic  */
+/* is the reference's host (glam on the CPU), the same in both profiles.      */
+/* ------------------------------------------------------------------------ */
+typedef struct OrbitEntityTransform { /* scene.rs Transform, field order of OrbitHostEntity */
+    float position[3];
+    float orientation[4]; /* quaternion x, y, z, w; not required to be normalised */
+    float scale[3];
+} OrbitEntityTransform;
+ORBIT_STATIC_ASSERT(sizeof(OrbitEntityTransform) == 40, "EntityTransform is 40 B");
+
+/* entity_data[i] (or entity_data[instance_indices[i]]) = EntityData::entity_gpu_data() of transforms[i], i < count */
+int32_t orbit_scene_update_entities(OrbitCtx *ctx, const OrbitEntityTransform *transforms,
+                                    const uint32_t *instance_indices, uint32_t count,
+                                    OrbitEntityData *entity_data, uint32_t entity_capacity, void *stream);
 
 #ifdef __cplusplus
 }

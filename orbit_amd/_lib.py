@@ -150,6 +150,8 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "orbit_compact_segments": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                            C.c_uint32, C.c_uint32, C.c_void_p]),
+    "orbit_scene_update_entities": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                C.c_void_p]),
 }
 
 _lib = None

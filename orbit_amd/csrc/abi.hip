@@ -475,7 +475,8 @@ int32_t orbit_ctx_status(OrbitCtx *ctx, void *stream, int32_t sync) {
         e = memset_now(ctx->status, 0, 4);
         if (e != hipSuccess) return hip_fail(ctx, e, "hipMemset(status)");
         return fail(ctx, v, v == ORBIT_E_CAPACITY ? "an append overflowed a caller buffer (entries dropped)"
-                            : v == ORBIT_E_RANGE  ? "a meshlet outside the bound meshlet stream was culled or expanded"
+                            : v == ORBIT_E_RANGE  ? "a meshlet outside the bound meshlet stream was culled or expanded, "
+                                                    "or a scene update named an instance index past entity_capacity"
                             : v == ORBIT_E_STALE  ? "the bound meshlet stream no longer mirrors its meshlet buffer (update missing)"
                                                   : "device-latched error %d", v);
     }
@@ -1988,6 +1989,28 @@ int32_t orbit_gather_visible(OrbitCtx *ctx, void *nccl_comm, uint32_t rank, uint
                              void *stream) {
     return gather_lists(ctx, nccl_comm, rank, world, local_draw_buffer, out_draw_buffer, out_capacity, stream,
                         ORBIT_DRAW_HEADER, sizeof(OrbitMeshletDrawCommand));
+}
+
+// ------------------------------------------------------------- scene update
+// EntityData rows from transforms (scene_update.hip).  No allocation, no scratch, no host sync: capturable on the first
+// call.  The sparse form's out-of-range indices are latched on the device (ORBIT_E_RANGE), not checked here.
+int32_t orbit_scene_update_entities(OrbitCtx *ctx, const OrbitEntityTransform *transforms,
+                                    const uint32_t *instance_indices, uint32_t count, OrbitEntityData *entity_data,
+                                    uint32_t entity_capacity, void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    if (count == 0) return ORBIT_OK;
+    if (!transforms || !entity_data) return fail(ctx, ORBIT_E_INVALID, "scene_update_entities: NULL buffer");
+    if (((uintptr_t)transforms & 3u) || ((uintptr_t)instance_indices & 3u) || ((uintptr_t)entity_data & 15u))
+        return fail(ctx, ORBIT_E_INVALID, "scene_update_entities: transforms and instance_indices must be 4-B aligned, "
+                                          "entity_data 16-B aligned");
+    if (!instance_indices && count > entity_capacity)
+        return fail(ctx, ORBIT_E_INVALID, "scene_update_entities: dense update of %u rows into a capacity of %u", count,
+                    entity_capacity);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_scene_update_entities(transforms, instance_indices, count, entity_data, entity_capacity,
+                                                      ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch scene_update_entities");
+    return ORBIT_OK;
 }
 
 } // extern "C"

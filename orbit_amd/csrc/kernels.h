@@ -356,6 +356,10 @@ hipError_t launch_meshlet_stream_build(const OrbitMeshlet *meshlets, uint64_t fi
 hipError_t launch_meshlet_stream_validate(const OrbitMeshlet *meshlets, const MeshletStreamView &ms,
                                           const OrbitMaterialData *materials, uint32_t material_count, int32_t *status,
                                           hipStream_t s);
+// scene_update.hip: orbit_scene_update_entities (instance_indices == nullptr: the dense form)
+hipError_t launch_scene_update_entities(const OrbitEntityTransform *transforms, const uint32_t *instance_indices,
+                                        uint32_t count, OrbitEntityData *entity_data, uint32_t entity_capacity,
+                                        int32_t *status, hipStream_t s);
 // the alpha classes of the whole stream, from its material indices (orbit_meshlet_stream_set_materials)
 // meshes [first, first + count) of `mesh_infos` -> their 32-B side entries; and the comparison (ORBIT_E_STALE)
 hipError_t launch_mesh_side_build(const OrbitMeshInfo *mesh_infos, uint32_t first, uint32_t count, MeshSide *table, hipStream_t s);

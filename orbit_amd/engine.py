@@ -208,6 +208,23 @@ class Engine:
                                                    entity_draw_count, _stream(stream))
         _lib.check(rc, self._ctx)
 
+    # -- the scene update: EntityData rows from transforms on the device (orbit_scene_update_entities)
+    def scene_update_entities(self, transforms, entity_data, count=None, instance_indices=None, entity_capacity=None,
+                              stream=None):
+        """entity_data[i] (or entity_data[instance_indices[i]]) = EntityData::entity_gpu_data of transforms[i], i < count.
+        transforms: device tensor holding layouts.ENTITY_TRANSFORM rows (40 B each); instance_indices: device tensor
+        holding u32 indices (any dtype: its bytes are read), or None for the dense form.  count defaults to the 4-B
+        entries of instance_indices (sparse) or the 40-B rows of transforms (dense), entity_capacity to the 128-B rows
+        entity_data holds.  Enqueued on `stream`; an index past the capacity is reported by status() (ORBIT_E_RANGE)."""
+        nbytes = lambda t: t.numel() * t.element_size()  # noqa: E731
+        if count is None:
+            count = nbytes(instance_indices) // 4 if instance_indices is not None else nbytes(transforms) // 40
+        if entity_capacity is None:
+            entity_capacity = nbytes(entity_data) // 128
+        _lib.check(self._lib.orbit_scene_update_entities(self._ctx, _ptr(transforms), _ptr(instance_indices), int(count),
+                                                         _ptr(entity_data), int(entity_capacity), _stream(stream)),
+                   self._ctx)
+
     # -- several views side by side (orbit_cull_views)
     def cull_views(self, views, stream=None):
         """views: list of dicts with the arguments of entity_cull + meshlet_cull for one view each:

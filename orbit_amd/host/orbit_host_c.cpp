@@ -425,6 +425,21 @@ const OrbitLightData *orbit_host_scene_light_data(const void *sc, uint64_t *coun
 uint64_t orbit_host_scene_shadow_command_count(const void *sc) {
     return ((const scene::SceneData *)sc)->shadow_commands.size();
 }
+int32_t orbit_host_scene_update_deferred(void *sc, const OrbitMeshInfo *mesh_infos, uint64_t mesh_info_count,
+                                         float luminance_cutoff, uint64_t frame_index) {
+    return guarded([&] {
+        ((scene::SceneData *)sc)->update_scene_deferred(mesh_infos, (size_t)mesh_info_count, luminance_cutoff,
+                                                        (size_t)frame_index);
+    });
+}
+const OrbitEntityTransform *orbit_host_scene_transforms(const void *sc, uint64_t *count) {
+    const scene::SceneData *s = (const scene::SceneData *)sc;
+    *count = s->entity_transform_cache.size();
+    return s->entity_transform_cache.data();
+}
+int64_t orbit_host_scene_instance_index(const void *sc, uint64_t entity) {
+    return ((const scene::SceneData *)sc)->instance_index((size_t)entity);
+}
 
 // ---------------------------------------------------------------- asset side (orbit_assets.hpp), host only
 int32_t orbit_host_compute_meshlets(const float *positions, uint64_t vertex_count, const uint32_t *indices,

@@ -171,6 +171,14 @@ const void *orbit_host_scene_entity_draws(const void *scene, uint64_t *count);  
 const OrbitEntityData *orbit_host_scene_entity_data(const void *scene, uint64_t *count);
 const OrbitLightData *orbit_host_scene_light_data(const void *scene, uint64_t *count);
 uint64_t orbit_host_scene_shadow_command_count(const void *scene);
+/* update_scene with the EntityData rows left to orbit_scene_update_entities: draws, visibility words, light data and
+ * shadow commands as orbit_host_scene_update makes them; the transforms of the drawn entities, in instance order, take
+ * the place of the entity data (orbit_host_scene_entity_data is then empty) */
+int32_t orbit_host_scene_update_deferred(void *scene, const OrbitMeshInfo *mesh_infos, uint64_t mesh_info_count,
+                                         float luminance_cutoff, uint64_t frame_index);
+const OrbitEntityTransform *orbit_host_scene_transforms(const void *scene, uint64_t *count);
+/* the entity's instance index (its row of entity_data) from the latest update, -1 if it had none */
+int64_t orbit_host_scene_instance_index(const void *scene, uint64_t entity);
 
 /* ---- asset side (orbit_assets.hpp): mesh -> Meshlet[] + meshlet data, mesh bounds (host only) ---- */
 /* assets::mesh::compute_meshlets (mesh.rs:292-338).  Two-call protocol: with out_meshlets == NULL only the counts are

@@ -153,14 +153,31 @@ size_t SceneData::add_entity(EntityData data) {
 
 void SceneData::update_scene(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff,
                              size_t frame_index) {
+    update(mesh_infos, mesh_info_count, luminance_cutoff, frame_index, false);
+}
+
+void SceneData::update_scene_deferred(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff,
+                                      size_t frame_index) {
+    update(mesh_infos, mesh_info_count, luminance_cutoff, frame_index, true);
+}
+
+int64_t SceneData::instance_index(size_t entity) const {
+    return entity < instance_index_.size() ? instance_index_[entity] : -1;
+}
+
+void SceneData::update(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff,
+                       size_t frame_index, bool deferred) {
     entity_draw_cache.clear();
     entity_data_cache.clear();
+    entity_transform_cache.clear();
     light_data_cache.clear();
     shadow_commands.clear(); // shadow_renderer.clear_shadow_commands(), :418
-    for (EntityData &entity : entities) {
+    instance_index_.assign(entities.size(), -1);
+    for (size_t e = 0; e < entities.size(); e++) {
+        EntityData &entity = entities[e];
         if (entity.mesh) { // :420-437
             const uint32_t mesh = *entity.mesh;
-            const uint32_t instance_index = (uint32_t)entity_data_cache.size();
+            const uint32_t instance_index = (uint32_t)entity_draw_cache.size();
             size_t visibility_offset;
             if (entity.visibility_buffer_range) {
                 visibility_offset = entity.visibility_buffer_range->range.start;
@@ -172,7 +189,16 @@ void SceneData::update_scene(const OrbitMeshInfo *mesh_infos, size_t mesh_info_c
                 entity.visibility_buffer_range = VisibilityBufferRange{a->first, a->second};
                 visibility_offset = a->second.start;
             }
-            entity_data_cache.push_back(entity.entity_gpu_data());
+            if (deferred) {
+                const passes::Transform &t = entity.transform;
+                entity_transform_cache.push_back(OrbitEntityTransform{{t.position.x, t.position.y, t.position.z},
+                                                                      {t.orientation.x, t.orientation.y,
+                                                                       t.orientation.z, t.orientation.w},
+                                                                      {t.scale.x, t.scale.y, t.scale.z}});
+            } else {
+                entity_data_cache.push_back(entity.entity_gpu_data());
+            }
+            instance_index_[e] = instance_index;
             entity_draw_cache.push_back(GpuEntityDraw{instance_index, mesh, (uint32_t)visibility_offset});
         }
         std::optional<OrbitLightData> light_data = entity.light_gpu_data(luminance_cutoff); // :449-468

@@ -182,18 +182,30 @@ class SceneData {
     std::vector<OrbitEntityData> entity_data_cache;
     std::vector<OrbitLightData> light_data_cache;
     std::vector<ShadowCommand> shadow_commands; // what update_scene hands to ShadowRenderer::add_shadow
+    // update_scene_deferred: every drawn entity's transform in instance order, the input of orbit_scene_update_entities
+    std::vector<OrbitEntityTransform> entity_transform_cache;
 
     size_t add_entity(EntityData data); // scene.rs:398-402
     // scene.rs:404-492.  `mesh_infos` = assets.shared_stuff.mesh_infos; an entity whose visibility words cannot be
     // allocated panics like the reference's unwrap (:427).
     void update_scene(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff,
                       size_t frame_index);
+    // update_scene with the EntityData rows left to the device: the same draws, visibility allocation, light data and
+    // shadow commands, but entity_transform_cache is filled instead of entity_data_cache (which is left empty)
+    void update_scene_deferred(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff,
+                               size_t frame_index);
+    // the entity's instance index (its row of entity_data) from the latest update; -1 if it had none (no mesh, or added
+    // since)
+    int64_t instance_index(size_t entity) const;
     // the bytes written at offset 0 of entity_draw_buffer (:470-481): u32 count, then the draws
     std::vector<uint8_t> entity_draw_buffer_bytes() const;
     collections::FreeListAllocator &meshlet_visibility_allocator() { return meshlet_visibility_allocator_; }
 
   private:
+    void update(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff, size_t frame_index,
+                bool deferred);
     collections::FreeListAllocator meshlet_visibility_allocator_;
+    std::vector<int64_t> instance_index_; // per entity, from the latest update
 };
 
 } // namespace scene

@@ -26,6 +26,8 @@ LIGHT_TYPE_SKY, LIGHT_TYPE_DIRECTIONAL, LIGHT_TYPE_POINT = 0, 1, 2  # types.glsl
 ENTITY_DRAW = np.dtype([("entity_index", "<u4"), ("mesh_index", "<u4"), ("visibility_offset", "<u4")])
 # types.glsl:75-78, src/scene.rs:120-125 (column-major mat4)
 ENTITY_DATA = np.dtype([("model_matrix", "<f4", (16,)), ("normal_matrix", "<f4", (16,))])
+# OrbitEntityTransform (include/orbit_abi_ext.h): scene.rs Transform, the input of orbit_scene_update_entities
+ENTITY_TRANSFORM = np.dtype([("position", "<f4", (3,)), ("orientation", "<f4", (4,)), ("scale", "<f4", (3,))])
 # types.glsl:128-141, src/assets/mod.rs:18-28
 MESH_INFO = np.dtype([
     ("bounding_sphere", "<f4", (4,)), ("aabb_min", "<f4", (4,)), ("aabb_max", "<f4", (4,)),
@@ -99,7 +101,8 @@ GPU_CLUSTER_INFO_BUFFER = np.dtype([
 ])
 
 _SIZES = {
-    "ENTITY_DRAW": (ENTITY_DRAW, 12), "ENTITY_DATA": (ENTITY_DATA, 128), "MESH_INFO": (MESH_INFO, 128),
+    "ENTITY_DRAW": (ENTITY_DRAW, 12), "ENTITY_DATA": (ENTITY_DATA, 128), "ENTITY_TRANSFORM": (ENTITY_TRANSFORM, 40),
+    "MESH_INFO": (MESH_INFO, 128),
     "MESHLET": (MESHLET, 32), "MATERIAL": (MATERIAL, 80), "LIGHT": (LIGHT, 64),
     "MESHLET_DISPATCH": (MESHLET_DISPATCH, 16), "MESHLET_DRAW_COMMAND": (MESHLET_DRAW_COMMAND, 28),
     "MESH_TASK_RECORD": (MESH_TASK_RECORD, 44), "VISIBLE_RECORD": (VISIBLE_RECORD, 12),
@@ -114,6 +117,7 @@ assert GPU_CULL_INFO.fields["occlusion_pass"][1] == 332
 assert GPU_CULL_INFO.fields["lod_target_pos_view_space"][1] == 384
 assert MATERIAL.fields["alpha_mode"][1] == 64
 assert MESH_INFO.fields["mesh_lods"][1] == 64
+assert ENTITY_TRANSFORM.fields["orientation"][1] == 12 and ENTITY_TRANSFORM.fields["scale"][1] == 28
 assert CLUSTER_CULL_INFO.fields["global_light_count"][1] == 176
 
 

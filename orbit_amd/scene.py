@@ -70,6 +70,11 @@ def _h():
             f.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         h.orbit_host_scene_shadow_command_count.restype = C.c_uint64
         h.orbit_host_scene_shadow_command_count.argtypes = [C.c_void_p]
+        h.orbit_host_scene_update_deferred.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_uint64]
+        h.orbit_host_scene_transforms.restype = C.c_void_p
+        h.orbit_host_scene_transforms.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        h.orbit_host_scene_instance_index.restype = C.c_int64
+        h.orbit_host_scene_instance_index.argtypes = [C.c_void_p, C.c_uint64]
         _bound = True
     return h
 
@@ -184,6 +189,21 @@ class SceneData:
         mi = np.ascontiguousarray(mesh_infos, dtype=L.MESH_INFO)
         _check(_h().orbit_host_scene_update(self._p, mi.ctypes.data_as(C.c_void_p), len(mi), luminance_cutoff,
                                             frame_index))
+
+    def update_scene_deferred(self, mesh_infos, luminance_cutoff=0.25, frame_index=0):
+        """update_scene with the EntityData rows left to the device (Engine.scene_update_entities): the transform cache
+        in instance order takes the place of the entity data cache."""
+        mi = np.ascontiguousarray(mesh_infos, dtype=L.MESH_INFO)
+        _check(_h().orbit_host_scene_update_deferred(self._p, mi.ctypes.data_as(C.c_void_p), len(mi), luminance_cutoff,
+                                                     frame_index))
+
+    def transform_cache(self):
+        """layouts.ENTITY_TRANSFORM rows of the drawn entities in instance order (update_scene_deferred)."""
+        return self._cache(_h().orbit_host_scene_transforms, L.ENTITY_TRANSFORM)
+
+    def instance_index(self, entity):
+        """The entity's row of entity_data from the latest update, or -1."""
+        return int(_h().orbit_host_scene_instance_index(self._p, entity))
 
     def _cache(self, fn, dtype):
         n = C.c_uint64()
