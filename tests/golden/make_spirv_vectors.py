@@ -1,5 +1,6 @@
 """Generates tests/golden/spirv_cull.npz and spirv_cluster.npz (no argument), spirv_pyramid.npz (`pyramid`: depth_reduce.comp.spv
-level by level), spirv_compact.npz (`compact`: active_cluster_compaction.comp.spv) and spirv_cull_dispatch_sizes.npz
+level by level), spirv_compact.npz (`compact`: active_cluster_compaction.comp.spv), spirv_cluster_shapes.npz (`cluster_shapes`: the two
+light-cluster binaries at other tile sizes, slice counts, sample counts, light types and edge cases) and spirv_cull_dispatch_sizes.npz
 (`dispatch`: the two cull shaders with MESHLET_DISPATCH_SIZE = 64 / 128, pass 0) and spirv_cull_contracted.npz
 (`contracted`: the cull cases with Dot / matrix products / Length as fma chains): inputs and OUTPUTS OF THE
 REFERENCE'S OWN COMPILED SHADERS.
@@ -221,15 +222,19 @@ def case(seed, occlusion_pass, ortho, knife, n=140, S=32, fused_dot=False):
 CREF = REF + "light_cluster/"
 
 
-def cluster_case(seed, width, height, n_lights, quantised, samples=1):
+def cluster_case(seed, width, height, n_lights, quantised, samples=1, tile=8, zsl=32, point_fraction=1.0,
+                 radius_scale=None, poison=False):
     """mark_active.comp.spv and light_culling.comp.spv (active_cluster_compaction.comp is integer-only and its list
-    order is the atomics' — the oracle's list is handed to the last stage as input)."""
+    order is the atomics' — the oracle's list is handed to the last stage as input).  point_fraction < 1 makes the
+    other lights directional (light_culling.comp:114-117: in every cluster); radius_scale multiplies the outer radii;
+    poison puts NaN / inf into light positions and NaN / inf / 0 into radii (the depth stays finite and positive: the
+    slice of a NaN or negative sample is undefined in SPIR-V, and the interpreter's would be the oracle's own choice)."""
     cam = sc.default_camera(aspect=width / height)
     depth = sc.make_depth(seed, width, height, cam, n_occluders=40, ground=(seed % 2 == 0))
     if samples > 1:  # a multisampled depth buffer [h][w][samples] (cluster.rs:439-456)
         jit = sc.rnd_range(seed, 90, np.arange(width * height * samples), 0.9, 1.1).reshape(height, width, samples)
         depth = (depth[:, :, None] * jit).astype(F)
-    tile, zsl, far = 8, 32, 200.0
+    far = 200.0
     cx, cy = -(-width // tile), -(-height // tile)
     zs, zb = oracle.cluster_grid_info(cam.z_near, far, zsl)
     push = np.zeros((), dtype=L.MARK_ACTIVE_PUSH)
@@ -241,7 +246,14 @@ def cluster_case(seed, width, height, n_lights, quantised, samples=1):
     info["screen_to_view_matrix"] = sc.mat4_cols(np.linalg.inv(cam.proj.astype(np.float64)).astype(F))
     info["cluster_count"], info["tile_size_px"], info["screen_size"] = (cx, cy, zsl), tile, (width, height)
     info["z_near"], info["z_far"], info["global_light_count"] = cam.z_near, far, n_lights
-    lights = sc.make_lights(seed, n_lights)
+    lights = sc.make_lights(seed, n_lights, point_fraction=point_fraction)
+    if radius_scale is not None:
+        lights["outer_radius"] *= F(radius_scale)
+    if poison:
+        for k, val in enumerate((np.nan, np.inf, -np.inf, np.nan, np.inf, -np.inf)):
+            lights["position"][10 + k, k % 3] = val
+        for k, val in enumerate((np.nan, np.inf, 0.0, np.nan, np.inf, 0.0)):
+            lights["outer_radius"][20 + k] = val
     if quantised is True:  # positions on a quarter-unit grid around the camera, few radii: exact ties in the sphere test
         rng = np.random.default_rng(seed)
         lights = lights.copy()
@@ -296,6 +308,80 @@ def cluster_case(seed, width, height, n_lights, quantised, samples=1):
     return dict(push=np.array(push).reshape(1), depth=depth, info=np.array(info).reshape(1), lights=lights,
                 unique=unique[:16 + 4 * na].copy(), spv_masks=masks, spv_bounds=bounds,
                 spv_light_list=B[2][:4 + 4 * nl].copy(), spv_offset_image=img)
+
+
+# The shapes the product serves beyond spirv_cluster.npz's one (96x64, 8-px tiles, 32 slices, 120 point lights):
+# name -> cluster_case arguments, and the property each case exists for (checked by shapes_main on the binary's output)
+CLUSTER_SHAPES = {
+    # partial edge tiles on both axes, 12-px tiles, 24 slices, 10 % directional lights and 12x radii: saturated clusters
+    # whose kept 256 hold directional lights
+    "edge12_sat": dict(seed=26, width=100, height=70, n_lights=700, tile=12, zsl=24, point_fraction=0.9, radius_scale=12.0),
+    # 5-px tiles, 7 slices, a 2-sample depth buffer, partial edge tiles on both axes, more than 256 active clusters
+    # (several light_culling workgroups)
+    "t5_z7_ms2": dict(seed=22, width=97, height=61, n_lights=120, tile=5, zsl=7, samples=2, point_fraction=0.9),
+    # 3-px tiles, 16 slices, a 4-sample depth buffer, partial edge tiles on both axes, more than 256 active clusters
+    "t3_z16_ms4": dict(seed=23, width=62, height=41, n_lights=60, tile=3, zsl=16, samples=4),
+    # 16-px tiles, 16 slices, no lights at all (light_count = 0, every count 0)
+    "t16_none": dict(seed=25, width=120, height=72, n_lights=0, tile=16, zsl=16),
+    # 16-px tiles, 24 slices, lights with NaN / inf positions and NaN / inf / 0 radii, directional lights among them
+    "t16_poison": dict(seed=24, width=200, height=120, n_lights=160, tile=16, zsl=24, point_fraction=0.95, poison=True),
+}
+
+
+def cluster_shape_properties(name, c):
+    """What a case of CLUSTER_SHAPES must show in the binary's own output (the generator refuses a case without it)."""
+    args = CLUSTER_SHAPES[name]
+    info = c["info"].view(L.CLUSTER_CULL_INFO)[0]
+    w, h = (int(v) for v in info["screen_size"])
+    tile = int(info["tile_size_px"])
+    na = int(c["unique"][12:16].view(np.uint32)[0])
+    nl = int(c["spv_light_list"][:4].view(np.uint32)[0])
+    act = c["unique"][16:16 + 4 * na].view(np.uint32)
+    img = c["spv_offset_image"][act]
+    point = c["lights"]["light_type"] == L.LIGHT_TYPE_POINT
+    assert na > 0 and int(img[:, 1].sum()) == nl
+    if name != "t16_none":
+        assert w % tile != 0 and h % tile != 0, "no partial edge tile on both axes"
+        cx, cy = (int(v) for v in info["cluster_count"][:2])
+        x, y = act % cx, act // cx % cy  # active clusters in the last column and the last row: the clamp decides them
+        assert (x == cx - 1).any() and (y == cy - 1).any()
+    if name in ("t5_z7_ms2", "t3_z16_ms4"):
+        assert na > 256, "one light_culling workgroup only"
+    if name == "edge12_sat":
+        sat = img[:, 1] == 256
+        assert sat.sum() >= 3, "fewer than three saturated clusters"
+        lst = c["spv_light_list"][4:].view(np.uint32)
+        kept_dir = [lst[o:o + 256][~point[lst[o:o + 256]]] for o, n in img[sat]]
+        assert all(len(k) > 0 for k in kept_dir), "a saturated list without a directional light"
+        assert (img[:, 1] > 64).sum() > (img[:, 1] == 256).sum() and ((img[:, 1] > 16) & (img[:, 1] <= 64)).any()
+    if name == "t16_none":
+        assert nl == 0 and (img[:, 1] == 0).all()
+    if name == "t16_poison":
+        pos, r = c["lights"]["position"], c["lights"]["outer_radius"]
+        assert (~np.isfinite(pos)).any(axis=1).sum() >= 6 and np.isnan(r).any() and np.isinf(r).any() and (r == 0).any()
+        assert (~point).any() and nl > 0
+    if args.get("samples", 1) > 1:
+        assert c["depth"].shape == (h, w, args["samples"])
+    assert np.isfinite(c["depth"]).all() and (c["depth"] >= 0).all(), "a depth sample whose slice is undefined"
+
+
+def cluster_shapes_main():
+    """tests/golden/spirv_cluster_shapes.npz: mark_active.comp.spv and light_culling.comp.spv on CLUSTER_SHAPES."""
+    out = {}
+    for name, args in CLUSTER_SHAPES.items():
+        a = dict(args)
+        c = cluster_case(a.pop("seed"), a.pop("width"), a.pop("height"), a.pop("n_lights"), False, **a)
+        cluster_shape_properties(name, c)
+        for k, v in c.items():
+            out[f"{name}/{k}"] = v
+        act = c["unique"][16:16 + 4 * int(c["unique"][12:16].view(np.uint32)[0])].view(np.uint32)
+        cnt = c["spv_offset_image"][act, 1]
+        print("%-12s active %4d, light indices %6d, max count %3d, saturated %3d" % (
+            name, len(act), int(c["spv_light_list"][:4].view(np.uint32)[0]), int(cnt.max()) if len(cnt) else 0,
+            int((cnt == 256).sum())))
+    path = os.path.join(HERE, "spirv_cluster_shapes.npz")
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), "bytes")
 
 
 def pyramid_depth(seed, sw, sh):
@@ -470,6 +556,8 @@ def main():
         return pyramid_main()
     if len(sys.argv) > 1 and sys.argv[1] == "compact":
         return compact_main()
+    if len(sys.argv) > 1 and sys.argv[1] == "cluster_shapes":
+        return cluster_shapes_main()
     out, summary = {}, []
     cl = {}
     for seed, quantised, samples in ((1, False, 1), (2, True, 1), (4, True, 1), (5, False, 4), (6, "knife", 1)):

@@ -387,3 +387,107 @@ def depth_reduce(depth, sw, sh):
         pyr[offs[k]:offs[k] + dw * dh] = lvl
         src, srcw, srch = lvl, dw, dh
     return pyr, (w0, h0, mips)
+
+
+# ----------------------------------------------------------------------------- light clusters (light_culling.comp)
+def _field(info, name):
+    return np.asarray(info).reshape(-1)[0][name]
+
+
+def cluster_aabb(info, bounds, cluster_index):
+    """compute_cluster_volume (light_culling.comp:62-90) of every cluster in `cluster_index` -> (mn[n, 3], mx[n, 3]).
+    screen_to_view and line_intersection_to_z_plane as written (eye = 0, normal = (0, 0, -1), dot products left to
+    right); min / max are the GLSL's (y < x ? y : x) forms the oracle documents."""
+    cx, cy = (int(v) for v in _field(info, "cluster_count")[:2])
+    tile = int(_field(info, "tile_size_px"))
+    sw, sh = (F(int(v)) for v in _field(info, "screen_size"))
+    s2v = np.asarray(_field(info, "screen_to_view_matrix"), F)
+    z_near = F(_field(info, "z_near"))
+    idx = np.asarray(cluster_index, np.int64).reshape(-1)
+    z = idx // (cx * cy)
+    rem = idx - z * cx * cy
+    y = rem // cx
+    x = rem - y * cx
+    with np.errstate(all="ignore"):
+        min_x, min_y = (x * tile).astype(F), (y * tile).astype(F)  # cluster_id.xy * tile_size_px, :67
+        max_x, max_y = gmin((min_x + F(tile)).astype(F), sw), gmin((min_y + F(tile)).astype(F), sh)  # :68
+
+        def screen_to_view(sx, sy):  # :34-48
+            tx, ty = (sx / sw).astype(F), (sy / sh).astype(F)
+            c0 = (tx * F(2.0) - F(1.0)).astype(F)
+            c1 = ((F(1.0) - ty).astype(F) * F(2.0) - F(1.0)).astype(F)
+            one = np.ones_like(c0)
+            v = mat_vec(s2v, c0, c1, one, one)
+            return [(v[i] / v[3]).astype(F) for i in range(3)]
+
+        def line_z(b, zd):  # :50-60 with a = 0
+            ab = [(t - F(0.0)).astype(F) for t in b]
+            dna = F(F(0.0) * F(0.0) + F(0.0) * F(0.0)) + F(-1.0) * F(0.0)
+            dnab = (((F(0.0) * ab[0]).astype(F) + (F(0.0) * ab[1]).astype(F)).astype(F) + (F(-1.0) * ab[2]).astype(F)).astype(F)
+            t = ((zd - dna).astype(F) / dnab).astype(F)
+            return [(F(0.0) + (t * a).astype(F)).astype(F) for a in ab]
+
+        lo, hi = screen_to_view(min_x, min_y), screen_to_view(max_x, max_y)
+        b = np.ascontiguousarray(bounds, np.uint32)[idx]
+        min_depth = (F(1.0) - b[:, 0].view(F)).astype(F)
+        max_depth = b[:, 1].view(F)
+        near, far = (z_near / max_depth).astype(F), (z_near / min_depth).astype(F)
+        p = [line_z(lo, near), line_z(lo, far), line_z(hi, near), line_z(hi, far)]
+        mn = np.stack([gmin(gmin(p[0][i], p[1][i]), gmin(p[2][i], p[3][i])) for i in range(3)], axis=1)
+        mx = np.stack([gmax(gmax(p[0][i], p[1][i]), gmax(p[2][i], p[3][i])) for i in range(3)], axis=1)
+    return mn, mx
+
+
+def light_view_centres(info, lights):
+    """world_to_view_matrix * vec4(position, 1.0) of every light (:110) -> [n, 3]."""
+    pos = np.asarray(lights["position"], F)
+    with np.errstate(all="ignore"):
+        c = mat_vec(np.asarray(_field(info, "world_to_view_matrix"), F), pos[:, 0], pos[:, 1], pos[:, 2],
+                    np.ones(len(pos), F))
+    return np.stack(c[:3], axis=1)
+
+
+def lights_in_clusters(mn, mx, centres, radius, point):
+    """is_light_in_cluster (:108-119) for every (cluster, light) pair -> bool[clusters, lights]: a non-point light is in
+    every cluster; a point light by aabb_sphere_test, whose sum the binary compiles to sqr_dist = fma(d, d, sqr_dist)."""
+    with np.errstate(all="ignore"):
+        sq = np.zeros((len(mn), len(centres)), F)
+        for i in range(3):
+            v = centres[None, :, i]
+            for inside, d in ((v < mn[:, i:i + 1], mn[:, i:i + 1] - v), (v > mx[:, i:i + 1], v - mx[:, i:i + 1])):
+                if inside.any():
+                    d = np.broadcast_to(d.astype(F), sq.shape)[inside]
+                    sq[inside] = fma32(d, d, sq[inside])
+        r = np.asarray(radius, F)
+        return ~np.asarray(point, bool)[None, :] | (sq <= (r * r).astype(F)[None, :])
+
+
+def cluster_assign(info, unique, bounds, lights, light_index_capacity, total_clusters, max_lights_per_cluster=256):
+    """light_culling.comp:121-151 for the compacted list `unique`, ranges allocated in list order (the oracle's
+    canonical order of the atomicAdd): the first min(count, 256) hits of every cluster in light order.  Returns
+    (index buffer with its light_count header, (offset, count) image, the UNCAPPED count of every listed cluster,
+    indices dropped past light_index_capacity)."""
+    unique = np.asarray(unique, np.uint8)
+    n = int(unique[12:16].view(np.uint32)[0])
+    act = unique[16:16 + 4 * n].view(np.uint32)
+    nl = int(_field(info, "global_light_count"))
+    lights = np.asarray(lights)[:nl]
+    centres = light_view_centres(info, lights)
+    point = lights["light_type"] == L.LIGHT_TYPE_POINT
+    hits = np.zeros((n, nl), bool)
+    step = max(1, (1 << 21) // max(nl, 1))
+    for c0 in range(0, n, step):
+        mn, mx = cluster_aabb(info, bounds, act[c0:c0 + step])
+        hits[c0:c0 + step] = lights_in_clusters(mn, mx, centres, lights["outer_radius"], point)
+    count = hits.sum(axis=1).astype(np.int64)
+    capped = np.minimum(count, max_lights_per_cluster)
+    kept = hits & (np.cumsum(hits, axis=1) <= max_lights_per_cluster)
+    indices = np.nonzero(kept)[1].astype(np.uint32)  # row-major: cluster by cluster in list order, ascending lights
+    offsets = np.cumsum(capped) - capped
+    out = np.zeros(4 + 4 * light_index_capacity, np.uint8)
+    out[:4] = np.array([int(capped.sum())], np.uint32).view(np.uint8)
+    kept_n = min(len(indices), light_index_capacity)
+    out[4:4 + 4 * kept_n] = indices[:kept_n].view(np.uint8)
+    img = np.zeros((total_clusters, 2), np.uint32)
+    img[act, 0], img[act, 1] = offsets, capped
+    return out, img, count, len(indices) - kept_n

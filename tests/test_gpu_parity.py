@@ -486,12 +486,29 @@ def cluster_inputs(oracle, seed, W, H, n_lights, tile_px=8, z_slices=32, far=200
     return push, depth, info, lights
 
 
-@pytest.mark.parametrize("W,H,n_lights,tile,zs,samples,pf", [
+LIGHT_CLUSTER_SHAPES = [  # (W, H, n_lights, tile, z slices, samples, point fraction); tests/test_oracle_cpu.py reuses them
     (320, 180, 200, 8, 32, 1, 1.0), (333, 187, 64, 16, 24, 1, 0.9), (256, 128, 300, 8, 32, 4, 1.0),
     (1920, 1080, 1000, 8, 32, 1, 1.0), (64, 64, 0, 8, 8, 1, 1.0), (200, 120, 40, 64, 32, 1, 1.0),
     # tile sizes that are not powers of two (the mark launch's lane geometry has a shift form and a division form), with
     # and without several samples; a tile of fewer than 64 samples and one of more than 64
-    (330, 190, 100, 12, 32, 1, 1.0), (200, 100, 50, 6, 16, 2, 1.0), (150, 90, 30, 5, 32, 1, 0.9), (97, 61, 20, 3, 7, 4, 1.0)])
+    (330, 190, 100, 12, 32, 1, 1.0), (200, 100, 50, 6, 16, 2, 1.0), (150, 90, 30, 5, 32, 1, 0.9), (97, 61, 20, 3, 7, 4, 1.0)]
+# the saturation cases of test_light_clusters_many_lights_and_saturated_clusters: (..., radius scale)
+LIGHT_CLUSTER_SATURATED = [(192, 108, 9000, 8, 32, 1, 0.98, 1.0), (128, 72, 5000, 16, 16, 1, 1.0, 12.0)]
+
+
+def poison_cluster_inputs(depth, lights):
+    """NaN / inf / negative / out-of-range depth samples and non-finite light positions and radii, in place."""
+    rng = np.random.default_rng(4)
+    flat = depth.reshape(-1)
+    for val in (np.nan, np.inf, -np.inf, -0.25, 0.0, 1.0, 3.0):
+        flat[rng.integers(0, len(flat), 200)] = val
+    if len(lights) > 22:
+        for k, val in enumerate((np.nan, np.inf, -np.inf)):
+            lights["position"][10 + k, k % 3] = val
+        lights["outer_radius"][20], lights["outer_radius"][21], lights["outer_radius"][22] = np.nan, np.inf, 0.0
+
+
+@pytest.mark.parametrize("W,H,n_lights,tile,zs,samples,pf", LIGHT_CLUSTER_SHAPES)
 def test_light_clusters(torch_mod, engine, oracle, W, H, n_lights, tile, zs, samples, pf):
     _light_clusters(torch_mod, engine, oracle, W, H, n_lights, tile, zs, samples, pf, poison=False)
 
@@ -505,8 +522,9 @@ def test_light_clusters_with_non_finite_inputs(torch_mod, engine, oracle):
 def test_light_clusters_many_lights_and_saturated_clusters(torch_mod, engine, oracle):
     """More lights than one filter tile holds (the device filters 4096 lights per step) and radii large enough that
     clusters exceed the 256-light cap (light_culling.comp:135): counts saturate, lists keep the first 256 in order."""
-    _light_clusters(torch_mod, engine, oracle, 192, 108, 9000, 8, 32, 1, 0.98, poison=False, radius_scale=1.0)
-    _light_clusters(torch_mod, engine, oracle, 128, 72, 5000, 16, 16, 1, 1.0, poison=False, radius_scale=12.0)
+    for W, H, n_lights, tile, zs, samples, pf, radius_scale in LIGHT_CLUSTER_SATURATED:
+        _light_clusters(torch_mod, engine, oracle, W, H, n_lights, tile, zs, samples, pf, poison=False,
+                        radius_scale=radius_scale)
 
 
 def test_light_clusters_config4_full_size(torch_mod, engine, oracle):
@@ -527,14 +545,7 @@ def _light_clusters(torch_mod, engine, oracle, W, H, n_lights, tile, zs, samples
     if radius_scale is not None:
         lights["outer_radius"] *= np.float32(radius_scale)
     if poison:
-        rng = np.random.default_rng(4)
-        flat = depth.reshape(-1)
-        for val in (np.nan, np.inf, -np.inf, -0.25, 0.0, 1.0, 3.0):
-            flat[rng.integers(0, len(flat), 200)] = val
-        if len(lights) > 22:
-            for k, val in enumerate((np.nan, np.inf, -np.inf)):
-                lights["position"][10 + k, k % 3] = val
-            lights["outer_radius"][20], lights["outer_radius"][21], lights["outer_radius"][22] = np.nan, np.inf, 0.0
+        poison_cluster_inputs(depth, lights)
     cc = [int(v) for v in push["cluster_count"]]
     total = cc[0] * cc[1] * cc[2]
     # mark

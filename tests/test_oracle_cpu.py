@@ -401,6 +401,66 @@ def test_cluster_lists_serve_the_fragment_shader_walk(oracle):
     assert checked > 1500 and inside > 50  # the property was exercised, not vacuous
 
 
+def _cluster_assign_both(oracle, W, H, n_lights, tile, zs, samples, pf, radius_scale=None, poison=False, cut=None):
+    """The oracle's light assignment and tests/np_restatement.py's on the inputs of test_gpu_parity.py::_light_clusters:
+    index buffer, (offset, count) image and dropped count compared bit for bit; returns the restatement's uncapped counts."""
+    from test_gpu_parity import cluster_inputs, poison_cluster_inputs
+
+    push, depth, info, lights = cluster_inputs(oracle, 4, W, H, n_lights, tile, zs, samples=samples, point_fraction=pf)
+    if radius_scale is not None:
+        lights["outer_radius"] *= np.float32(radius_scale)
+    if poison:
+        poison_cluster_inputs(depth, lights)
+    cc = [int(v) for v in push["cluster_count"]]
+    total = cc[0] * cc[1] * cc[2]
+    masks, bounds = oracle.cluster_mark(push, depth)
+    unique, _ = oracle.cluster_compact(cc, masks, total)
+    na = int(unique[12:16].view(np.uint32)[0])
+    act = unique[16:16 + 4 * na].view(np.uint32)
+    mn, mx = npr.cluster_aabb(info, bounds, act)
+    for k in range(0, na, max(1, na // 40)):  # the boxes themselves, bit for bit (NaN boxes included)
+        omn, omx = oracle.cluster_aabb(info, bounds, int(act[k]))
+        assert np.array_equal(omn.view(np.uint32), mn[k].view(np.uint32)) and np.array_equal(omx.view(np.uint32), mx[k].view(np.uint32))
+    cap = 256 * na + 16 if cut is None else cut
+    ol, oimg, odrop = oracle.cluster_assign(info, unique, bounds, lights, cap, total)
+    nl, nimg, count, ndrop = npr.cluster_assign(info, unique, bounds, lights, cap, total)
+    assert odrop == ndrop and np.array_equal(ol, nl), "light index lists differ"
+    assert np.array_equal(oimg, nimg), "(offset, count) images differ"
+    assert np.array_equal(np.minimum(count, 256), oimg[act, 1])
+    return count, int(ol[:4].view(np.uint32)[0])
+
+
+@pytest.mark.parametrize("W,H,n_lights,tile,zs,samples,pf", [
+    s for s in __import__("test_gpu_parity").LIGHT_CLUSTER_SHAPES if s[0] * s[1] <= 400 * 200])
+def test_np_cluster_assign_equals_oracle(oracle, W, H, n_lights, tile, zs, samples, pf):
+    """light_culling.comp restated in numpy over (cluster, light) pairs against oracle_cluster_assign, on
+    test_gpu_parity.py::test_light_clusters' shapes up to 400x200."""
+    count, n_idx = _cluster_assign_both(oracle, W, H, n_lights, tile, zs, samples, pf)
+    assert n_idx == int(count.sum()) and (n_lights < 200 or n_idx > 0)
+
+
+def test_np_cluster_assign_equals_oracle_on_non_finite_inputs(oracle):
+    """test_light_clusters_with_non_finite_inputs' scene: NaN / inf depth samples (NaN boxes) and NaN / inf light
+    positions and radii."""
+    count, _ = _cluster_assign_both(oracle, 320, 180, 300, 8, 32, 1, 0.95, poison=True)
+    assert count.max() > 0
+
+
+@pytest.mark.parametrize("W,H,n_lights,tile,zs,samples,pf,radius_scale", __import__("test_gpu_parity").LIGHT_CLUSTER_SATURATED)
+def test_np_cluster_assign_equals_oracle_when_saturated(oracle, W, H, n_lights, tile, zs, samples, pf, radius_scale):
+    """The many-lights scenes: 9 000 lights (more than 160 hits per cluster), and 12x radii whose uncapped counts pass
+    256, where the lists keep the first 256 hits in light order — also with the index buffer cut inside the range of
+    the longest list."""
+    count, n_idx = _cluster_assign_both(oracle, W, H, n_lights, tile, zs, samples, pf, radius_scale=radius_scale)
+    assert count.max() > 160
+    if radius_scale > 1.0:
+        assert (count > 256).sum() > 1
+    capped = np.minimum(count, 256)
+    first = int(np.argmax(count))
+    start = int(capped[:first].sum())
+    _cluster_assign_both(oracle, W, H, n_lights, tile, zs, samples, pf, radius_scale=radius_scale, cut=start + 100)
+
+
 def test_config1_sphere_frustum(oracle):
     """BASELINE.json configs[0]: 8k spheres, frustum only (plumbing, CPU)."""
     n = 8192

@@ -115,6 +115,59 @@ def test_oracle_equals_the_cluster_binaries(oracle, cluster_vectors, name):
     assert np.array_equal(oimg[active], c["spv_offset_image"][active])
 
 
+# the two binaries at the other shapes the product serves (make_spirv_vectors.py cluster_shapes, CLUSTER_SHAPES there):
+# partial edge tiles, 3 / 5 / 12 / 16-px tiles, 7 / 16 / 24 slices, 2 and 4 samples, no lights, several workgroups,
+# saturated clusters with directional lights among the kept 256, non-finite light positions and radii
+CLUSTER_SHAPES_GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spirv_cluster_shapes.npz")
+CLUSTER_SHAPE_CASES = ["edge12_sat", "t5_z7_ms2", "t3_z16_ms4", "t16_none", "t16_poison"]
+
+
+@pytest.fixture(scope="module")
+def cluster_shape_vectors():
+    return np.load(CLUSTER_SHAPES_GOLD)
+
+
+def test_the_shape_cases_cover_what_they_are_for(cluster_shape_vectors):
+    cs = {n: load_cluster_case(cluster_shape_vectors, n) for n in CLUSTER_SHAPE_CASES}
+    tiles = {int(c["push"]["tile_size_px"]) for c in cs.values()}
+    slices = {int(c["push"]["cluster_count"][2]) for c in cs.values()}
+    samples = {int(c["push"]["depth_buffer_sample_count"]) for c in cs.values()}
+    assert {3, 5, 12, 16} <= tiles and {7, 16, 24} <= slices and {2, 4} <= samples
+    counts = {}
+    for name, c in cs.items():
+        na = int(c["unique"][12:16].view(np.uint32)[0])
+        active = c["unique"][16:16 + 4 * na].view(np.uint32)
+        counts[name] = (na, c["spv_offset_image"][active, 1], int(c["spv_light_list"][:4].view(np.uint32)[0]))
+    assert counts["t16_none"][2] == 0 and len(cs["t16_none"]["lights"]) == 0
+    assert max(na for na, _, _ in counts.values()) > 256  # several light_culling workgroups
+    sat = counts["edge12_sat"][1]
+    assert (sat == 256).sum() >= 3 and ((sat > 64) & (sat < 256)).any() and ((sat > 16) & (sat <= 64)).any()
+    assert not np.isfinite(cs["t16_poison"]["lights"]["position"]).all()
+
+
+@pytest.mark.parametrize("name", CLUSTER_SHAPE_CASES)
+def test_oracle_equals_the_cluster_binaries_at_other_shapes(oracle, cluster_shape_vectors, name):
+    """As test_oracle_equals_the_cluster_binaries, on tests/golden/spirv_cluster_shapes.npz."""
+    c = load_cluster_case(cluster_shape_vectors, name)
+    om, ob = oracle.cluster_mark(c["push"], c["depth"])
+    assert np.array_equal(om, c["spv_masks"]) and np.array_equal(ob, c["spv_bounds"])
+    cc = [int(v) for v in c["push"]["cluster_count"]]
+    total = cc[0] * cc[1] * cc[2]
+    ou, dropped = oracle.cluster_compact(cc, om, total)
+    na = int(ou[12:16].view(np.uint32)[0])
+    assert dropped == 0 and na > 0 and np.array_equal(ou[:16 + 4 * na], c["unique"])
+    want = [x + y * cc[0] + z * cc[0] * cc[1] for z in range(cc[2]) for y in range(cc[1]) for x in range(cc[0])
+            if (int(c["spv_masks"][x + y * cc[0]]) >> z) & 1]
+    assert ou[16:16 + 4 * na].view(np.uint32).tolist() == want
+    nl = int(c["spv_light_list"][:4].view(np.uint32)[0])
+    ol, oimg, dropped = oracle.cluster_assign(c["info"], ou, ob, c["lights"], 256 * na + 16, total)
+    assert dropped == 0 and int(ol[:4].view(np.uint32)[0]) == nl
+    assert np.array_equal(ol[:4 + 4 * nl], c["spv_light_list"])
+    active = ou[16:16 + 4 * na].view(np.uint32)
+    assert np.array_equal(oimg[active], c["spv_offset_image"][active])
+    assert int(oimg[active, 1].sum()) == nl and (oimg[active, 1] <= 256).all()
+
+
 # ----------------------------------------------------------------------------- depth_reduce.comp.spv, compaction binary
 PYR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spirv_pyramid.npz")
 COMPACT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spirv_compact.npz")

@@ -177,3 +177,60 @@ def test_product_compaction_equals_the_binary_as_a_multiset(torch_mod, name):
     ids = got[16:16 + 4 * n].view(np.uint32)
     assert np.array_equal(ids, np.sort(spv[16:16 + 4 * n].view(np.uint32))) and (np.diff(ids.astype(np.int64)) > 0).all()
     eng.close()
+
+
+# ----------------------------------------------------------------------------- light clusters at the other shapes
+from test_spirv_vectors_cpu import CLUSTER_SHAPE_CASES, CLUSTER_SHAPES_GOLD, load_cluster_case  # noqa: E402
+
+
+@pytest.mark.parametrize("max_lights", ["exact", 4096])
+@pytest.mark.parametrize("name", CLUSTER_SHAPE_CASES)
+def test_product_equals_the_cluster_binaries_at_other_shapes(torch_mod, name, max_lights):
+    """cluster_mark / cluster_compact / cluster_assign, and compute_clusters, against the binaries' outputs at the shapes
+    of tests/golden/spirv_cluster_shapes.npz.  The Engine's max_lights sets the coarse segment size (abi.hip:
+    round64(ceil(max_lights / 16))): "exact" makes the light count equal to max_lights, 4096 puts every light of these
+    cases into the first few segments."""
+    from orbit_amd.engine import Engine
+
+    torch = torch_mod
+    c = load_cluster_case(np.load(CLUSTER_SHAPES_GOLD), name)
+    cc = [int(v) for v in c["push"]["cluster_count"]]
+    total = cc[0] * cc[1] * cc[2]
+    n_lights = len(c["lights"])
+    assert int(c["info"]["global_light_count"]) == n_lights
+    eng = Engine(0, max_lights=max(n_lights, 1) if max_lights == "exact" else max_lights, max_clusters=total)
+    lights = dev(torch, c["lights"]) if n_lights else None
+    depth = dev(torch, c["depth"])
+    na = int(c["unique"][12:16].view(np.uint32)[0])
+    active = c["unique"][16:16 + 4 * na].view(np.uint32)
+    nl = int(c["spv_light_list"][:4].view(np.uint32)[0])
+    lcap = 256 * na + 16
+
+    def check(gm, gb, gu, gl, gimg):
+        assert np.array_equal(host(gm, np.uint32), c["spv_masks"]), "tile slice masks differ"
+        assert np.array_equal(host(gb, np.uint32).reshape(-1, 2), c["spv_bounds"]), "depth bounds differ"
+        assert np.array_equal(host(gu)[:16 + 4 * na], c["unique"]), "compacted list differs"
+        assert np.array_equal(host(gl)[:4 + 4 * nl], c["spv_light_list"]), "light index lists differ"
+        assert bool((host(gl)[4 + 4 * nl:] == 0xEE).all()), "written past the light list"
+        img = host(gimg, np.uint32).reshape(-1, 2)
+        assert np.array_equal(img[active], c["spv_offset_image"][active]), "(offset, count) image differs"
+
+    gm = torch.full((cc[0] * cc[1],), 0x7FFFFFFF, dtype=torch.int32, device="cuda")
+    gb = torch.full((total, 2), 0x7FFFFFFF, dtype=torch.int32, device="cuda")
+    eng.cluster_mark(c["push"], depth, gm, gb)
+    gu = torch.full((L.COMPACT_HEADER + 4 * total,), 0xEE, dtype=torch.uint8, device="cuda")
+    eng.cluster_compact(cc, gm, gu, total)
+    gl = torch.full((L.LIGHT_INDEX_HEADER + 4 * lcap,), 0xEE, dtype=torch.uint8, device="cuda")
+    gimg = torch.zeros((total, 2), dtype=torch.int32, device="cuda")
+    eng.cluster_assign(c["info"], gu, gb, lights, gl, lcap, gimg)
+    torch.cuda.synchronize()
+    eng.status()
+    check(gm, gb, gu, gl, gimg)
+    # the three stages behind one call
+    gm2, gb2 = torch.full_like(gm, 0x55), torch.full_like(gb, 0x55)
+    gu2, gl2, gimg2 = torch.full_like(gu, 0xEE), torch.full_like(gl, 0xEE), torch.zeros_like(gimg)
+    eng.compute_clusters(c["push"], c["info"], depth, lights, gm2, gb2, gu2, total, gl2, lcap, gimg2)
+    torch.cuda.synchronize()
+    eng.status()
+    check(gm2, gb2, gu2, gl2, gimg2)
+    eng.close()
