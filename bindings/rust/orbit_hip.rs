@@ -39,6 +39,17 @@ pub struct OrbitFrameLate {
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct OrbitEntityTransform { pub position: [f32; 3], pub orientation: [f32; 4], pub scale: [f32; 3] }
 
+/// orbit_cull_stats' 256-B block of u64 counters (include/orbit_abi_ext.h OrbitCullStats)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitCullStats {
+    pub entities: u64, pub entity_skipped_prev_invisible: u64, pub entity_frustum_culled: u64,
+    pub entity_occlusion_culled: u64, pub entity_drawn_in_early_pass: u64, pub entity_drawn: u64, pub records: u64,
+    pub reserved0: u64, pub lod_drawn: [u64; 8],
+    pub meshlets: u64, pub meshlet_skipped_prev_invisible: u64, pub meshlet_frustum_culled: u64,
+    pub meshlet_cone_culled: u64, pub meshlet_occlusion_culled: u64, pub meshlet_alpha_filtered: u64,
+    pub meshlet_drawn_in_early_pass: u64, pub meshlet_drawn: u64, pub reserved1: [u64; 8],
+}
+
 /// push-constant order of shaders/entity_cull.comp:17-23 (== draw_gen.rs:372-376)
 #[repr(C)]
 pub struct OrbitEntityCullBufs {
@@ -201,6 +212,11 @@ extern "C" {
     pub fn orbit_scene_update_entities(ctx: *mut OrbitCtx, transforms: *const OrbitEntityTransform,
                                        instance_indices: *const u32, count: u32, entity_data: *mut c_void,
                                        entity_capacity: u32, stream: *mut c_void) -> i32;
+    /// What orbit_entity_cull + orbit_meshlet_cull with these arguments would do, counted per test into a DEVICE
+    /// OrbitCullStats (overwritten).  Call it BEFORE the cull: passes 1 and 2 rewrite the visibility words it reads.
+    pub fn orbit_cull_stats(ctx: *mut OrbitCtx, cull_info: *const c_void, ebufs: *const OrbitEntityCullBufs,
+                            entity_draw_count: u32, mbufs: *const OrbitMeshletCullBufs, stats: *mut OrbitCullStats,
+                            stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

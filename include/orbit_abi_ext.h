@@ -13,7 +13,8 @@
  *   - the sharded engine: the shard cull, the record list, its device-side exchanges (HIP-IPC stores; RCCL all-gather)
  *     and the expansion of a gathered list,
  *   - the measurement hook of bench.py,
- *   - the scene update: model and normal matrices computed on the device from entity transforms.
+ *   - the scene update: model and normal matrices computed on the device from entity transforms,
+ *   - cull statistics: every entity and meshlet of a cull counted by the first test that rejected it.
  * A build that only needs the drop-in includes orbit_abi.h alone; liborbit_cull.so exports both sets.
  */
 #ifndef ORBIT_ABI_EXT_H
@@ -471,6 +472,92 @@ ORBIT_STATIC_ASSERT(sizeof(OrbitEntityTransform) == 40, "EntityTransform is 40 B
 int32_t orbit_scene_update_entities(OrbitCtx *ctx, const OrbitEntityTransform *transforms,
                                     const uint32_t *instance_indices, uint32_t count,
                                     OrbitEntityData *entity_data, uint32_t entity_capacity, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* Cull statistics.  The cull returns survivors only (dispatch records,     */
+/* draw commands, visibility bits); orbit_cull_stats counts, on the device, */
+/* what it did with every entity-draw and every meshlet: each is counted    */
+/* ONCE, by the first reason in the shaders' own order of evaluation        */
+/* (shaders/entity_cull.comp:106-230, meshlet_cull.comp:108-214).           */
+/*                                                                          */
+/* Contract: *stats is OVERWRITTEN with what                                */
+/*     orbit_entity_cull(ctx, cull_info, ebufs, entity_draw_count, stream)  */
+/*     orbit_meshlet_cull(ctx, cull_info, mbufs, stream)                    */
+/* would do if they were enqueued NEXT on the same stream, with the same    */
+/* arguments and under the context's current dispatch_size and             */
+/* arith_profile (the classes are the cull's own in either profile).       */
+/* CALL IT BEFORE THE CULL: passes 1 and 2 rewrite the visibility words the */
+/* counts depend on.  The call reads what those two calls read, except      */
+/* mbufs->meshlet_dispatch_buffer: the meshlet stage's records are worked   */
+/* out from the entity stage itself (the pointer must still be non-NULL,    */
+/* as for the cull).  It writes *stats and nothing else — no visibility     */
+/* word, no dispatch or draw buffer, no latched status (only its own        */
+/* argument errors are returned).  The meshlets are read from the caller's  */
+/* 32-B Meshlet buffer; a bound meshlet stream holds the same bits, so the  */
+/* counts hold for every cull path.                                         */
+/* Served: caps.dispatch_size 32, occlusion passes 0, 1 and 2, both         */
+/* projections.  Refused like the culls refuse (same checks, same codes):   */
+/*   ORBIT_E_INVALID  dispatch_size != 32, projection_type > 1, stats NULL  */
+/*                    or not 8-B aligned, NULL bufs / cull_info            */
+/*   ORBIT_E_PLANES   cull_plane_count > 12                                 */
+/*   ORBIT_E_MISSING  a buffer a cull requires is NULL (pyramid, visibility */
+/*                    buffers of the occlusion passes)                      */
+/*   ORBIT_E_CAPACITY entity_draw_count > caps.max_entities, dispatch       */
+/*                    capacity > caps.max_dispatches                        */
+/* The call allocates nothing and never synchronises the host: a graph can  */
+/* capture it on its first call.  The counters are cleared on the stream    */
+/* and summed with 64-bit device atomics: the result is deterministic.      */
+/*                                                                          */
+/* Invariants (every counter is uncapped: dispatch_capacity and            */
+/* draw_capacity cut the cull's OUTPUT, not these counts):                 */
+/*   entities == entity_skipped_prev_invisible + entity_frustum_culled +    */
+/*               entity_occlusion_culled + entity_drawn_in_early_pass +     */
+/*               entity_drawn                                               */
+/*   sum(lod_drawn) == entity_drawn                                         */
+/*   meshlets == meshlet_skipped_prev_invisible + meshlet_frustum_culled +  */
+/*               meshlet_cone_culled + meshlet_occlusion_culled +           */
+/*               meshlet_alpha_filtered + meshlet_drawn_in_early_pass +     */
+/*               meshlet_drawn                                              */
+/*   records == the workgroup_count_x the entity cull writes                */
+/*              (records > dispatch_capacity: the cull drops the rest and   */
+/*              latches ORBIT_E_CAPACITY)                                   */
+/*   meshlet_drawn == the cull's command count whenever neither capacity is */
+/*              exceeded (meshlet_drawn > draw_capacity: commands dropped)  */
+/* ------------------------------------------------------------------------ */
+typedef struct OrbitCullStats {
+    /* entity stage: entity-draws evaluated (gID < min(in-buffer count, 256 * ceil(entity_draw_count / 256)), :106) */
+    uint64_t entities;
+    uint64_t entity_skipped_prev_invisible; /* pass 1: not visible last frame (:123) */
+    uint64_t entity_frustum_culled;         /* a cull plane (:137-144) */
+    uint64_t entity_occlusion_culled;       /* pass 2: the HiZ test (:147-191) */
+    uint64_t entity_drawn_in_early_pass;    /* pass 2: visible now and last frame, no meshlet occlusion (:198-200) */
+    uint64_t entity_drawn;                  /* records emitted for it (:203) */
+    uint64_t records;                       /* MeshletDispatch records of the drawn entities: ceil(meshlets / 32) each */
+    uint64_t reserved0;
+    uint64_t lod_drawn[8];                  /* entity_drawn by the LOD whose MeshLod was used (min(lod, lod_count - 1)) */
+    /* meshlet stage, over the meshlets of the records above */
+    uint64_t meshlets;
+    uint64_t meshlet_skipped_prev_invisible; /* pass 1 with meshlet occlusion: not visible last frame (:137) */
+    uint64_t meshlet_frustum_culled;         /* a cull plane (:139-146) */
+    uint64_t meshlet_cone_culled;            /* the normal cone (:148-158) */
+    uint64_t meshlet_occlusion_culled;       /* pass 2 with meshlet occlusion: the HiZ test (:161-205) */
+    uint64_t meshlet_alpha_filtered;         /* visible, but (1 << alpha_mode) & alpha_mode_flag == 0 (:207) */
+    uint64_t meshlet_drawn_in_early_pass;    /* pass 2 with meshlet occlusion, alpha mode not in noskip_alphamode, visible
+                                                last frame: drawn by pass 1 (:210-213; the alpha flag is not consulted) */
+    uint64_t meshlet_drawn;                  /* a draw command (:215) */
+    uint64_t reserved1[8];
+} OrbitCullStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitCullStats) == 256, "CullStats is 256 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitCullStats, records) == 48, "records @48");
+ORBIT_STATIC_ASSERT(offsetof(OrbitCullStats, lod_drawn) == 64, "lod_drawn @64");
+ORBIT_STATIC_ASSERT(offsetof(OrbitCullStats, meshlets) == 128, "meshlets @128");
+ORBIT_STATIC_ASSERT(offsetof(OrbitCullStats, meshlet_drawn) == 184, "meshlet_drawn @184");
+ORBIT_STATIC_ASSERT(offsetof(OrbitCullStats, reserved1) == 192, "reserved1 @192");
+
+/* *stats (DEVICE, 8-B aligned) = the counts of orbit_entity_cull + orbit_meshlet_cull with these arguments; see above */
+int32_t orbit_cull_stats(OrbitCtx *ctx, const OrbitGpuCullInfo *cull_info, const OrbitEntityCullBufs *ebufs,
+                         uint32_t entity_draw_count, const OrbitMeshletCullBufs *mbufs, OrbitCullStats *stats,
+                         void *stream);
 
 #ifdef __cplusplus
 }

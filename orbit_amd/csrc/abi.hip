@@ -215,11 +215,12 @@ MeshletStreamView stream_view_for(OrbitMeshletStream *ms, const void *meshlet_bu
 }
 
 // The mesh side table an entity cull of `mesh_info_buffer` may read: only the one derived from that very buffer.
-MeshSideView mesh_side_for(OrbitMeshletStream *ms, const void *mesh_info_buffer) {
+// (count: the call is a cull — orbit_cull_stats reads the table without being one)
+MeshSideView mesh_side_for(OrbitMeshletStream *ms, const void *mesh_info_buffer, bool count = true) {
     if (!ms) return MeshSideView{nullptr, 0u};
     std::lock_guard<std::mutex> lock(ms->mu);
     if (ms->mesh_side == nullptr || ms->mesh_source != mesh_info_buffer || ms->mesh_hi == 0u) return MeshSideView{nullptr, 0u};
-    ms->mesh_side_culls++;
+    if (count) ms->mesh_side_culls++;
     return MeshSideView{ms->mesh_side, ms->mesh_hi};
 }
 
@@ -614,7 +615,7 @@ int32_t orbit_debug_read_cluster_tests(OrbitCtx *ctx, unsigned long long out[8])
 // (`ctx` itself, or one of its view children), errors are reported on `ctx`.  Caller holds ctx->mu.
 static int32_t entity_cull_params(OrbitCtx *ctx, OrbitCtx *scratch, const OrbitGpuCullInfo *ci,
                                   const OrbitEntityCullBufs *b, uint32_t draw_first, uint32_t entity_draw_count,
-                                  bool exact_range, EntityCullParams &p) {
+                                  bool exact_range, EntityCullParams &p, bool is_cull = true) {
     int32_t rc = check_cull_info(ctx, ci);
     if (rc) return rc;
     if (ctx->rec_shift > 5u && ci->occlusion_pass != 0)
@@ -638,7 +639,7 @@ static int32_t entity_cull_params(OrbitCtx *ctx, OrbitCtx *scratch, const OrbitG
     p.ci = *ci;
     p.entity_draw_buffer = (const uint8_t *)b->entity_draw_buffer;
     p.mesh_infos = (const OrbitMeshInfo *)b->mesh_info_buffer;
-    p.mesh_side = mesh_side_for(ctx->meshlet_stream, b->mesh_info_buffer);
+    p.mesh_side = mesh_side_for(ctx->meshlet_stream, b->mesh_info_buffer, is_cull);
     p.dispatch_buffer = (uint8_t *)b->meshlet_dispatch_buffer;
     p.entities = (const OrbitEntityData *)b->entity_buffer;
     p.visibility = b->visibility_buffer;
@@ -2010,6 +2011,31 @@ int32_t orbit_scene_update_entities(OrbitCtx *ctx, const OrbitEntityTransform *t
     const hipError_t e = launch_scene_update_entities(transforms, instance_indices, count, entity_data, entity_capacity,
                                                       ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch scene_update_entities");
+    return ORBIT_OK;
+}
+
+// ------------------------------------------------------------- cull statistics
+// What orbit_entity_cull + orbit_meshlet_cull with these arguments would do, counted (cull_stats.hip).  Validated by the
+// culls' own parameter blocks, so it refuses what they refuse with their codes; the meshlet stage's block is the Meshlet-
+// buffer evaluation's (no stream, no class path — the stream holds the same bits).  No allocation, no scratch, no host
+// sync: capturable on the first call.
+int32_t orbit_cull_stats(OrbitCtx *ctx, const OrbitGpuCullInfo *cull_info, const OrbitEntityCullBufs *ebufs,
+                         uint32_t entity_draw_count, const OrbitMeshletCullBufs *mbufs, OrbitCullStats *stats,
+                         void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    if (!stats || ((uintptr_t)stats & 7u)) return fail(ctx, ORBIT_E_INVALID, "cull_stats: stats is NULL or not 8-B aligned");
+    if (ctx->rec_shift != 5u)
+        return fail(ctx, ORBIT_E_INVALID, "cull_stats serves dispatch_size 32; this context has %u", ctx->caps.dispatch_size);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    CullStatsParams p;
+    int32_t rc = entity_cull_params(ctx, ctx, cull_info, ebufs, 0u, entity_draw_count, false, p.e, false);
+    if (rc) return rc;
+    rc = meshlet_cull_params(ctx, ctx, cull_info, mbufs, nullptr, false, nullptr, 0u, 0u, p.m);
+    if (rc) return rc;
+    p.m.ms = MeshletStreamView{};
+    p.stats = reinterpret_cast<unsigned long long *>(stats);
+    const hipError_t e = launch_cull_stats(p, ctx->num_cus, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch cull_stats");
     return ORBIT_OK;
 }
 

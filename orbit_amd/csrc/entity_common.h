@@ -10,15 +10,25 @@ namespace {
 
 constexpr int kEntityBlock = 256; // entity-draws per block of every entity launch (one thread each)
 
+// What entity_eval_one decided for an entity-draw, by the first test that rejected it (orbit_cull_stats, cull_stats.hip);
+// the culls pass none, and nothing of it is computed for them.
+enum : uint32_t { kEntNone = 0, kEntSkipped, kEntFrustum, kEntOcclusion, kEntEarly, kEntDrawn };
+struct EntityVerdict {
+    uint32_t cls; // kEnt*: kEntNone for an inactive invocation
+    uint32_t lod; // kEntDrawn: the LOD whose MeshLod was read (after lod_count - 1 and ORBIT_MAX_MESH_LODS - 1)
+};
+
 // The shader body up to the record emission for entity-draw `g` (:106-209): the proto-record (meshlet_count == 0 when
 // nothing is drawn) and `visible` for the pass-2 bitset.
 // P: EntityCullParams, or any block with its ci / entity_draw_buffer / mesh_infos / entities / visibility / pyr.
 template <class P>
-__device__ __forceinline__ OrbitMeshletDispatch entity_eval_one(const P &p, uint32_t g, bool active, bool &visible) {
+__device__ __forceinline__ OrbitMeshletDispatch entity_eval_one(const P &p, uint32_t g, bool active, bool &visible,
+                                                                EntityVerdict *verdict = nullptr) {
     const OrbitGpuCullInfo &ci = p.ci;
     const bool meshlet_occ = ci.meshlet_visibility_buffer != ORBIT_NONE;
     visible = false;
     OrbitMeshletDispatch pr = {0u, 0u, 0u, 0u};
+    if (verdict) verdict->cls = kEntNone, verdict->lod = 0u;
     if (active) {
         const OrbitEntityDraw *draws =
             reinterpret_cast<const OrbitEntityDraw *>(p.entity_draw_buffer + ORBIT_ENTITY_DRAW_HEADER);
@@ -61,11 +71,16 @@ __device__ __forceinline__ OrbitMeshletDispatch entity_eval_one(const P &p, uint
         const float scale = sqrtf(gmax(dx, gmax(dy, dz)));
         s.r = bs.w * scale;
 
+        const bool gated = visible;
         if (visible) visible = plane_test(ci, s);                                        // :137-144
+        const bool in_frustum = visible;
         if (ci.occlusion_pass == 2 && visible) visible = occlusion_test(ci, s, bs.w, scale, p.pyr);  // :147-191
 
         bool should_draw = visible;
         if (ci.occlusion_pass == 2) should_draw = visible && (!visible_in_buffer || meshlet_occ); // :198-200
+        if (verdict)
+            verdict->cls = !gated ? kEntSkipped : !in_frustum ? kEntFrustum : !visible ? kEntOcclusion
+                         : !should_draw ? kEntEarly : kEntDrawn;
 
         if (should_draw) { // :203-209
             const float ex = ci.lod_target_pos_view_space[0] - s.x;
@@ -79,6 +94,7 @@ __device__ __forceinline__ OrbitMeshletDispatch entity_eval_one(const P &p, uint
             lod = min(lod, (uint32_t)ORBIT_MAX_MESH_LODS - 1u);
             OrbitMeshLod ml = {side_b.y, side_b.z};
             if (!side || lod != 0u) ml = mi->mesh_lods[lod];
+            if (verdict) verdict->lod = lod;
             pr.entity_index = ed.entity_index;
             pr.meshlet_offset = ml.meshlet_offset;
             pr.meshlet_count = ml.meshlet_count;

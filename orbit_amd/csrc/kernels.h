@@ -360,6 +360,17 @@ hipError_t launch_meshlet_stream_validate(const OrbitMeshlet *meshlets, const Me
 hipError_t launch_scene_update_entities(const OrbitEntityTransform *transforms, const uint32_t *instance_indices,
                                         uint32_t count, OrbitEntityData *entity_data, uint32_t entity_capacity,
                                         int32_t *status, hipStream_t s);
+// cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
+// Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
+struct CullStatsParams {
+    EntityCullParams e;
+    MeshletCullParams m;
+    unsigned long long *stats; // OrbitCullStats, 8-B aligned
+};
+hipError_t launch_cull_stats(const CullStatsParams &p, uint32_t num_cus, hipStream_t s);
+#if !ORBIT_CONTRACT
+hipError_t launch_cull_stats_contracted(const CullStatsParams &p, uint32_t num_cus, hipStream_t s);
+#endif
 // the alpha classes of the whole stream, from its material indices (orbit_meshlet_stream_set_materials)
 // meshes [first, first + count) of `mesh_infos` -> their 32-B side entries; and the comparison (ORBIT_E_STALE)
 hipError_t launch_mesh_side_build(const OrbitMeshInfo *mesh_infos, uint32_t first, uint32_t count, MeshSide *table, hipStream_t s);

@@ -49,6 +49,17 @@ def shard_range(entity_draw_count, rank, world):
     return b.value, e.value
 
 
+def cull_stats_dict(stats):
+    """The 256 bytes of an OrbitCullStats (a torch tensor or anything numpy can view as bytes) as {counter: int};
+    lod_drawn is a list of 8 and the reserved words are left out."""
+    if hasattr(stats, "detach"):
+        stats = stats.detach().cpu().numpy()
+    raw = np.ascontiguousarray(stats).reshape(-1).view(np.uint8)[:layouts.CULL_STATS.itemsize]
+    rec = raw.view(layouts.CULL_STATS)[0]
+    return {n: [int(v) for v in rec[n]] if n == "lod_drawn" else int(rec[n])
+            for n in layouts.CULL_STATS.names if not n.startswith("reserved")}
+
+
 class MeshletStream:
     """Handle of an OrbitMeshletStream (include/orbit_abi.h, "Derived meshlet streams")."""
 
@@ -224,6 +235,38 @@ class Engine:
         _lib.check(self._lib.orbit_scene_update_entities(self._ctx, _ptr(transforms), _ptr(instance_indices), int(count),
                                                          _ptr(entity_data), int(entity_capacity), _stream(stream)),
                    self._ctx)
+
+    # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
+    def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
+                   entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,
+                   draw_capacity, visibility_buffer=None, meshlet_visibility_buffer=None, depth_pyramid=None,
+                   depth_pyramid_size=(0, 0), material_count=0, depth_pyramid_levels=None, stream=None):
+        """Enqueues orbit_cull_stats into `stats`, a device tensor of at least 256 bytes (8-B aligned) that is
+        overwritten with an OrbitCullStats (read it with cull_stats_dict).  The arguments are entity_cull's and
+        meshlet_cull's; call it BEFORE the cull they describe — passes 1 and 2 rewrite the visibility words it reads.
+        Nothing but `stats` is written; the dispatch and draw buffers are only checked for presence."""
+        if stats.numel() * stats.element_size() < layouts.CULL_STATS.itemsize:
+            raise ValueError("stats needs 256 bytes")
+        ci = _host_bytes(cull_info, 400)
+        e, m = _lib.EntityCullBufs(), _lib.MeshletCullBufs()
+        e.entity_draw_buffer = _ptr(entity_draw_buffer)
+        e.mesh_info_buffer = _ptr(mesh_info_buffer)
+        e.meshlet_dispatch_buffer = m.meshlet_dispatch_buffer = _ptr(meshlet_dispatch_buffer)
+        e.entity_buffer = m.entity_buffer = _ptr(entity_buffer)
+        e.visibility_buffer = _ptr(visibility_buffer)
+        e.depth_pyramid = m.depth_pyramid = _ptr(depth_pyramid)
+        e.depth_pyramid_size[0], e.depth_pyramid_size[1] = depth_pyramid_size
+        m.depth_pyramid_size[0], m.depth_pyramid_size[1] = depth_pyramid_size
+        e.depth_pyramid_levels = m.depth_pyramid_levels = _ptr(depth_pyramid_levels)
+        e.dispatch_capacity = m.dispatch_capacity = dispatch_capacity
+        m.meshlet_buffer = _ptr(meshlet_buffer)
+        m.draw_commands_buffer = _ptr(draw_commands_buffer)
+        m.material_buffer = _ptr(material_buffer)
+        m.meshlet_visibility_buffer = _ptr(meshlet_visibility_buffer)
+        m.draw_capacity = draw_capacity
+        m.material_count = material_count
+        _lib.check(self._lib.orbit_cull_stats(self._ctx, ci.ctypes.data_as(C.c_void_p), C.byref(e), int(entity_draw_count),
+                                              C.byref(m), _ptr(stats), _stream(stream)), self._ctx)
 
     # -- several views side by side (orbit_cull_views)
     def cull_views(self, views, stream=None):

@@ -100,6 +100,15 @@ GPU_CLUSTER_INFO_BUFFER = np.dtype([
     ("light_offset_image", "<u4"), ("light_index_list", "<u4"), ("tile_depth_slice_mask_buffer", "<u4"),
 ])
 
+# OrbitCullStats (include/orbit_abi_ext.h): the u64 counters orbit_cull_stats writes, 256 B
+CULL_STATS_ENTITY = ("entities", "entity_skipped_prev_invisible", "entity_frustum_culled", "entity_occlusion_culled",
+                     "entity_drawn_in_early_pass", "entity_drawn")
+CULL_STATS_MESHLET = ("meshlets", "meshlet_skipped_prev_invisible", "meshlet_frustum_culled", "meshlet_cone_culled",
+                      "meshlet_occlusion_culled", "meshlet_alpha_filtered", "meshlet_drawn_in_early_pass", "meshlet_drawn")
+CULL_STATS = np.dtype([(n, "<u8") for n in CULL_STATS_ENTITY] + [("records", "<u8"), ("reserved0", "<u8"),
+                                                                 ("lod_drawn", "<u8", (8,))]
+                      + [(n, "<u8") for n in CULL_STATS_MESHLET] + [("reserved1", "<u8", (8,))])
+
 _SIZES = {
     "ENTITY_DRAW": (ENTITY_DRAW, 12), "ENTITY_DATA": (ENTITY_DATA, 128), "ENTITY_TRANSFORM": (ENTITY_TRANSFORM, 40),
     "MESH_INFO": (MESH_INFO, 128),
@@ -108,7 +117,7 @@ _SIZES = {
     "MESH_TASK_RECORD": (MESH_TASK_RECORD, 44), "VISIBLE_RECORD": (VISIBLE_RECORD, 12),
     "GPU_CULL_INFO": (GPU_CULL_INFO, 400), "CLUSTER_DEPTH_BOUNDS": (CLUSTER_DEPTH_BOUNDS, 8),
     "MARK_ACTIVE_PUSH": (MARK_ACTIVE_PUSH, 56), "CLUSTER_CULL_INFO": (CLUSTER_CULL_INFO, 192),
-    "GPU_CLUSTER_INFO_BUFFER": (GPU_CLUSTER_INFO_BUFFER, 52),
+    "GPU_CLUSTER_INFO_BUFFER": (GPU_CLUSTER_INFO_BUFFER, 52), "CULL_STATS": (CULL_STATS, 256),
 }
 for _name, (_dt, _sz) in _SIZES.items():
     assert _dt.itemsize == _sz, (_name, _dt.itemsize, _sz)
@@ -119,6 +128,8 @@ assert MATERIAL.fields["alpha_mode"][1] == 64
 assert MESH_INFO.fields["mesh_lods"][1] == 64
 assert ENTITY_TRANSFORM.fields["orientation"][1] == 12 and ENTITY_TRANSFORM.fields["scale"][1] == 28
 assert CLUSTER_CULL_INFO.fields["global_light_count"][1] == 176
+assert CULL_STATS.fields["records"][1] == 48 and CULL_STATS.fields["lod_drawn"][1] == 64
+assert CULL_STATS.fields["meshlets"][1] == 128 and CULL_STATS.fields["meshlet_drawn"][1] == 184
 
 
 def entity_draw_buffer(draws: np.ndarray, count=None) -> np.ndarray:
