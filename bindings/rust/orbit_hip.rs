@@ -50,6 +50,15 @@ pub struct OrbitCullStats {
     pub meshlet_drawn_in_early_pass: u64, pub meshlet_drawn: u64, pub reserved1: [u64; 8],
 }
 
+/// orbit_cluster_stats' 256-B block of u64 counters (include/orbit_abi_ext.h OrbitClusterStats); the classes of a
+/// cluster's uncapped light count: 0, 1-16, 17-64, 65-256, > 256
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitClusterStats {
+    pub samples: u64, pub samples_outside_grid: u64, pub active_clusters: u64, pub light_refs: u64,
+    pub light_indices: u64, pub max_cluster_lights: u64, pub sample_light_refs: u64, pub reserved0: u64,
+    pub clusters_by_lights: [u64; 5], pub reserved1: [u64; 3], pub samples_by_lights: [u64; 5], pub reserved2: [u64; 11],
+}
+
 /// push-constant order of shaders/entity_cull.comp:17-23 (== draw_gen.rs:372-376)
 #[repr(C)]
 pub struct OrbitEntityCullBufs {
@@ -217,6 +226,10 @@ extern "C" {
     pub fn orbit_cull_stats(ctx: *mut OrbitCtx, cull_info: *const c_void, ebufs: *const OrbitEntityCullBufs,
                             entity_draw_count: u32, mbufs: *const OrbitMeshletCullBufs, stats: *mut OrbitCullStats,
                             stream: *mut c_void) -> i32;
+    /// The uncapped counts of orbit_compute_clusters for these inputs into a DEVICE OrbitClusterStats (overwritten).
+    /// Writes nothing else, uses no context scratch: before, after or beside the chain.
+    pub fn orbit_cluster_stats(ctx: *mut OrbitCtx, push: *const c_void, info: *const c_void, depth: *const f32,
+                               lights: *const c_void, stats: *mut OrbitClusterStats, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

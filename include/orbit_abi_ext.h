@@ -14,7 +14,8 @@
  *     and the expansion of a gathered list,
  *   - the measurement hook of bench.py,
  *   - the scene update: model and normal matrices computed on the device from entity transforms,
- *   - cull statistics: every entity and meshlet of a cull counted by the first test that rejected it.
+ *   - cull statistics: every entity and meshlet of a cull counted by the first test that rejected it,
+ *   - cluster statistics: the uncapped light counts of the cluster chain, by cluster and by depth sample.
  * A build that only needs the drop-in includes orbit_abi.h alone; liborbit_cull.so exports both sets.
  */
 #ifndef ORBIT_ABI_EXT_H
@@ -558,6 +559,75 @@ ORBIT_STATIC_ASSERT(offsetof(OrbitCullStats, reserved1) == 192, "reserved1 @192"
 int32_t orbit_cull_stats(OrbitCtx *ctx, const OrbitGpuCullInfo *cull_info, const OrbitEntityCullBufs *ebufs,
                          uint32_t entity_draw_count, const OrbitMeshletCullBufs *mbufs, OrbitCullStats *stats,
                          void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* Cluster statistics.  The cluster chain returns capped results only: an   */
+/* (offset, count) image whose counts stop at 256 (light_culling.comp:135), */
+/* a compacted list and a light_count header that stop at the capacities.   */
+/* orbit_cluster_stats counts, on the device, what the chain finds before   */
+/* any cap, and what the forward pass will loop over.                       */
+/*                                                                          */
+/* Contract: *stats is OVERWRITTEN with what                                */
+/*     orbit_compute_clusters(ctx, push, info, depth, lights, ...)          */
+/* computes for these inputs.  No counter depends on index_capacity or      */
+/* light_index_capacity: every counter is uncapped.  push and info are host */
+/* pointers; depth, lights and stats are device pointers, stats 8-B aligned.*/
+/* The call reads only the chain's inputs and writes *stats and nothing     */
+/* else — no mask, bounds, compacted list, index buffer, image or latched   */
+/* status — so it may come before or after the chain.  It uses no scratch   */
+/* of the context: on a stream beside the chain (orbit_frame_late runs the  */
+/* chain on side streams) it does not race with it.  It allocates nothing   */
+/* and never synchronises the host: a graph can capture it on its first     */
+/* call.  The counters are cleared on the stream and summed with 64-bit     */
+/* device atomics: the result is deterministic.  The cluster passes are     */
+/* canonical in either arith_profile: one build serves both.                */
+/* Refused exactly like orbit_compute_clusters refuses the same push, info, */
+/* depth and lights (same checks, same codes), and also:                   */
+/*   ORBIT_E_INVALID  stats NULL or not 8-B aligned                         */
+/*                                                                          */
+/* Definitions.  A depth sample is depth[(py W + px) samples + s]; its      */
+/* slice is mark_active's, depth_slice(z_near / d) (orbit_device.h); it is  */
+/* in the grid iff slice < cz, and then its cluster is (px/ts, py/ts,       */
+/* slice).  A cluster is active iff it holds an in-grid sample (the         */
+/* compaction's clusters, uncut).  count(c) = the lights < global_light_    */
+/* count for which is_light_in_cluster(aabb(c), l) holds (:108-133; a       */
+/* non-point light is in every cluster), uncapped; capped(c) =              */
+/* min(count(c), 256).  The classes of count(c):                            */
+/*   [0] 0, [1] 1-16, [2] 17-64, [3] 65-256, [4] > 256.                     */
+/*                                                                          */
+/* Invariants:                                                              */
+/*   samples == samples_outside_grid + sum(samples_by_lights)               */
+/*   active_clusters == sum(clusters_by_lights)                             */
+/*   light_refs - light_indices = the lights lost to the 256 cap; it is 0   */
+/*              iff clusters_by_lights[4] == 0                              */
+/*   with index_capacity >= active_clusters, the chain's compaction header  */
+/*              is active_clusters and its light_count header is            */
+/*              light_indices (the index capacity the frame needs)          */
+/* ------------------------------------------------------------------------ */
+typedef struct OrbitClusterStats {
+    uint64_t samples;              /* W * H * depth_buffer_sample_count */
+    uint64_t samples_outside_grid; /* slice >= cz: the forward pass's imageLoad misses, no clustered light (clear 0.0) */
+    uint64_t active_clusters;      /* the compaction's count, uncut by index_capacity */
+    uint64_t light_refs;           /* sum over active clusters of count(c) */
+    uint64_t light_indices;        /* sum over active clusters of capped(c): the chain's light_count header */
+    uint64_t max_cluster_lights;   /* max of count(c), or 0 */
+    uint64_t sample_light_refs;    /* sum over in-grid samples of capped(their cluster): the trips of forward.frag:371's
+                                      loop, each sample shaded once at its own depth (MSAA: per sample, an upper bound) */
+    uint64_t reserved0;
+    uint64_t clusters_by_lights[5]; /* active clusters per class of count(c) */
+    uint64_t reserved1[3];
+    uint64_t samples_by_lights[5];  /* in-grid samples per class of their cluster's count(c) */
+    uint64_t reserved2[11];
+} OrbitClusterStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitClusterStats) == 256, "ClusterStats is 256 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitClusterStats, sample_light_refs) == 48, "sample_light_refs @48");
+ORBIT_STATIC_ASSERT(offsetof(OrbitClusterStats, clusters_by_lights) == 64, "clusters_by_lights @64");
+ORBIT_STATIC_ASSERT(offsetof(OrbitClusterStats, samples_by_lights) == 128, "samples_by_lights @128");
+ORBIT_STATIC_ASSERT(offsetof(OrbitClusterStats, reserved2) == 168, "reserved2 @168");
+
+/* *stats (DEVICE, 8-B aligned) = the uncapped counts of orbit_compute_clusters for these inputs; see above */
+int32_t orbit_cluster_stats(OrbitCtx *ctx, const OrbitMarkActivePush *push, const OrbitClusterCullInfo *info,
+                            const float *depth, const OrbitLightData *lights, OrbitClusterStats *stats, void *stream);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,8 @@ SYMBOLS = {
                                                 C.c_void_p]),
     "orbit_cull_stats": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(EntityCullBufs), C.c_uint32,
                                      C.POINTER(MeshletCullBufs), C.c_void_p, C.c_void_p]),
+    "orbit_cluster_stats": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
 }
 
 _lib = None

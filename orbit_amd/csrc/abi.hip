@@ -2039,4 +2039,35 @@ int32_t orbit_cull_stats(OrbitCtx *ctx, const OrbitGpuCullInfo *cull_info, const
     return ORBIT_OK;
 }
 
+// ----------------------------------------------------------- cluster statistics
+// The uncapped counts of orbit_compute_clusters for these inputs (cluster_stats.hip).  Refused by the chain's own check
+// with the same codes: the buffers only the chain writes are not arguments here, and `stats` stands in for them (it is
+// checked first).  No allocation, no context scratch, no host sync: capturable on the first call, and safe beside a
+// chain on another stream.
+int32_t orbit_cluster_stats(OrbitCtx *ctx, const OrbitMarkActivePush *push, const OrbitClusterCullInfo *info,
+                            const float *depth, const OrbitLightData *lights, OrbitClusterStats *stats, void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!stats || ((uintptr_t)stats & 7u)) return fail(ctx, ORBIT_E_INVALID, "cluster_stats: stats is NULL or not 8-B aligned");
+    void *out = stats;
+    const int32_t rc = compute_clusters_check(ctx, push, info, depth, lights, (uint32_t *)out, (OrbitClusterDepthBounds *)out,
+                                              out, out, (uint32_t *)out);
+    if (rc != ORBIT_OK) return rc;
+    ClusterStatsParams p;
+    p.pc = *push;
+    p.info = *info;
+    p.depth = depth;
+    p.lights = lights;
+    p.stats = reinterpret_cast<unsigned long long *>(stats);
+    const uint64_t W = push->screen_size[0], H = push->screen_size[1], sc = push->depth_buffer_sample_count;
+    const uint64_t ts = push->tile_size_px;
+    const uint64_t covered_w = std::min<uint64_t>(W, ts * push->cluster_count[0]);
+    const uint64_t covered_h = std::min<uint64_t>(H, ts * push->cluster_count[1]);
+    p.samples = W * H * sc;
+    p.uncovered = p.samples - covered_w * covered_h * sc;
+    const hipError_t e = launch_cluster_stats(p, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch cluster_stats");
+    return ORBIT_OK;
+}
+
 } // extern "C"

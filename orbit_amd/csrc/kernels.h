@@ -371,6 +371,18 @@ hipError_t launch_cull_stats(const CullStatsParams &p, uint32_t num_cus, hipStre
 #if !ORBIT_CONTRACT
 hipError_t launch_cull_stats_contracted(const CullStatsParams &p, uint32_t num_cus, hipStream_t s);
 #endif
+// cluster_stats.hip: orbit_cluster_stats — the uncapped counts of the cluster chain for these inputs into `stats`, cleared
+// on the stream first
+struct ClusterStatsParams {
+    OrbitMarkActivePush pc;
+    OrbitClusterCullInfo info;
+    const float *depth;
+    const OrbitLightData *lights;
+    unsigned long long *stats;     // OrbitClusterStats, 8-B aligned
+    unsigned long long samples;    // W * H * samples
+    unsigned long long uncovered;  // ... of them in pixels no tile of the grid covers (outside the grid)
+};
+hipError_t launch_cluster_stats(const ClusterStatsParams &p, hipStream_t s);
 // the alpha classes of the whole stream, from its material indices (orbit_meshlet_stream_set_materials)
 // meshes [first, first + count) of `mesh_infos` -> their 32-B side entries; and the comparison (ORBIT_E_STALE)
 hipError_t launch_mesh_side_build(const OrbitMeshInfo *mesh_infos, uint32_t first, uint32_t count, MeshSide *table, hipStream_t s);

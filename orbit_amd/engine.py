@@ -60,6 +60,17 @@ def cull_stats_dict(stats):
             for n in layouts.CULL_STATS.names if not n.startswith("reserved")}
 
 
+def cluster_stats_dict(stats):
+    """The 256 bytes of an OrbitClusterStats (a torch tensor or anything numpy can view as bytes) as {counter: int};
+    clusters_by_lights and samples_by_lights are lists of 5 and the reserved words are left out."""
+    if hasattr(stats, "detach"):
+        stats = stats.detach().cpu().numpy()
+    raw = np.ascontiguousarray(stats).reshape(-1).view(np.uint8)[:layouts.CLUSTER_STATS.itemsize]
+    rec = raw.view(layouts.CLUSTER_STATS)[0]
+    return {n: [int(v) for v in rec[n]] if n.endswith("_by_lights") else int(rec[n])
+            for n in layouts.CLUSTER_STATS.names if not n.startswith("reserved")}
+
+
 class MeshletStream:
     """Handle of an OrbitMeshletStream (include/orbit_abi.h, "Derived meshlet streams")."""
 
@@ -594,6 +605,18 @@ class Engine:
             self._ctx, pc.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p), _ptr(depth), _ptr(lights),
             _ptr(tile_depth_slice_mask), _ptr(depth_bounds), _ptr(unique_cluster_buffer), index_capacity,
             _ptr(light_index_buffer), light_index_capacity, _ptr(cluster_offset_image), _stream(stream)), self._ctx)
+
+    # -- cluster statistics: the uncapped counts of compute_clusters for these inputs (orbit_cluster_stats)
+    def cluster_stats(self, stats, push, info, depth, lights, stream=None):
+        """Enqueues orbit_cluster_stats into `stats`, a device tensor of at least 256 bytes (8-B aligned) that is
+        overwritten with an OrbitClusterStats (read it with cluster_stats_dict).  The arguments are compute_clusters'
+        inputs; nothing but `stats` is written, so it may come before, after or beside the chain."""
+        if stats.numel() * stats.element_size() < layouts.CLUSTER_STATS.itemsize:
+            raise ValueError("stats needs 256 bytes")
+        pc = _host_bytes(push, layouts.MARK_ACTIVE_PUSH.itemsize)
+        ib = _host_bytes(info, layouts.CLUSTER_CULL_INFO.itemsize)
+        _lib.check(self._lib.orbit_cluster_stats(self._ctx, pc.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p),
+                                                 _ptr(depth), _ptr(lights), _ptr(stats), _stream(stream)), self._ctx)
 
     # -- compute_clusters stages (cluster.rs:399-591)
     def cluster_mark(self, push, depth, tile_depth_slice_mask, depth_bounds, stream=None):

@@ -109,6 +109,15 @@ CULL_STATS = np.dtype([(n, "<u8") for n in CULL_STATS_ENTITY] + [("records", "<u
                                                                  ("lod_drawn", "<u8", (8,))]
                       + [(n, "<u8") for n in CULL_STATS_MESHLET] + [("reserved1", "<u8", (8,))])
 
+# OrbitClusterStats (include/orbit_abi_ext.h): the u64 counters orbit_cluster_stats writes, 256 B; the classes of a
+# cluster's uncapped light count are 0, 1-16, 17-64, 65-256, > 256
+CLUSTER_STATS_SCALARS = ("samples", "samples_outside_grid", "active_clusters", "light_refs", "light_indices",
+                         "max_cluster_lights", "sample_light_refs")
+CLUSTER_STATS_CLASSES = ((0, 0), (1, 16), (17, 64), (65, 256), (257, None))  # (lo, hi) light counts, inclusive
+CLUSTER_STATS = np.dtype([(n, "<u8") for n in CLUSTER_STATS_SCALARS]
+                         + [("reserved0", "<u8"), ("clusters_by_lights", "<u8", (5,)), ("reserved1", "<u8", (3,)),
+                            ("samples_by_lights", "<u8", (5,)), ("reserved2", "<u8", (11,))])
+
 _SIZES = {
     "ENTITY_DRAW": (ENTITY_DRAW, 12), "ENTITY_DATA": (ENTITY_DATA, 128), "ENTITY_TRANSFORM": (ENTITY_TRANSFORM, 40),
     "MESH_INFO": (MESH_INFO, 128),
@@ -118,6 +127,7 @@ _SIZES = {
     "GPU_CULL_INFO": (GPU_CULL_INFO, 400), "CLUSTER_DEPTH_BOUNDS": (CLUSTER_DEPTH_BOUNDS, 8),
     "MARK_ACTIVE_PUSH": (MARK_ACTIVE_PUSH, 56), "CLUSTER_CULL_INFO": (CLUSTER_CULL_INFO, 192),
     "GPU_CLUSTER_INFO_BUFFER": (GPU_CLUSTER_INFO_BUFFER, 52), "CULL_STATS": (CULL_STATS, 256),
+    "CLUSTER_STATS": (CLUSTER_STATS, 256),
 }
 for _name, (_dt, _sz) in _SIZES.items():
     assert _dt.itemsize == _sz, (_name, _dt.itemsize, _sz)
@@ -130,6 +140,8 @@ assert ENTITY_TRANSFORM.fields["orientation"][1] == 12 and ENTITY_TRANSFORM.fiel
 assert CLUSTER_CULL_INFO.fields["global_light_count"][1] == 176
 assert CULL_STATS.fields["records"][1] == 48 and CULL_STATS.fields["lod_drawn"][1] == 64
 assert CULL_STATS.fields["meshlets"][1] == 128 and CULL_STATS.fields["meshlet_drawn"][1] == 184
+assert CLUSTER_STATS.fields["sample_light_refs"][1] == 48 and CLUSTER_STATS.fields["clusters_by_lights"][1] == 64
+assert CLUSTER_STATS.fields["samples_by_lights"][1] == 128 and CLUSTER_STATS.fields["reserved2"][1] == 168
 
 
 def entity_draw_buffer(draws: np.ndarray, count=None) -> np.ndarray:
