@@ -8,7 +8,7 @@ The kernel picks its path from the data:
   per group of 256 active clusters, by its coarse segment counts (cluster_assign_kernel's s_fast): every segment within
     8 candidates is one wave's item, within 16 one speculative fetch, within 64 one fetched step, longer segments the
     stepped path — several steps once the group has more than kLightTile = 1024 candidates.  The segments split the
-    light array in round64(ceil(max_lights / 16)) lights each (abi.hip).
+    light array in round64(ceil(max_lights / 16)) lights each (abi_ctx.hip).
 The scene puts zero-radius point lights at the centres of chosen active clusters' boxes (oracle.cluster_aabb), the
 lights of different clusters interleaved, a few directional lights at chosen indices, and asserts on the host — from
 tests/np_restatement.py's uncapped counts and a restatement of the group union boxes and the segment split — that every

@@ -187,7 +187,7 @@ from test_spirv_vectors_cpu import CLUSTER_SHAPE_CASES, CLUSTER_SHAPES_GOLD, loa
 @pytest.mark.parametrize("name", CLUSTER_SHAPE_CASES)
 def test_product_equals_the_cluster_binaries_at_other_shapes(torch_mod, name, max_lights):
     """cluster_mark / cluster_compact / cluster_assign, and compute_clusters, against the binaries' outputs at the shapes
-    of tests/golden/spirv_cluster_shapes.npz.  The Engine's max_lights sets the coarse segment size (abi.hip:
+    of tests/golden/spirv_cluster_shapes.npz.  The Engine's max_lights sets the coarse segment size (abi_ctx.hip:
     round64(ceil(max_lights / 16))): "exact" makes the light count equal to max_lights, 4096 puts every light of these
     cases into the first few segments."""
     from orbit_amd.engine import Engine
