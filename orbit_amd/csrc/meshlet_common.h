@@ -477,7 +477,7 @@ __device__ __forceinline__ void cand_flush(const MeshletCullParams &p, WaveTileL
         const float scale = L.r[(info.x >> 5) & 15u].scale;
         Sphere s;
         s.x = sp.x, s.y = sp.y, s.z = sp.z, s.r = sp.w * scale;
-        visible = occlusion_test(p.ci, s, sp.w, scale, p.pyr); // :161-205
+        visible = occlusion_test(p.ci, s, sp.w, scale, p.pyr, p.task_records == nullptr); // :161-205
     }
     const uint32_t code = info.x;
     const uint32_t abits = (code >> 9) & 3u;

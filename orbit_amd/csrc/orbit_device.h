@@ -202,15 +202,18 @@ __device__ __forceinline__ void project_sphere(const Sphere &s, float p00, float
 // (oracle/orbit_oracle.c occlusion_test): `radius` is the model-space radius and `scale` the matrix's largest scale —
 // s.r = radius * scale — because three sums of the test are fused with that product in the reference's binaries.
 // Flips s.z in the perspective branch; the flip persists for the caller.
+// `fused` = false (wave-uniform) is the mesh-shading path: in the task shader's binary those three sums are NOT fused, they
+// take the rounded product s.r (oracle/orbit_oracle.c occlusion_test; tests/golden/spirv_cull_hiz_edges.npz holds rows —
+// a near point exactly on the near plane under a scale that is no power of two — that the two forms decide differently).
 __device__ __forceinline__ bool occlusion_test(const OrbitGpuCullInfo &ci, Sphere &s, float radius, float scale,
-                                               const PyramidView &pyr) {
+                                               const PyramidView &pyr, bool fused = true) {
     bool cullable = true;
     float aabb[4], closest;
     if (ci.projection_type == 0) {
         s.z = -s.z;
-        cullable = s.z >= __builtin_fmaf(radius, scale, ci.z_near);
+        cullable = s.z >= (fused ? __builtin_fmaf(radius, scale, ci.z_near) : s.r + ci.z_near);
         project_sphere(s, ci.p00_or_width_recipx2, ci.p11_or_height_recipx2, aabb);
-        closest = ci.z_near / __builtin_fmaf(-radius, scale, s.z);
+        closest = ci.z_near / (fused ? __builtin_fmaf(-radius, scale, s.z) : s.z - s.r);
     } else {
         const float sr = ci.p00_or_width_recipx2;
         const float cx = s.x * sr, cy = s.y * sr;
@@ -221,7 +224,7 @@ __device__ __forceinline__ bool occlusion_test(const OrbitGpuCullInfo &ci, Spher
         aabb[1] = __builtin_fmaf(gclamp(b1, -1.0f, 1.0f), -0.5f, 0.5f);
         aabb[2] = __builtin_fmaf(gclamp(b2, -1.0f, 1.0f), 0.5f, 0.5f);
         aabb[3] = __builtin_fmaf(gclamp(b3, -1.0f, 1.0f), -0.5f, 0.5f);
-        const float closest_z = __builtin_fmaf(radius, scale, s.z);
+        const float closest_z = fused ? __builtin_fmaf(radius, scale, s.z) : s.z + s.r;
         const float r = 1.0f / (ci.z_far - ci.z_near);
         closest = r * (closest_z + ci.z_far);
     }

@@ -284,8 +284,8 @@ class Engine:
         """views: list of dicts with the arguments of entity_cull + meshlet_cull for one view each:
         cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer, entity_draw_count,
         dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer, draw_capacity and optionally
-        visibility_buffer, meshlet_visibility_buffer, depth_pyramid, depth_pyramid_size, material_count,
-        skip_meshlet_stage."""
+        visibility_buffer, meshlet_visibility_buffer, depth_pyramid, depth_pyramid_size, depth_pyramid_levels,
+        material_count, skip_meshlet_stage."""
         arr, keep = self.prepare_views(views)
         self.cull_views_prepared(arr, stream)
         del keep
@@ -313,6 +313,8 @@ class Engine:
             ps = v.get("depth_pyramid_size", (0, 0))
             e.depth_pyramid_size[0], e.depth_pyramid_size[1] = ps
             m.depth_pyramid_size[0], m.depth_pyramid_size[1] = ps
+            # DEVICE array of OrbitDepthPyramidLevel (separate per-mip images), or None for the packed chain
+            e.depth_pyramid_levels = m.depth_pyramid_levels = _ptr(v.get("depth_pyramid_levels"))
             e.dispatch_capacity = m.dispatch_capacity = v["dispatch_capacity"]
             m.meshlet_buffer = _ptr(v.get("meshlet_buffer"))
             m.draw_commands_buffer = _ptr(v.get("draw_commands_buffer"))

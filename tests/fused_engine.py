@@ -19,8 +19,7 @@ class FusedEngine(Engine):
                     entity_draw_count, dispatch_capacity, visibility_buffer=None, depth_pyramid=None,
                     depth_pyramid_size=(0, 0), draw_first=None, stream=None, depth_pyramid_levels=None):
         self._pending = None
-        whole = draw_first is None and entity_draw_count > 0 and depth_pyramid_levels is None \
-            and not isinstance(meshlet_dispatch_buffer, int)
+        whole = draw_first is None and entity_draw_count > 0 and not isinstance(meshlet_dispatch_buffer, int)
         if whole:
             import torch
 
@@ -30,7 +29,8 @@ class FusedEngine(Engine):
                                  mesh_info_buffer=mesh_info_buffer, meshlet_dispatch_buffer=meshlet_dispatch_buffer,
                                  entity_buffer=entity_buffer, entity_draw_count=entity_draw_count,
                                  dispatch_capacity=dispatch_capacity, visibility_buffer=visibility_buffer,
-                                 depth_pyramid=depth_pyramid, depth_pyramid_size=depth_pyramid_size, _saved=saved)
+                                 depth_pyramid=depth_pyramid, depth_pyramid_size=depth_pyramid_size,
+                                 depth_pyramid_levels=depth_pyramid_levels, _saved=saved)
         super().entity_cull(cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                             entity_draw_count, dispatch_capacity, visibility_buffer=visibility_buffer,
                             depth_pyramid=depth_pyramid, depth_pyramid_size=depth_pyramid_size, draw_first=draw_first,
@@ -41,7 +41,7 @@ class FusedEngine(Engine):
                      depth_pyramid=None, depth_pyramid_size=(0, 0), material_count=0, stream=None, task_records=None,
                      depth_pyramid_levels=None, record_buffer=None, record_capacity=None):
         p, self._pending = self._pending, None
-        plain = task_records is None and record_buffer is None and depth_pyramid_levels is None
+        plain = task_records is None and record_buffer is None
         if p is None or not plain or p["meshlet_dispatch_buffer"] is not meshlet_dispatch_buffer \
                 or p["dispatch_capacity"] != dispatch_capacity or isinstance(meshlet_buffer, int):
             return super().meshlet_cull(cull_info, meshlet_dispatch_buffer, meshlet_buffer, draw_commands_buffer,
@@ -60,8 +60,9 @@ class FusedEngine(Engine):
         view = dict(p, meshlet_buffer=meshlet_buffer, draw_commands_buffer=draw_commands_buffer,
                     material_buffer=material_buffer, draw_capacity=draw_capacity,
                     meshlet_visibility_buffer=meshlet_visibility_buffer, material_count=material_count)
-        if depth_pyramid is not None:
-            view.update(depth_pyramid=depth_pyramid, depth_pyramid_size=depth_pyramid_size)
+        if depth_pyramid is not None or depth_pyramid_levels is not None:  # (a level table: separate per-mip images)
+            view.update(depth_pyramid=depth_pyramid, depth_pyramid_size=depth_pyramid_size,
+                        depth_pyramid_levels=depth_pyramid_levels)
         before = self.fused_culls()
         self.cull_views([view], stream=stream)
         assert self.fused_culls() == before + 1, "the one-launch path was not taken"

@@ -2,8 +2,9 @@
 level by level), spirv_compact.npz (`compact`: active_cluster_compaction.comp.spv), spirv_cluster_shapes.npz (`cluster_shapes`: the two
 light-cluster binaries at other tile sizes, slice counts, sample counts, light types and edge cases) and spirv_cull_dispatch_sizes.npz
 (`dispatch`: the two cull shaders with MESHLET_DISPATCH_SIZE = 64 / 128, pass 0) and spirv_cull_contracted.npz
-(`contracted`: the cull cases with Dot / matrix products / Length as fma chains): inputs and OUTPUTS OF THE
-REFERENCE'S OWN COMPILED SHADERS.
+(`contracted`: the cull cases with Dot / matrix products / Length as fma chains) and spirv_cull_hiz_edges.npz (`hiz_edges`:
+pass 2 on the hostile scenes, pyramids and depth buffers of tests/hiz_edges.py, canonical and contracted): inputs and
+OUTPUTS OF THE REFERENCE'S OWN COMPILED SHADERS.
 
 Run after build() has copied the reference's binaries (oracle/Makefile `ref`; it reads oracle/_ref/shaders/{entity_cull,meshlet_cull}.comp.spv,
 forward/forward_depth_prepass.task.spv and light_cluster/{mark_active,light_culling}.comp.spv, which do not travel): `python tests/golden/make_spirv_vectors.py`.  The binaries are executed by oracle/spirv_vm.py; what the
@@ -159,7 +160,13 @@ def case(seed, occlusion_pass, ortho, knife, n=140, S=32, fused_dot=False):
         depth = depth_knife_edge(scene, cam, ci, ortho, seed, rng)
         evis[:], mvis[:] = 0, 0
     pyr, dsc = oracle.depth_reduce(depth, W, H)
-    ps = (dsc.width, dsc.height)
+    return run_binaries(scene, ci, evis, mvis, pyr, (dsc.width, dsc.height), S, fused_dot)
+
+
+def run_binaries(scene, ci, evis, mvis, pyr, ps, S=32, fused_dot=False):
+    """entity_cull.comp.spv, meshlet_cull.comp.spv and forward_depth_prepass.task.spv on one scene -> the inputs and the
+    binaries' outputs under the names the vector files use."""
+    occlusion_pass = int(ci["occlusion_pass"])
     cap_d, cap_c = scene.max_dispatches() + 8, scene.lod0_meshlets + 8
     # registry: one index space for all storage buffers (set 0, binding 0), textures and samplers apart
     B = {}
@@ -515,6 +522,43 @@ def contracted_main():
     print(path, os.path.getsize(path), "bytes")
 
 
+HIZ_EDGE_INPUTS = ("cull_info", "entity_draws", "mesh_infos", "entities", "meshlets", "materials", "caps", "evis_in", "mvis_in",
+                   "pyramid", "pyramid_size")
+HIZ_EDGE_OUTPUTS = ("spv_dispatch", "spv_draw", "spv_evis", "spv_mvis", "spv_task_records", "spv_task_mvis")
+
+
+def hiz_edges_case(name, fused_dot=False):
+    """One case of tests/hiz_edges.py VECTOR_CASES (pass 2, no cull planes, random visibility words) through the three
+    binaries.  The ReduceMin sampler is not in the binaries: the interpreter is handed oracle.hiz_sample."""
+    import hiz_edges as hz
+
+    c = hz.make_case(name, oracle)
+    evis, mvis = hz.words(c["scene"], "random", seed=len(name))
+    return run_binaries(c["scene"], c["ci"], evis, mvis, c["pyr"], c["psize"], fused_dot=fused_dot)
+
+
+def hiz_edges_main():
+    """tests/golden/spirv_cull_hiz_edges.npz: the inputs of every case once, the binaries' outputs canonical (`spv_*`)
+    and with Dot / matrix products / Length as fma chains (`contracted/spv_*`)."""
+    import hiz_edges as hz
+
+    out = {}
+    for name in hz.VECTOR_CASES:
+        c, cc = hiz_edges_case(name), hiz_edges_case(name, fused_dot=True)
+        for k in HIZ_EDGE_INPUTS + HIZ_EDGE_OUTPUTS:
+            out[f"{name}/{k}"] = c[k]
+        differ = 0
+        for k in HIZ_EDGE_OUTPUTS:
+            out[f"{name}/contracted/{k}"] = cc[k]
+            differ += int(np.ascontiguousarray(c[k]).tobytes() != np.ascontiguousarray(cc[k]).tobytes())
+        print("%-18s records %5d  draws %6d  task survivors %6d  contracted outputs that differ: %d of 6" % (
+            name, int(c["spv_dispatch"][:4].view(np.uint32)[0]), int(c["spv_draw"][:4].view(np.uint32)[0]),
+            int(c["spv_task_records"]["task_mesh_count"].sum()), differ))
+    path = os.path.join(HERE, "spirv_cull_hiz_edges.npz")
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), "bytes")
+
+
 def dispatch_main():
     """tests/golden/spirv_cull_dispatch_sizes.npz: entity_cull.comp.spv + meshlet_cull.comp.spv with spec constant 0 = 64
     and 128, occlusion pass 0, perspective / orthographic x plain / knife-edge — and, per case, whether the binaries'
@@ -552,6 +596,8 @@ def main():
         return dispatch_main()
     if len(sys.argv) > 1 and sys.argv[1] == "contracted":
         return contracted_main()
+    if len(sys.argv) > 1 and sys.argv[1] == "hiz_edges":
+        return hiz_edges_main()
     if len(sys.argv) > 1 and sys.argv[1] == "pyramid":
         return pyramid_main()
     if len(sys.argv) > 1 and sys.argv[1] == "compact":

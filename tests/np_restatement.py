@@ -152,8 +152,8 @@ def pyramid_levels(w0, h0):
     return mips, np.array(offs), np.array(ws), np.array(hs), off
 
 
-def footprint_min(img, w, h, u, v):
-    """img flat; w, h, u, v arrays (per sample)."""
+def footprint_min(img, w, h, u, v, detail=None):
+    """img flat; w, h, u, v arrays (per sample).  `detail`, a dict, receives the unclamped texel coordinates fx, fy."""
     wf, hf = w.astype(np.float32), h.astype(np.float32)
     x = ((u * wf).astype(np.float32) - F(0.5)).astype(np.float32)
     y = ((v * hf).astype(np.float32) - F(0.5)).astype(np.float32)
@@ -170,30 +170,43 @@ def footprint_min(img, w, h, u, v):
         return out
     x0, x1 = cl(fx, w - 1), cl((fx + F(1)).astype(F), w - 1)
     y0, y1 = cl(fy, h - 1), cl((fy + F(1)).astype(F), h - 1)
+    if detail is not None:
+        detail.update(fx=fx, fy=fy)
     return x0, x1, y0, y1
 
 
-def hiz_sample(pyr, w0, h0, u, v, lod):
+def hiz_sample(pyr, w0, h0, u, v, lod, detail=None):
+    """`detail`, a dict, receives the intermediates (tests/hiz_edges.py takes its census from them): mips, the level and
+    its size, the unclamped and the clamped footprint, the four texels' indices in the packed chain, the result."""
     mips, offs, ws, hs, _ = pyramid_levels(w0, h0)
     with np.errstate(all="ignore"):
         lf = (np.ceil((lod + F(0.5)).astype(F)) - F(1.0)).astype(np.float32)
     level = f2i_clamp(lf, mips - 1)
     w, h, off = ws[level], hs[level], offs[level]
-    x0, x1, y0, y1 = footprint_min(pyr, w, h, u, v)
+    x0, x1, y0, y1 = footprint_min(pyr, w, h, u, v, detail)
     a, b = pyr[off + y0 * w + x0], pyr[off + y0 * w + x1]
     c, d = pyr[off + y1 * w + x0], pyr[off + y1 * w + x1]
-    return gmin(gmin(a, b), gmin(c, d))
+    sampled = gmin(gmin(a, b), gmin(c, d))
+    if detail is not None:
+        detail.update(mips=mips, level=level, w=w, h=h, x0=x0, x1=x1, y0=y0, y1=y1, sampled=sampled,
+                      texels=np.stack([off + y0 * w + x0, off + y0 * w + x1, off + y1 * w + x0, off + y1 * w + x1]))
+    return sampled
 
 
-def occlusion_test(ci, x, y, z, r, pyr, pw, ph, radius, scale):
+def occlusion_test(ci, x, y, z, r, pyr, pw, ph, radius, scale, detail=None):
     """Returns (visible, z') — z' is the possibly flipped z (persists).  Operation by operation as the reference's
-    compiled shaders hold it (oracle/orbit_oracle.c occlusion_test): radius = model-space radius, r = radius * scale."""
+    compiled shaders hold it (oracle/orbit_oracle.c occlusion_test): radius = model-space radius, r = radius * scale.
+    `detail`, a dict, receives cullable (and where it is decided by equality), u, v, lod, closest and hiz_sample's
+    intermediates, per row."""
     n = len(x)
     with np.errstate(all="ignore"):
         if int(ci["projection_type"]) == 0:
             z = (-z).astype(np.float32)
             zn = F(ci["z_near"])
-            cullable = z >= fma32(radius, scale, zn)
+            near = fma32(radius, scale, zn)
+            cullable = z >= near
+            if detail is not None:
+                detail["cullable_tie"] = z == near
             p00, p11 = F(ci["p00_or_width_recipx2"]), F(ci["p11_or_height_recipx2"])
 
             def bounds(c0, c1):
@@ -228,14 +241,19 @@ def occlusion_test(ci, x, y, z, r, pyr, pw, ph, radius, scale):
             u1 = fma32(cl(b2), F(0.5), F(0.5))
             v1 = fma32(cl(b3), F(-0.5), F(0.5))
             cullable = np.ones(n, dtype=bool)
+            if detail is not None:
+                detail["cullable_tie"] = np.zeros(n, dtype=bool)
             rr = F(1.0) / (F(ci["z_far"]) - F(ci["z_near"]))
             closest = (rr * (fma32(radius, scale, z) + F(ci["z_far"])).astype(F)).astype(F)
         width = ((u1 - u0).astype(F) * F(pw)).astype(F)
         height = ((v1 - v0).astype(F) * F(ph)).astype(F)
         u = ((u0 + u1).astype(F) * F(0.5)).astype(F)
         v = ((v0 + v1).astype(F) * F(0.5)).astype(F)
-        sampled = hiz_sample(pyr, pw, ph, u, v, log2c(gmax(width, height)))
+        lod = log2c(gmax(width, height))
+        sampled = hiz_sample(pyr, pw, ph, u, v, lod, detail)
         vis = np.where(cullable, closest >= sampled, True)
+    if detail is not None:
+        detail.update(cullable=cullable, u=u, v=v, lod=lod, closest=closest, visible=vis)
     return vis, z
 
 
@@ -250,8 +268,10 @@ def f2u_sat(f):
     return out
 
 
-def entity_cull(ci, scene_draws, count, entity_draw_count, mesh_infos, entities, vis_words, pyr=None, pyr_size=(0, 0)):
-    """Returns (visible[g], should_draw[g], records list, new entity words or None)."""
+def entity_cull(ci, scene_draws, count, entity_draw_count, mesh_infos, entities, vis_words, pyr=None, pyr_size=(0, 0),
+                detail=None):
+    """Returns (visible[g], should_draw[g], records list, new entity words or None).  `detail`, a dict, receives
+    occlusion_test's intermediates of pass 2 and `reached`, the rows that got as far as that test."""
     end = min(count, (entity_draw_count + 255) // 256 * 256)
     draws = scene_draws[:end]
     g = np.arange(end)
@@ -267,7 +287,9 @@ def entity_cull(ci, scene_draws, count, entity_draw_count, mesh_infos, entities,
     x, y, z, r, scale = transform_sphere(mv, mi["bounding_sphere"])
     visible &= np.where(visible, plane_test(ci, x, y, z, r), False)
     if op == 2:
-        ov, zf = occlusion_test(ci, x, y, z, r, pyr, *pyr_size, mi["bounding_sphere"][:, 3].astype(F), scale)
+        ov, zf = occlusion_test(ci, x, y, z, r, pyr, *pyr_size, mi["bounding_sphere"][:, 3].astype(F), scale, detail)
+        if detail is not None:
+            detail["reached"] = visible.copy()
         z = np.where(visible, zf, z).astype(np.float32) if int(ci["projection_type"]) == 0 else z
         visible = np.where(visible, ov, False)
     should = visible.copy()
@@ -299,8 +321,8 @@ def entity_cull(ci, scene_draws, count, entity_draw_count, mesh_infos, entities,
     return visible, should, np.array(records, dtype=np.uint32).reshape(-1, 4).view(L.MESHLET_DISPATCH).reshape(-1), new_words
 
 
-def meshlet_cull(ci, records, meshlets, entities, materials, mvis, pyr=None, pyr_size=(0, 0)):
-    """Returns (commands, new meshlet visibility words or None)."""
+def meshlet_cull(ci, records, meshlets, entities, materials, mvis, pyr=None, pyr_size=(0, 0), detail=None):
+    """Returns (commands, new meshlet visibility words or None).  `detail`: as for entity_cull."""
     op = int(ci["occlusion_pass"])
     meshlet_occ = int(ci["meshlet_visibility_buffer"]) != L.NONE
     nrec = len(records)
@@ -333,7 +355,9 @@ def meshlet_cull(ci, records, meshlets, entities, materials, mvis, pyr=None, pyr
         rhs = fma32(cutoff, np.sqrt(dot3(dx, dy, dz, dx, dy, dz), dtype=F), r)
         visible &= ~(lhs >= rhs)
     if meshlet_occ and op == 2:
-        ov, _ = occlusion_test(ci, x, y, z, r, pyr, *pyr_size, m["bounding_sphere"][:, 3].astype(F), scale)
+        ov, _ = occlusion_test(ci, x, y, z, r, pyr, *pyr_size, m["bounding_sphere"][:, 3].astype(F), scale, detail)
+        if detail is not None:
+            detail["reached"] = visible.copy()
         visible = np.where(visible, ov, False)
     shl = lambda a: np.where(a < 32, np.uint64(1) << a.astype(np.uint64), 0).astype(np.uint64)
     should = visible & ((shl(alpha) & np.uint64(int(ci["alpha_mode_flag"]))) != 0)

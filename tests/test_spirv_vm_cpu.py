@@ -78,6 +78,20 @@ def test_rerunning_the_binaries_contracted_reproduces_the_committed_vectors(occl
 
 
 @pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not in oracle/_ref")
+@pytest.mark.parametrize("name,fused_dot", [("v_ortho_1x1", False), ("v_persp_16x256", True)])
+def test_rerunning_the_binaries_reproduces_the_committed_hiz_edge_vectors(name, fused_dot):
+    """tests/golden/spirv_cull_hiz_edges.npz: pass 2 on the hostile cases of tests/hiz_edges.py, canonical and contracted."""
+    import make_spirv_vectors as gen
+
+    stored = np.load(os.path.join(HERE, "golden", "spirv_cull_hiz_edges.npz"))
+    fresh = gen.hiz_edges_case(name, fused_dot=fused_dot)
+    for k in gen.HIZ_EDGE_INPUTS + gen.HIZ_EDGE_OUTPUTS:
+        key = f"{name}/contracted/{k}" if fused_dot and k in gen.HIZ_EDGE_OUTPUTS else f"{name}/{k}"
+        assert np.array_equal(np.ascontiguousarray(fresh[k]).view(np.uint8).reshape(-1),
+                              np.ascontiguousarray(stored[key]).view(np.uint8).reshape(-1)), key
+
+
+@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's shader binaries are not in oracle/_ref")
 def test_rerunning_the_binaries_reproduces_a_committed_cluster_vector():
     import make_spirv_vectors as gen
 
