@@ -325,8 +325,16 @@ int32_t orbit_ctx_profile_read(OrbitCtx *ctx, float *avg_ms, uint32_t *launches)
 /*   orbit_expand_visible_records  record list -> MeshletDrawCommandBuffer   */
 /*       in list order (= the canonical order), the command words read from  */
 /*       `meshlet_buffer` under global indices (or from a bound stream that  */
-/*       mirrors it); at most 64 M records per list (the gathered header's   */
-/*       second word is not maintained by the exchanges and not read here).  */
+/*       mirrors it).  What is written depends on the list and on            */
+/*       draw_capacity only.  With S the set bits of all the list's masks    */
+/*       (an entry's mask may be 0: a list can be far longer than what it    */
+/*       expands to, and draw_capacity may be sized for the survivors): the  */
+/*       header is min(S, draw_capacity), the first min(S, draw_capacity)    */
+/*       commands follow in list order and nothing behind them is written;   */
+/*       ORBIT_E_CAPACITY is latched if and only if S > draw_capacity or the */
+/*       list holds more than 64 M records (it is cut there).  No read-back, */
+/*       no synchronisation: capturable.  The gathered header's second word  */
+/*       is not maintained by the exchanges and not read here.               */
 /* ------------------------------------------------------------------------ */
 int32_t orbit_meshlet_cull_visible_records(OrbitCtx *ctx, const OrbitGpuCullInfo *cull_info,
                                            const OrbitMeshletCullBufs *bufs, void *record_buffer,

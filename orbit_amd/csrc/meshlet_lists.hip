@@ -37,23 +37,29 @@ constexpr uint32_t kVrBlock = 1024; // records per block of the record list's ex
 // Commands from a (gathered) record list, in list order = the canonical order: orbit_expand_visible_records.  A count
 // launch sums the survivors of every block of 1024 records; here a block adds up the blocks before it, a wave takes 64
 // records at a time, lays their survivors out in LDS as (record lane, bit) codes at the records' prefix offsets and
-// then writes them 64 commands at a time through LDS (every store covers 256 contiguous bytes).
+// then writes them 64 commands at a time through LDS (every store covers 256 contiguous bytes).  The host does not
+// know how many records the list holds — an entry's mask may be 0, so the list can be far longer than the commands it
+// expands to — and both launches walk the list's blocks with the stride of the grid: what they write depends on the
+// list and on draw_capacity, never on the number of workgroups.
 __global__ __launch_bounds__(256) void visible_records_pop_kernel(const uint8_t *records, uint32_t *block_pop,
                                                                   uint32_t max_blocks) {
     __shared__ uint32_t smem[4];
     const uint32_t n = *reinterpret_cast<const uint32_t *>(records);
-    if (blockIdx.x * kVrBlock >= n || blockIdx.x >= max_blocks) return;
+    const uint32_t nblocks = min((n + kVrBlock - 1u) / kVrBlock, max_blocks);
     const uint32_t *recs = reinterpret_cast<const uint32_t *>(records + ORBIT_VISIBLE_HEADER);
-    uint32_t pop = 0;
+    for (uint32_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+        uint32_t pop = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < 4; k++) {
-        const uint32_t r = blockIdx.x * kVrBlock + k * 256u + threadIdx.x;
-        pop += r < n ? (uint32_t)__popc(recs[3 * (size_t)r + 2]) : 0u;
+        for (uint32_t k = 0; k < 4; k++) {
+            const uint32_t r = b * kVrBlock + k * 256u + threadIdx.x;
+            pop += r < n ? (uint32_t)__popc(recs[3 * (size_t)r + 2]) : 0u;
+        }
+        pop = wave_reduce_add(pop);
+        if ((threadIdx.x & 63) == 0) smem[threadIdx.x >> 6] = pop;
+        __syncthreads();
+        if (threadIdx.x == 0) block_pop[b] = smem[0] + smem[1] + smem[2] + smem[3];
+        __syncthreads(); // smem is rewritten by the next trip
     }
-    pop = wave_reduce_add(pop);
-    if ((threadIdx.x & 63) == 0) smem[threadIdx.x >> 6] = pop;
-    __syncthreads();
-    if (threadIdx.x == 0) block_pop[blockIdx.x] = smem[0] + smem[1] + smem[2] + smem[3];
 }
 
 template <bool STREAM>
@@ -68,93 +74,102 @@ __global__ __launch_bounds__(256) void visible_records_expand_kernel(const uint8
     __shared__ uint32_t s_chunk[kVrBlock / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t n = *reinterpret_cast<const uint32_t *>(records);
-    // the grid covers draw_capacity / 1024 blocks of records (every record holds a survivor: more records than that
-    // cannot fit) and the scratch max_blocks: a longer list is cut there, and says so
+    // the scratch holds the survivor counts of max_blocks blocks of records: a longer list is cut there, and says so
     const uint32_t all_blocks = (n + kVrBlock - 1u) / kVrBlock;
-    const uint32_t nblocks = min(min(all_blocks, max_blocks), gridDim.x);
-    if (all_blocks > nblocks && blockIdx.x == 0 && threadIdx.x == 0) latch_status(status, ORBIT_E_CAPACITY);
-    if (blockIdx.x >= nblocks && blockIdx.x != 0) return;
-    const uint32_t upto = blockIdx.x == 0 ? nblocks : blockIdx.x;
-    uint32_t part = 0;
-    for (uint32_t i = threadIdx.x; i < upto; i += 256u) part += block_pop[i];
-    part = wave_reduce_add(part);
-    if (lane == 0) smem[wave] = part;
-    __syncthreads();
-    const uint32_t before = smem[0] + smem[1] + smem[2] + smem[3];
-    if (blockIdx.x == 0 && threadIdx.x == 0) { // `count` header of the command list
-        *reinterpret_cast<uint32_t *>(draw_buffer) = min(before, draw_capacity);
-        if (before > draw_capacity) latch_status(status, ORBIT_E_CAPACITY);
+    const uint32_t nblocks = min(all_blocks, max_blocks);
+    if (blockIdx.x == 0) { // `count` header of the command list: the survivors of the whole list
+        uint32_t part = 0;
+        for (uint32_t i = threadIdx.x; i < nblocks; i += 256u) part += block_pop[i];
+        part = wave_reduce_add(part);
+        if (lane == 0) smem[4 + wave] = part;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t survivors = smem[4] + smem[5] + smem[6] + smem[7];
+            *reinterpret_cast<uint32_t *>(draw_buffer) = min(survivors, draw_capacity);
+            if (survivors > draw_capacity || all_blocks > nblocks) latch_status(status, ORBIT_E_CAPACITY);
+        }
     }
-    if (blockIdx.x >= nblocks) return;
     const uint32_t *recs = reinterpret_cast<const uint32_t *>(records + ORBIT_VISIBLE_HEADER);
-    // the block's 16 chunks of 64 records: wave w takes chunks 4w .. 4w+3; their survivor counts first
-    uint32_t ent[4], off[4], mask[4];
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++) {
-        const uint32_t r = blockIdx.x * kVrBlock + (wave * 4u + k) * 64u + (uint32_t)lane;
-        const bool in = r < n;
-        ent[k] = in ? recs[3 * (size_t)r + 0] : 0u;
-        off[k] = in ? recs[3 * (size_t)r + 1] : 0u;
-        mask[k] = in ? recs[3 * (size_t)r + 2] : 0u;
-        const uint32_t cs = wave_reduce_add((uint32_t)__popc(mask[k]));
-        if (lane == 0) s_chunk[wave * 4u + k] = cs;
-    }
-    __syncthreads();
-    uint32_t chunk_base = blockIdx.x == 0 ? 0u : before;
-    for (uint32_t c = 0; c < wave * 4u; c++) chunk_base += s_chunk[c];
     uint32_t *cmd = s_cmd[wave];
     uint16_t *code = s_code[wave];
     uint8_t *out = draw_buffer + ORBIT_DRAW_HEADER;
+    uint32_t before = 0, summed = 0; // the survivors of the record blocks [0, summed)
 #pragma unroll 1
-    for (uint32_t k = 0; k < 4; k++) {
-        const uint32_t pc = (uint32_t)__popc(mask[k]);
-        const uint32_t inc = wave_inclusive_scan(pc);
-        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-        {   // lane = record: its survivors' codes at its prefix offset, ascending bits
-            uint32_t m = mask[k], at = inc - pc;
-            while (m != 0u) {
-                code[at++] = (uint16_t)((uint32_t)lane << 5 | (uint32_t)__builtin_ctz(m));
-                m &= m - 1u;
-            }
+    for (uint32_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+        uint32_t part = 0;
+        for (uint32_t i = summed + threadIdx.x; i < b; i += 256u) part += block_pop[i];
+        part = wave_reduce_add(part);
+        if (lane == 0) smem[wave] = part;
+        __syncthreads();
+        before += smem[0] + smem[1] + smem[2] + smem[3];
+        summed = b;
+        if (before >= draw_capacity) break; // this block's commands and all those behind them are past the capacity
+        // the block's 16 chunks of 64 records: wave w takes chunks 4w .. 4w+3; their survivor counts first
+        uint32_t ent[4], off[4], mask[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            const uint32_t r = b * kVrBlock + (wave * 4u + k) * 64u + (uint32_t)lane;
+            const bool in = r < n;
+            ent[k] = in ? recs[3 * (size_t)r + 0] : 0u;
+            off[k] = in ? recs[3 * (size_t)r + 1] : 0u;
+            mask[k] = in ? recs[3 * (size_t)r + 2] : 0u;
+            const uint32_t cs = wave_reduce_add((uint32_t)__popc(mask[k]));
+            if (lane == 0) s_chunk[wave * 4u + k] = cs;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (uint32_t j0 = 0; j0 < total; j0 += 64u) {
-            const uint32_t j = j0 + (uint32_t)lane;
-            const bool valid = j < total;
-            const uint32_t cd = valid ? code[j] : 0u;
-            const uint32_t mi = (uint32_t)__shfl((int)off[k], (int)(cd >> 5), 64) + (cd & 31u);
-            const uint32_t en = (uint32_t)__shfl((int)ent[k], (int)(cd >> 5), 64);
-            ExpandChunk ch;
-            ch.item = make_uint2(mi, en);
-            ch.valid = valid;
-            const uint4 b = expand_gather<STREAM>(meshlets, ms, ch, zero_page, status);
-            uint32_t *c = cmd + lane * 7;
-            c[0] = (b.w >> 24) * 3u;                    // cmd_index_count = triangle_count * 3
-            c[1] = 1u;                                  // cmd_instance_count
-            c[2] = (b.z + ((b.w >> 16) & 0xFFu)) * 4u;  // cmd_first_index = (data_offset + vertex_count) * 4
-            c[3] = b.z;                                 // cmd_vertex_offset = int(data_offset)
-            c[4] = en;                                  // cmd_first_instance = entity_index
-            c[5] = b.y;                                 // meshlet_vertex_offset
-            c[6] = mi;                                  // meshlet_index
+        __syncthreads(); // (also: every wave has read smem before the next trip rewrites it)
+        uint32_t chunk_base = before;
+        for (uint32_t c = 0; c < wave * 4u; c++) chunk_base += s_chunk[c];
+#pragma unroll 1
+        for (uint32_t k = 0; k < 4; k++) {
+            const uint32_t pc = (uint32_t)__popc(mask[k]);
+            const uint32_t inc = wave_inclusive_scan(pc);
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+            {   // lane = record: its survivors' codes at its prefix offset, ascending bits
+                uint32_t m = mask[k], at = inc - pc;
+                while (m != 0u) {
+                    code[at++] = (uint16_t)((uint32_t)lane << 5 | (uint32_t)__builtin_ctz(m));
+                    m &= m - 1u;
+                }
+            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // the chunk's commands as one range-checked window: words past the list or the capacity are dropped
-            const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(chunk_base + j0));
-            const uint32_t room = first < draw_capacity ? draw_capacity - first : 0u;
-            const uint32_t bytes = min(min(total - j0, 64u), room) * 28u;
-            const __amdgpu_buffer_rsrc_t win = __builtin_amdgcn_make_buffer_rsrc(out + (size_t)first * 28u, 0, bytes, 0x00020000);
+            for (uint32_t j0 = 0; j0 < total; j0 += 64u) {
+                const uint32_t j = j0 + (uint32_t)lane;
+                const bool valid = j < total;
+                const uint32_t cd = valid ? code[j] : 0u;
+                const uint32_t mi = (uint32_t)__shfl((int)off[k], (int)(cd >> 5), 64) + (cd & 31u);
+                const uint32_t en = (uint32_t)__shfl((int)ent[k], (int)(cd >> 5), 64);
+                ExpandChunk ch;
+                ch.item = make_uint2(mi, en);
+                ch.valid = valid;
+                const uint4 b = expand_gather<STREAM>(meshlets, ms, ch, zero_page, status);
+                uint32_t *c = cmd + lane * 7;
+                c[0] = (b.w >> 24) * 3u;                    // cmd_index_count = triangle_count * 3
+                c[1] = 1u;                                  // cmd_instance_count
+                c[2] = (b.z + ((b.w >> 16) & 0xFFu)) * 4u;  // cmd_first_index = (data_offset + vertex_count) * 4
+                c[3] = b.z;                                 // cmd_vertex_offset = int(data_offset)
+                c[4] = en;                                  // cmd_first_instance = entity_index
+                c[5] = b.y;                                 // meshlet_vertex_offset
+                c[6] = mi;                                  // meshlet_index
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                // the chunk's commands as one range-checked window: words past the list or the capacity are dropped
+                const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(chunk_base + j0));
+                const uint32_t room = first < draw_capacity ? draw_capacity - first : 0u;
+                const uint32_t bytes = min(min(total - j0, 64u), room) * 28u;
+                const __amdgpu_buffer_rsrc_t win = __builtin_amdgcn_make_buffer_rsrc(out + (size_t)first * 28u, 0, bytes, 0x00020000);
 #pragma unroll
-            for (uint32_t q = 0; q < 7; q++) {
-                const uint32_t w = q * 64u + (uint32_t)lane;
-                __builtin_amdgcn_raw_buffer_store_b32(cmd[w], win, w * 4u, 0, 0);
+                for (uint32_t q = 0; q < 7; q++) {
+                    const uint32_t w = q * 64u + (uint32_t)lane;
+                    __builtin_amdgcn_raw_buffer_store_b32(cmd[w], win, w * 4u, 0, 0);
+                }
+                __builtin_amdgcn_wave_barrier(); // cmd is rewritten by the next trip
             }
-            __builtin_amdgcn_wave_barrier(); // cmd is rewritten by the next trip
+            chunk_base += total;
+            __builtin_amdgcn_wave_barrier(); // code is rewritten by the next chunk
         }
-        chunk_base += total;
-        __builtin_amdgcn_wave_barrier(); // code is rewritten by the next chunk
     }
 }
 
@@ -397,7 +412,9 @@ hipError_t launch_compact_segments(const uint8_t *segments, uint32_t world, uint
 hipError_t launch_visible_records_expand(const uint8_t *records, uint32_t *block_pop, uint32_t max_blocks,
                                          const OrbitMeshlet *meshlets, const MeshletStreamView &ms, uint8_t *draw_buffer,
                                          uint32_t draw_capacity, const void *zero_page, int32_t *status, hipStream_t s) {
-    // a command list of draw_capacity entries has at most that many records behind it
+    // the list's length is on the device: a workgroup per block of records there would be if every record held a survivor
+    // and the commands filled their buffer.  The grid only sets how many blocks are walked side by side: a list whose
+    // records are mostly empty, or one that overflows the buffer, has more blocks than that.
     const uint32_t blocks = max(min((draw_capacity + kVrBlock - 1u) / kVrBlock, max_blocks), 1u);
     hipLaunchKernelGGL(visible_records_pop_kernel, dim3(blocks), dim3(256), 0, s, records, block_pop, max_blocks);
     if (ms.cmd)

@@ -15,6 +15,7 @@ import torch.multiprocessing as mp
 import scenes as sc
 from orbit_amd import layouts as L
 from orbit_amd.dist import shard_ranges
+from record_lists import compact_segments_numpy as _compact_segments_numpy
 
 
 def _free_port():
@@ -141,21 +142,6 @@ def _visible_records(disp, cmds):
     buf[:8].view(np.uint32)[:] = (len(arr), len(cmds))
     buf[8:8 + 12 * len(arr)] = arr.view(np.uint8)
     return buf
-
-
-def _compact_segments_numpy(segments, world, segment_capacity, out, out_capacity, header, stride, stream=None):
-    """orbit_compact_segments restated with numpy (meshlet_lists.hip compact_segments_kernel): the segments' items in
-    rank order behind {total, 0 ..}; a count beyond the segment's capacity is cut, nothing is written past out_capacity."""
-    seg_bytes = header + stride * segment_capacity
-    counts = [min(int(segments[seg_bytes * r:seg_bytes * r + 4].view(torch.int32)[0]), segment_capacity) for r in range(world)]
-    first = 0
-    for r in range(world):
-        n = min(counts[r], max(out_capacity - first, 0))
-        out[header + stride * first:header + stride * (first + n)] = \
-            segments[seg_bytes * r + header:seg_bytes * r + header + stride * n]
-        first += counts[r]
-    out[:header] = 0
-    out[:4].view(torch.int32)[0] = min(sum(counts), out_capacity)
 
 
 # (the ranks' barriers are gloo's host-side monitored_barrier: dist.barrier() asks for the machine's accelerator first,
