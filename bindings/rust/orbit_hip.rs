@@ -39,6 +39,32 @@ pub struct OrbitFrameLate {
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct OrbitEntityTransform { pub position: [f32; 3], pub orientation: [f32; 4], pub scale: [f32; 3] }
 
+pub const ORBIT_SCENE_NONE: u32 = 0xFFFF_FFFF;
+
+/// One entity as orbit_scene_update reads it (48 B, entity order): mesh slot and visibility offset, light kind
+/// (0 Sky, 1 Directional, 2 Point) and its parameters; ORBIT_SCENE_NONE in mesh_index / light_kind = none
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitSceneEntity {
+    pub mesh_index: u32, pub visibility_offset: u32, pub light_kind: u32, pub light_flags: u32,
+    pub light_color: [f32; 3], pub light_intensity: f32, pub light_param: f32,
+    pub irradiance_map_index: u32, pub prefiltered_map_index: u32, pub _pad: u32,
+}
+
+/// The uncapped totals orbit_scene_update leaves on the device
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitSceneCounts { pub draws: u32, pub lights: u32, pub shadows: u32, pub entities: u32 }
+
+/// orbit_scene_update's argument block (96 B): DEVICE pointers; the last four may be null
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitSceneUpdate {
+    pub entities: *const OrbitSceneEntity, pub transforms: *const OrbitEntityTransform,
+    pub entity_data: *mut c_void, pub entity_draw_buffer: *mut c_void, pub light_data: *mut c_void,
+    pub shadow_orientations: *mut f32, pub instance_of_entity: *mut u32, pub light_of_entity: *mut u32,
+    pub counts: *mut OrbitSceneCounts,
+    pub entity_count: u32, pub instance_capacity: u32, pub light_capacity: u32, pub shadow_capacity: u32,
+    pub luminance_cutoff: f32, pub shadow_index_base: u32,
+}
+
 /// orbit_cull_stats' 256-B block of u64 counters (include/orbit_abi_ext.h OrbitCullStats)
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct OrbitCullStats {
@@ -221,6 +247,9 @@ extern "C" {
     pub fn orbit_scene_update_entities(ctx: *mut OrbitCtx, transforms: *const OrbitEntityTransform,
                                        instance_indices: *const u32, count: u32, entity_data: *mut c_void,
                                        entity_capacity: u32, stream: *mut c_void) -> i32;
+    /// All of SceneData::update_scene on the device, from one OrbitSceneEntity and one transform per entity in entity
+    /// order: EntityData rows, the EntityDrawBuffer, LightData rows with shadow indices, shadow orientations, maps.
+    pub fn orbit_scene_update(ctx: *mut OrbitCtx, update: *const OrbitSceneUpdate, stream: *mut c_void) -> i32;
     /// What orbit_entity_cull + orbit_meshlet_cull with these arguments would do, counted per test into a DEVICE
     /// OrbitCullStats (overwritten).  Call it BEFORE the cull: passes 1 and 2 rewrite the visibility words it reads.
     pub fn orbit_cull_stats(ctx: *mut OrbitCtx, cull_info: *const c_void, ebufs: *const OrbitEntityCullBufs,

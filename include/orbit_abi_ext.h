@@ -483,6 +483,104 @@ int32_t orbit_scene_update_entities(OrbitCtx *ctx, const OrbitEntityTransform *t
                                     OrbitEntityData *entity_data, uint32_t entity_capacity, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* The whole scene update on the device.  orbit_scene_update_entities above  */
+/* leaves two thirds of SceneData::update_scene (src/scene.rs:404-492) on    */
+/* the CPU: the EntityDrawBuffer, the LightData[] array with its shadow      */
+/* indices, and the instance order of the transforms themselves.             */
+/* orbit_scene_update builds all of it from two DEVICE arrays in ENTITY      */
+/* order: one 48-B descriptor and one 40-B transform per entity.  It is      */
+/* three ordered stream compactions (entities with a mesh, with a light,     */
+/* directional lights that cast shadows); order comes from prefix sums,      */
+/* never from atomics, and the outputs equal the host mirror's               */
+/* SceneData::update_scene byte for byte.  With e running over the entities: */
+/*   mesh   mesh_index != ORBIT_SCENE_NONE.  r = the mesh-bearing entities   */
+/*          before e: entity_data[r] = entity_gpu_data() of transforms[e]    */
+/*          (the bits of orbit_scene_update_entities), draw r = {r,          */
+/*          mesh_index, visibility_offset} (mesh_index is copied, not        */
+/*          validated), instance_of_entity[e] = r.  The draw buffer's count  */
+/*          word is min(draws, instance_capacity).                           */
+/*   light  light_kind <= 2.  l = the light-bearing entities before e:       */
+/*          light_data[l] = light_gpu_data(luminance_cutoff): colour,        */
+/*          intensity and light_type copied; Sky: the two map indices;       */
+/*          Directional: direction = -(orientation * (0, 0, -1)) in glam's   */
+/*          mul_vec3 expression (its zero products kept), inner_radius =     */
+/*          light_param; Point: position, inner_radius = light_param,        */
+/*          outer_radius = sqrt(intensity / cutoff), both correctly rounded; */
+/*          every other field zero.  light_of_entity[e] = l.                 */
+/*   shadow Directional with bit 0 of light_flags.  s = such lights before   */
+/*          e: shadow_data_index = shadow_index_base + s (u32 arithmetic),   */
+/*          shadow_orientations[s] = the four orientation words as bits.     */
+/*          Every other light's shadow_data_index is 0xFFFFFFFF.             */
+/*   A light_kind in 3 .. 0xFFFFFFFE is none the host can produce: the       */
+/*   entity counts as having no light and ORBIT_E_RANGE is latched.          */
+/* Capacities: a row whose rank is >= its capacity is dropped, nothing       */
+/* behind a capacity is written and ORBIT_E_CAPACITY is latched; ranks and   */
+/* shadow_data_index are assigned as if every row fitted, and *counts and    */
+/* the two maps hold the uncapped values.  shadow_capacity applies only with */
+/* a shadow_orientations array.  Output rows behind the counts are not       */
+/* touched.  Every pointer is a DEVICE pointer, 4-B aligned (entities and    */
+/* transforms: 16 B is faster), entity_data 16-B aligned.                    */
+/*   entity_count == 0  ORBIT_OK: the count word and *counts are written as  */
+/*                      zeros (where given), nothing else                    */
+/*   ORBIT_E_INVALID    NULL update; with entity_count > 0 a NULL entities,  */
+/*                      transforms, entity_data, entity_draw_buffer or       */
+/*                      light_data; a misaligned pointer                     */
+/*   ORBIT_E_CAPACITY   entity_count > caps.max_entities                     */
+/* The entity cull reads the draw count from the buffer on the device and    */
+/* clamps it with its entity_draw_count argument: pass the entity count (an  */
+/* upper bound) and a device-built draw buffer feeds the cull with no        */
+/* read-back.  The call enqueues two launches on the stream, allocates       */
+/* nothing (its scan scratch is part of the context), never synchronises the */
+/* host and can be captured into a graph on its first call; calls on one     */
+/* context must be ordered against each other like the culls.                */
+/* OrbitCaps.arith_profile does not apply.                                   */
+/* Cost beyond the buffers: every workgroup of 256 entities sums the 12-B    */
+/* totals of the workgroups in front of it, so the call reads about          */
+/* 6 B * (entity_count / 256)^2 from L2 on top: 3.5 MB at 195 313 entities,  */
+/* 100 MB at one million (a quarter of the call's own traffic there), and    */
+/* growing with the square beyond.  It is meant for scenes of up to about a  */
+/* million entities; larger ones still give the right bytes, more slowly.    */
+/* ------------------------------------------------------------------------ */
+#define ORBIT_SCENE_NONE 0xFFFFFFFFu
+typedef struct OrbitSceneEntity { /* one per ENTITY, entity order, DEVICE; 48 B */
+    uint32_t mesh_index;        /* MeshHandle slot, ORBIT_SCENE_NONE = no mesh (scene.rs:420) */
+    uint32_t visibility_offset; /* first meshlet-visibility word: the host allocator's (scene.rs:422-431) */
+    uint32_t light_kind;        /* 0 Sky, 1 Directional, 2 Point, ORBIT_SCENE_NONE = no light */
+    uint32_t light_flags;       /* bit 0: cast_shadows */
+    float light_color[3], light_intensity;
+    float light_param;          /* Directional: angular_size, Point: inner_radius */
+    uint32_t irradiance_map_index, prefiltered_map_index; /* Sky */
+    uint32_t _pad;
+} OrbitSceneEntity;
+ORBIT_STATIC_ASSERT(sizeof(OrbitSceneEntity) == 48, "SceneEntity is 48 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSceneEntity, light_kind) == 8, "light_kind @8");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSceneEntity, light_color) == 16, "light_color @16");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSceneEntity, light_param) == 32, "light_param @32");
+typedef struct OrbitSceneCounts { uint32_t draws, lights, shadows, entities; } OrbitSceneCounts; /* uncapped */
+ORBIT_STATIC_ASSERT(sizeof(OrbitSceneCounts) == 16, "SceneCounts is 16 B");
+typedef struct OrbitSceneUpdate {
+    const OrbitSceneEntity *entities;       /* entity_count entries */
+    const OrbitEntityTransform *transforms; /* entity_count entries, ENTITY order */
+    OrbitEntityData *entity_data;           /* instance_capacity rows, 16-B aligned */
+    void *entity_draw_buffer;               /* {u32 count; OrbitEntityDraw[instance_capacity]} */
+    OrbitLightData *light_data;             /* light_capacity rows */
+    float *shadow_orientations;             /* 4 floats per shadow command, shadow_capacity rows; may be NULL */
+    uint32_t *instance_of_entity;           /* entity_count words, NONE where no mesh; may be NULL */
+    uint32_t *light_of_entity;              /* entity_count words, NONE where no light; may be NULL */
+    OrbitSceneCounts *counts;               /* may be NULL */
+    uint32_t entity_count, instance_capacity, light_capacity, shadow_capacity;
+    float luminance_cutoff;
+    uint32_t shadow_index_base;             /* MAX_SHADOW_COMMANDS * frame_index (scene.rs:461) */
+} OrbitSceneUpdate;
+ORBIT_STATIC_ASSERT(sizeof(OrbitSceneUpdate) == 96, "SceneUpdate is 96 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSceneUpdate, counts) == 64, "counts @64");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSceneUpdate, entity_count) == 72, "entity_count @72");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSceneUpdate, luminance_cutoff) == 88, "luminance_cutoff @88");
+
+/* draws, EntityData rows, LightData rows, shadow orientations and both maps of SceneData::update_scene; see above */
+int32_t orbit_scene_update(OrbitCtx *ctx, const OrbitSceneUpdate *update, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Cull statistics.  The cull returns survivors only (dispatch records,     */
 /* draw commands, visibility bits); orbit_cull_stats counts, on the device, */
 /* what it did with every entity-draw and every meshlet: each is counted    */

@@ -72,6 +72,14 @@ class DepthPyramidDesc(C.Structure):
                 ("mip_width", C.c_uint32 * MAX_PYRAMID_MIPS), ("mip_height", C.c_uint32 * MAX_PYRAMID_MIPS)]
 
 
+class SceneUpdate(C.Structure):  # OrbitSceneUpdate
+    _fields_ = [("entities", C.c_void_p), ("transforms", C.c_void_p), ("entity_data", C.c_void_p),
+                ("entity_draw_buffer", C.c_void_p), ("light_data", C.c_void_p), ("shadow_orientations", C.c_void_p),
+                ("instance_of_entity", C.c_void_p), ("light_of_entity", C.c_void_p), ("counts", C.c_void_p),
+                ("entity_count", C.c_uint32), ("instance_capacity", C.c_uint32), ("light_capacity", C.c_uint32),
+                ("shadow_capacity", C.c_uint32), ("luminance_cutoff", C.c_float), ("shadow_index_base", C.c_uint32)]
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -152,6 +160,7 @@ SYMBOLS = {
                                            C.c_uint32, C.c_uint32, C.c_void_p]),
     "orbit_scene_update_entities": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),
+    "orbit_scene_update": (C.c_int32, [C.c_void_p, C.POINTER(SceneUpdate), C.c_void_p]),
     "orbit_cull_stats": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(EntityCullBufs), C.c_uint32,
                                      C.POINTER(MeshletCullBufs), C.c_void_p, C.c_void_p]),
     "orbit_cluster_stats": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -82,6 +82,7 @@ size_t layout_arena(OrbitCtx *ctx, uintptr_t base, uint64_t md32) {
     ctx->a_group_order = (uint32_t *)carve((agroups + 1) * 4);
     ctx->a_coarse_seg = (uint32_t)aseg;
     ctx->a_hit_cache = (uint32_t *)carve(((size_t)caps.max_clusters + kAssignPad) * kHitCache * 4);
+    ctx->s_block_sums = (uint32_t *)carve((ent / 256 + 1) * 3 * 4); // last: nothing in front of it moves
     return off;
 }
 

@@ -1,5 +1,6 @@
 // abi_cull.hip — the C ABI's culls (include/orbit_abi.h): entity and meshlet culls, the task and record-list forms,
-// orbit_cull_views, the shard cull, the record list's expansion, orbit_cull_stats and orbit_scene_update_entities.
+// orbit_cull_views, the shard cull, the record list's expansion, orbit_cull_stats, orbit_scene_update_entities and
+// orbit_scene_update.
 #include "abi_internal.h"
 
 namespace {
@@ -502,6 +503,30 @@ int32_t orbit_scene_update_entities(OrbitCtx *ctx, const OrbitEntityTransform *t
     const hipError_t e = launch_scene_update_entities(transforms, instance_indices, count, entity_data, entity_capacity,
                                                       ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch scene_update_entities");
+    return ORBIT_OK;
+}
+
+// The whole of update_scene from per-entity descriptors and transforms (scene_full.hip): two launches on the stream, the
+// scan scratch is the context's.  No allocation, no host sync: capturable on the first call.  Capacity overflows and
+// light kinds the host cannot produce are latched on the device, not checked here.
+int32_t orbit_scene_update(OrbitCtx *ctx, const OrbitSceneUpdate *update, void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    if (!update) return fail(ctx, ORBIT_E_INVALID, "scene_update: update is NULL");
+    const OrbitSceneUpdate &u = *update;
+    if (u.entity_count > 0 && (!u.entities || !u.transforms || !u.entity_data || !u.entity_draw_buffer || !u.light_data))
+        return fail(ctx, ORBIT_E_INVALID, "scene_update: NULL buffer");
+    if ((uintptr_t)u.entity_data & 15u) return fail(ctx, ORBIT_E_INVALID, "scene_update: entity_data must be 16-B aligned");
+    if (((uintptr_t)u.entities | (uintptr_t)u.transforms | (uintptr_t)u.entity_draw_buffer | (uintptr_t)u.light_data |
+         (uintptr_t)u.shadow_orientations | (uintptr_t)u.instance_of_entity | (uintptr_t)u.light_of_entity |
+         (uintptr_t)u.counts) & 3u)
+        return fail(ctx, ORBIT_E_INVALID, "scene_update: every buffer must be 4-B aligned");
+    if (u.entity_count > ctx->caps.max_entities)
+        return fail(ctx, ORBIT_E_CAPACITY, "scene_update: %u entities > caps.max_entities %u", u.entity_count,
+                    ctx->caps.max_entities);
+    if (u.entity_count == 0 && !u.entity_draw_buffer && !u.counts) return ORBIT_OK; // nothing to write
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_scene_update(u, ctx->s_block_sums, ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch scene_update");
     return ORBIT_OK;
 }
 

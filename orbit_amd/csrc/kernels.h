@@ -360,6 +360,8 @@ hipError_t launch_meshlet_stream_validate(const OrbitMeshlet *meshlets, const Me
 hipError_t launch_scene_update_entities(const OrbitEntityTransform *transforms, const uint32_t *instance_indices,
                                         uint32_t count, OrbitEntityData *entity_data, uint32_t entity_capacity,
                                         int32_t *status, hipStream_t s);
+// scene_full.hip: orbit_scene_update — `u` validated by the entry point; block_sums: scratch, 3 words per 256 entities
+hipError_t launch_scene_update(const OrbitSceneUpdate &u, uint32_t *block_sums, int32_t *status, hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

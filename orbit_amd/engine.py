@@ -247,6 +247,35 @@ class Engine:
                                                          _ptr(entity_data), int(entity_capacity), _stream(stream)),
                    self._ctx)
 
+    # -- the whole scene update on the device: draws, rows, lights and shadow indices (orbit_scene_update)
+    def scene_update(self, entities, transforms, entity_data, entity_draw_buffer, light_data, entity_count=None,
+                     shadow_orientations=None, instance_of_entity=None, light_of_entity=None, counts=None,
+                     instance_capacity=None, light_capacity=None, shadow_capacity=None, luminance_cutoff=0.25,
+                     shadow_index_base=0, stream=None):
+        """SceneData::update_scene on the device.  entities / transforms: device tensors holding one
+        layouts.SCENE_ENTITY (48 B) and one layouts.ENTITY_TRANSFORM (40 B) per entity, in entity order
+        (SceneData.update_scene_device makes them).  Written: entity_data (128-B rows in instance order),
+        entity_draw_buffer ({u32 count; draws}), light_data (64-B rows) and, where given, shadow_orientations (16 B per
+        shadow command), the two u32 maps entity -> instance / light (layouts.NONE where none) and counts
+        (layouts.SCENE_COUNTS, uncapped).  entity_count defaults to the 48-B entries of `entities`, the capacities to
+        what the output tensors hold.  Enqueued on `stream`; rows past a capacity and light kinds above 2 are reported
+        by status() (ORBIT_E_CAPACITY, ORBIT_E_RANGE).  The entity cull takes the draw count from the buffer: pass it
+        entity_draw_count = entity_count (an upper bound) and nothing is read back."""
+        nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
+        u = _lib.SceneUpdate()
+        u.entities, u.transforms, u.entity_data = _ptr(entities), _ptr(transforms), _ptr(entity_data)
+        u.entity_draw_buffer, u.light_data = _ptr(entity_draw_buffer), _ptr(light_data)
+        u.shadow_orientations = _ptr(shadow_orientations)
+        u.instance_of_entity, u.light_of_entity, u.counts = _ptr(instance_of_entity), _ptr(light_of_entity), _ptr(counts)
+        u.entity_count = nbytes(entities) // 48 if entity_count is None else int(entity_count)
+        u.instance_capacity = (min(nbytes(entity_data) // 128, max(nbytes(entity_draw_buffer) - 4, 0) // 12)
+                               if instance_capacity is None else int(instance_capacity))
+        u.light_capacity = nbytes(light_data) // 64 if light_capacity is None else int(light_capacity)
+        u.shadow_capacity = nbytes(shadow_orientations) // 16 if shadow_capacity is None else int(shadow_capacity)
+        u.luminance_cutoff = float(luminance_cutoff)
+        u.shadow_index_base = int(shadow_index_base) & 0xFFFFFFFF
+        _lib.check(self._lib.orbit_scene_update(self._ctx, C.byref(u), _stream(stream)), self._ctx)
+
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                    entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,

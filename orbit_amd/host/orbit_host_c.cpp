@@ -440,6 +440,40 @@ const OrbitEntityTransform *orbit_host_scene_transforms(const void *sc, uint64_t
 int64_t orbit_host_scene_instance_index(const void *sc, uint64_t entity) {
     return ((const scene::SceneData *)sc)->instance_index((size_t)entity);
 }
+int64_t orbit_host_scene_add_entities(void *sc, const OrbitSceneEntity *table, const OrbitEntityTransform *transforms,
+                                      uint64_t count) {
+    int64_t first = -1;
+    const int32_t rc = guarded([&] {
+        if (count && (!table || !transforms)) throw Panic("add_entities: NULL array");
+        first = (int64_t)((scene::SceneData *)sc)->add_entities(table, transforms, (size_t)count);
+    });
+    return rc ? -1 : first;
+}
+int32_t orbit_host_scene_set_mesh(void *sc, uint64_t entity, int32_t mesh) {
+    return guarded([&] {
+        ((scene::SceneData *)sc)->set_mesh((size_t)entity, mesh >= 0 ? std::optional<uint32_t>((uint32_t)mesh) : std::nullopt);
+    });
+}
+int32_t orbit_host_scene_update_device(void *sc, const OrbitMeshInfo *mesh_infos, uint64_t mesh_info_count) {
+    return guarded([&] { ((scene::SceneData *)sc)->update_scene_device(mesh_infos, (size_t)mesh_info_count); });
+}
+const OrbitSceneEntity *orbit_host_scene_entity_table(const void *sc, uint64_t *count) {
+    const scene::SceneData *s = (const scene::SceneData *)sc;
+    *count = s->entity_table_cache.size();
+    return s->entity_table_cache.data();
+}
+uint64_t orbit_host_scene_shadow_orientations(const void *sc, float *orientations, uint64_t capacity) {
+    const scene::SceneData *s = (const scene::SceneData *)sc;
+    for (uint64_t i = 0; i < s->shadow_commands.size() && i < capacity; i++) {
+        const Quat &q = s->shadow_commands[i].orientation;
+        const float v[4] = {q.x, q.y, q.z, q.w};
+        std::memcpy(orientations + 4 * i, v, sizeof(v));
+    }
+    return s->shadow_commands.size();
+}
+int64_t orbit_host_scene_light_index(const void *sc, uint64_t entity) {
+    return ((const scene::SceneData *)sc)->light_index((size_t)entity);
+}
 
 // ---------------------------------------------------------------- asset side (orbit_assets.hpp), host only
 int32_t orbit_host_compute_meshlets(const float *positions, uint64_t vertex_count, const uint32_t *indices,

@@ -179,6 +179,21 @@ int32_t orbit_host_scene_update_deferred(void *scene, const OrbitMeshInfo *mesh_
 const OrbitEntityTransform *orbit_host_scene_transforms(const void *scene, uint64_t *count);
 /* the entity's instance index (its row of entity_data) from the latest update, -1 if it had none */
 int64_t orbit_host_scene_instance_index(const void *scene, uint64_t entity);
+/* `count` unnamed entities from one OrbitSceneEntity (visibility_offset is not read) and one transform each: the
+ * inverse of orbit_host_scene_entity_table.  Returns the first one's index, -1 + orbit_host_last_error() on failure */
+int64_t orbit_host_scene_add_entities(void *scene, const OrbitSceneEntity *table, const OrbitEntityTransform *transforms,
+                                      uint64_t count);
+/* another mesh for the entity, -1 = None; its visibility words stay its own */
+int32_t orbit_host_scene_set_mesh(void *scene, uint64_t entity, int32_t mesh);
+/* what stays on the host when orbit_scene_update builds draws, rows and lights on the device: allocates the visibility
+ * words of mesh-bearing entities that have none and fills one OrbitSceneEntity and one transform per entity, in ENTITY
+ * order (orbit_host_scene_transforms then returns every entity's); the caches of orbit_host_scene_update are untouched */
+int32_t orbit_host_scene_update_device(void *scene, const OrbitMeshInfo *mesh_infos, uint64_t mesh_info_count);
+const OrbitSceneEntity *orbit_host_scene_entity_table(const void *scene, uint64_t *count);
+/* the shadow commands' orientations (x, y, z, w) of the latest update, at most `capacity` of them; returns their number */
+uint64_t orbit_host_scene_shadow_orientations(const void *scene, float *orientations, uint64_t capacity);
+/* the entity's row of light_data from the latest orbit_host_scene_update, -1 if it had none */
+int64_t orbit_host_scene_light_index(const void *scene, uint64_t entity);
 
 /* ---- asset side (orbit_assets.hpp): mesh -> Meshlet[] + meshlet data, mesh bounds (host only) ---- */
 /* assets::mesh::compute_meshlets (mesh.rs:292-338).  Two-call protocol: with out_meshlets == NULL only the counts are

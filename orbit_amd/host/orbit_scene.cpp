@@ -9,25 +9,29 @@ namespace orbit {
 namespace collections {
 
 FreeListAllocator::FreeListAllocator(size_t size) { // freelist_alloc.rs:27-38
-    blocks_.insert(Block{true, BlockRange{0, size}, std::nullopt, std::nullopt});
+    const Index first = blocks_.insert(Block{true, BlockRange{0, size}, std::nullopt, std::nullopt});
+    free_blocks_[first.slot] = first;
 }
 
 std::optional<std::pair<Index, BlockRange>> FreeListAllocator::allocate(size_t size) {
     // :41-45 — iter().filter(free && fits).min_by_key(size): the FIRST of equally small blocks in slot order
     std::optional<Index> best;
     size_t best_size = 0;
-    blocks_.for_each([&](Index i, const Block &b) {
-        if (!b.free || b.range.size() < size) return;
+    for (const auto &slot_index : free_blocks_) { // the free blocks in slot order
+        const Index i = slot_index.second;
+        const Block &b = *blocks_.get(i);
+        if (b.range.size() < size) continue;
         if (!best || b.range.size() < best_size) {
             best = i;
             best_size = b.range.size();
         }
-    });
+    }
     if (!best) return std::nullopt;
     const Index free_block_index = *best;
     Block *free_block = blocks_.get_mut(free_block_index);
     if (free_block->range.size() == size) { // :47-50
         free_block->free = false;
+        free_blocks_.erase(free_block_index.slot);
         return std::make_pair(free_block_index, free_block->range);
     }
     // :52-71 — the allocation takes the front of the free block and is linked in before it
@@ -57,7 +61,9 @@ void FreeListAllocator::deallocate(Index index) { // :74-104
     const std::optional<Index> prev_free_index = free_neighbour(blocks_.get(index)->prev_index);
     const std::optional<Index> next_free_index = free_neighbour(blocks_.get(index)->next_index);
     blocks_.get_mut(index)->free = true;
+    free_blocks_[index.slot] = index;
     if (prev_free_index) {
+        free_blocks_.erase(prev_free_index->slot);
         const Block prev_block = *blocks_.remove(*prev_free_index);
         if (prev_block.prev_index)
             if (Block *pp = blocks_.get_mut(*prev_block.prev_index)) pp->next_index = index;
@@ -66,6 +72,7 @@ void FreeListAllocator::deallocate(Index index) { // :74-104
         b->range.start = prev_block.range.start;
     }
     if (next_free_index) {
+        free_blocks_.erase(next_free_index->slot);
         const Block next_block = *blocks_.remove(*next_free_index);
         if (next_block.next_index)
             if (Block *nn = blocks_.get_mut(*next_block.next_index)) nn->prev_index = index;
@@ -151,6 +158,38 @@ size_t SceneData::add_entity(EntityData data) {
     return index;
 }
 
+size_t SceneData::add_entities(const OrbitSceneEntity *table, const OrbitEntityTransform *transforms, size_t count) {
+    const size_t first = entities.size();
+    entities.reserve(first + count);
+    for (size_t i = 0; i < count; i++) {
+        const OrbitSceneEntity &d = table[i];
+        const OrbitEntityTransform &t = transforms[i];
+        EntityData e;
+        e.transform.position = {t.position[0], t.position[1], t.position[2]};
+        e.transform.orientation = {t.orientation[0], t.orientation[1], t.orientation[2], t.orientation[3]};
+        e.transform.scale = {t.scale[0], t.scale[1], t.scale[2]};
+        if (d.mesh_index != ORBIT_SCENE_NONE) e.mesh = d.mesh_index;
+        if (d.light_kind != ORBIT_SCENE_NONE) {
+            if (d.light_kind > 2u) throw Panic("add_entities: light_kind is not a LightKind");
+            Light l;
+            l.color = {d.light_color[0], d.light_color[1], d.light_color[2]};
+            l.intensity = d.light_intensity;
+            l.kind = (LightKind)d.light_kind;
+            l.param = d.light_param;
+            l.irradiance_map_index = d.irradiance_map_index, l.prefiltered_map_index = d.prefiltered_map_index;
+            l.cast_shadows = (d.light_flags & 1u) != 0;
+            e.light = l;
+        }
+        entities.push_back(std::move(e));
+    }
+    return first;
+}
+
+void SceneData::set_mesh(size_t entity, std::optional<uint32_t> mesh) {
+    if (entity >= entities.size()) throw Panic("set_mesh: entity index out of range");
+    entities[entity].mesh = mesh;
+}
+
 void SceneData::update_scene(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff,
                              size_t frame_index) {
     update(mesh_infos, mesh_info_count, luminance_cutoff, frame_index, false);
@@ -163,6 +202,54 @@ void SceneData::update_scene_deferred(const OrbitMeshInfo *mesh_infos, size_t me
 
 int64_t SceneData::instance_index(size_t entity) const {
     return entity < instance_index_.size() ? instance_index_[entity] : -1;
+}
+
+int64_t SceneData::light_index(size_t entity) const {
+    if (entity >= entities.size() || !entities[entity].light || !entities[entity].light->light_index) return -1;
+    return (int64_t)*entities[entity].light->light_index;
+}
+
+// scene.rs:422-431: the entity's visibility words, allocated on first use and kept from then on
+size_t SceneData::visibility_offset_of(EntityData &entity, const OrbitMeshInfo *mesh_infos, size_t mesh_info_count) {
+    if (entity.visibility_buffer_range) return entity.visibility_buffer_range->range.start;
+    const uint32_t mesh = *entity.mesh;
+    if (mesh >= mesh_info_count) throw Panic("update_scene: mesh slot out of range (index panic, scene.rs:425)");
+    const size_t meshlet_count = mesh_infos[mesh].mesh_lods[0].meshlet_count;
+    const auto a = meshlet_visibility_allocator_.allocate((meshlet_count + 31) / 32);
+    if (!a) throw Panic("update_scene: meshlet visibility words exhausted (unwrap on None, scene.rs:427)");
+    entity.visibility_buffer_range = VisibilityBufferRange{a->first, a->second};
+    return a->second.start;
+}
+
+void SceneData::update_scene_device(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count) {
+    entity_table_cache.clear();
+    entity_transform_cache.clear();
+    entity_table_cache.reserve(entities.size());
+    entity_transform_cache.reserve(entities.size());
+    for (EntityData &entity : entities) {
+        OrbitSceneEntity d;
+        std::memset(&d, 0, sizeof(d));
+        d.mesh_index = ORBIT_SCENE_NONE, d.light_kind = ORBIT_SCENE_NONE;
+        if (entity.mesh) {
+            d.mesh_index = *entity.mesh;
+            d.visibility_offset = (uint32_t)visibility_offset_of(entity, mesh_infos, mesh_info_count);
+        }
+        if (entity.light) {
+            const Light &l = *entity.light;
+            d.light_kind = (uint32_t)l.kind;
+            d.light_flags = l.cast_shadows ? 1u : 0u;
+            d.light_color[0] = l.color.x, d.light_color[1] = l.color.y, d.light_color[2] = l.color.z;
+            d.light_intensity = l.intensity;
+            d.light_param = l.param;
+            d.irradiance_map_index = l.irradiance_map_index, d.prefiltered_map_index = l.prefiltered_map_index;
+        }
+        entity_table_cache.push_back(d);
+        const passes::Transform &t = entity.transform;
+        entity_transform_cache.push_back(OrbitEntityTransform{{t.position.x, t.position.y, t.position.z},
+                                                              {t.orientation.x, t.orientation.y, t.orientation.z,
+                                                               t.orientation.w},
+                                                              {t.scale.x, t.scale.y, t.scale.z}});
+    }
 }
 
 void SceneData::update(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff,
@@ -178,17 +265,7 @@ void SceneData::update(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, 
         if (entity.mesh) { // :420-437
             const uint32_t mesh = *entity.mesh;
             const uint32_t instance_index = (uint32_t)entity_draw_cache.size();
-            size_t visibility_offset;
-            if (entity.visibility_buffer_range) {
-                visibility_offset = entity.visibility_buffer_range->range.start;
-            } else {
-                if (mesh >= mesh_info_count) throw Panic("update_scene: mesh slot out of range (index panic, scene.rs:425)");
-                const size_t meshlet_count = mesh_infos[mesh].mesh_lods[0].meshlet_count;
-                const auto a = meshlet_visibility_allocator_.allocate((meshlet_count + 31) / 32);
-                if (!a) throw Panic("update_scene: meshlet visibility words exhausted (unwrap on None, scene.rs:427)");
-                entity.visibility_buffer_range = VisibilityBufferRange{a->first, a->second};
-                visibility_offset = a->second.start;
-            }
+            const size_t visibility_offset = visibility_offset_of(entity, mesh_infos, mesh_info_count);
             if (deferred) {
                 const passes::Transform &t = entity.transform;
                 entity_transform_cache.push_back(OrbitEntityTransform{{t.position.x, t.position.y, t.position.z},

@@ -7,6 +7,7 @@
 // C++ because this image has no Rust toolchain.  Host code only: nothing here touches the device.
 #pragma once
 #include <cstdint>
+#include <map>
 #include <optional>
 #include <string>
 #include <utility>
@@ -119,6 +120,9 @@ class FreeListAllocator {
         std::optional<Index> prev_index, next_index;
     };
     Arena<Block> blocks_;
+    // the free blocks by slot: allocate visits only these, in the arena's slot order (a scene that only allocates has
+    // one free block among all its blocks, and visiting every block made n allocations cost n^2)
+    std::map<uint32_t, Index> free_blocks_;
 };
 
 } // namespace collections
@@ -183,9 +187,18 @@ class SceneData {
     std::vector<OrbitLightData> light_data_cache;
     std::vector<ShadowCommand> shadow_commands; // what update_scene hands to ShadowRenderer::add_shadow
     // update_scene_deferred: every drawn entity's transform in instance order, the input of orbit_scene_update_entities
+    // (update_scene_device: EVERY entity's transform, in entity order)
     std::vector<OrbitEntityTransform> entity_transform_cache;
+    // update_scene_device: one descriptor per entity in entity order, the other input of orbit_scene_update
+    std::vector<OrbitSceneEntity> entity_table_cache;
 
     size_t add_entity(EntityData data); // scene.rs:398-402
+    // `count` unnamed entities from the arrays update_scene_device makes (a descriptor's visibility_offset is not read:
+    // visibility words are the allocator's); returns the index of the first
+    size_t add_entities(const OrbitSceneEntity *table, const OrbitEntityTransform *transforms, size_t count);
+    // gives the entity another mesh or none; the visibility words it has stay its own, as an entity's of the
+    // reference do when its mesh field is reassigned
+    void set_mesh(size_t entity, std::optional<uint32_t> mesh);
     // scene.rs:404-492.  `mesh_infos` = assets.shared_stuff.mesh_infos; an entity whose visibility words cannot be
     // allocated panics like the reference's unwrap (:427).
     void update_scene(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff,
@@ -194,14 +207,22 @@ class SceneData {
     // shadow commands, but entity_transform_cache is filled instead of entity_data_cache (which is left empty)
     void update_scene_deferred(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff,
                                size_t frame_index);
+    // What must stay on the host when orbit_scene_update builds the draws, rows and lights on the device: visibility
+    // words are allocated for the mesh-bearing entities that have none (as update_scene would, in entity order), and
+    // entity_table_cache and entity_transform_cache are filled for ALL entities in entity order.  The draw, data and
+    // light caches, the shadow commands and the indices of the latest update_scene are left as they are.
+    void update_scene_device(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count);
     // the entity's instance index (its row of entity_data) from the latest update; -1 if it had none (no mesh, or added
     // since)
     int64_t instance_index(size_t entity) const;
     // the bytes written at offset 0 of entity_draw_buffer (:470-481): u32 count, then the draws
     std::vector<uint8_t> entity_draw_buffer_bytes() const;
+    // the entity's row of light_data from the latest update_scene (Light::_light_index); -1 if it had none
+    int64_t light_index(size_t entity) const;
     collections::FreeListAllocator &meshlet_visibility_allocator() { return meshlet_visibility_allocator_; }
 
   private:
+    size_t visibility_offset_of(EntityData &entity, const OrbitMeshInfo *mesh_infos, size_t mesh_info_count);
     void update(const OrbitMeshInfo *mesh_infos, size_t mesh_info_count, float luminance_cutoff, size_t frame_index,
                 bool deferred);
     collections::FreeListAllocator meshlet_visibility_allocator_;

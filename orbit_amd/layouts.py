@@ -28,6 +28,14 @@ ENTITY_DRAW = np.dtype([("entity_index", "<u4"), ("mesh_index", "<u4"), ("visibi
 ENTITY_DATA = np.dtype([("model_matrix", "<f4", (16,)), ("normal_matrix", "<f4", (16,))])
 # OrbitEntityTransform (include/orbit_abi_ext.h): scene.rs Transform, the input of orbit_scene_update_entities
 ENTITY_TRANSFORM = np.dtype([("position", "<f4", (3,)), ("orientation", "<f4", (4,)), ("scale", "<f4", (3,))])
+# OrbitSceneEntity (include/orbit_abi_ext.h): one descriptor per entity, the other input of orbit_scene_update
+SCENE_ENTITY = np.dtype([
+    ("mesh_index", "<u4"), ("visibility_offset", "<u4"), ("light_kind", "<u4"), ("light_flags", "<u4"),
+    ("light_color", "<f4", (3,)), ("light_intensity", "<f4"), ("light_param", "<f4"),
+    ("irradiance_map_index", "<u4"), ("prefiltered_map_index", "<u4"), ("_pad", "<u4"),
+])
+# OrbitSceneCounts: the uncapped totals orbit_scene_update leaves on the device
+SCENE_COUNTS = np.dtype([("draws", "<u4"), ("lights", "<u4"), ("shadows", "<u4"), ("entities", "<u4")])
 # types.glsl:128-141, src/assets/mod.rs:18-28
 MESH_INFO = np.dtype([
     ("bounding_sphere", "<f4", (4,)), ("aabb_min", "<f4", (4,)), ("aabb_max", "<f4", (4,)),
@@ -127,7 +135,7 @@ _SIZES = {
     "GPU_CULL_INFO": (GPU_CULL_INFO, 400), "CLUSTER_DEPTH_BOUNDS": (CLUSTER_DEPTH_BOUNDS, 8),
     "MARK_ACTIVE_PUSH": (MARK_ACTIVE_PUSH, 56), "CLUSTER_CULL_INFO": (CLUSTER_CULL_INFO, 192),
     "GPU_CLUSTER_INFO_BUFFER": (GPU_CLUSTER_INFO_BUFFER, 52), "CULL_STATS": (CULL_STATS, 256),
-    "CLUSTER_STATS": (CLUSTER_STATS, 256),
+    "CLUSTER_STATS": (CLUSTER_STATS, 256), "SCENE_ENTITY": (SCENE_ENTITY, 48), "SCENE_COUNTS": (SCENE_COUNTS, 16),
 }
 for _name, (_dt, _sz) in _SIZES.items():
     assert _dt.itemsize == _sz, (_name, _dt.itemsize, _sz)
@@ -137,6 +145,7 @@ assert GPU_CULL_INFO.fields["lod_target_pos_view_space"][1] == 384
 assert MATERIAL.fields["alpha_mode"][1] == 64
 assert MESH_INFO.fields["mesh_lods"][1] == 64
 assert ENTITY_TRANSFORM.fields["orientation"][1] == 12 and ENTITY_TRANSFORM.fields["scale"][1] == 28
+assert SCENE_ENTITY.fields["light_kind"][1] == 8 and SCENE_ENTITY.fields["light_param"][1] == 32
 assert CLUSTER_CULL_INFO.fields["global_light_count"][1] == 176
 assert CULL_STATS.fields["records"][1] == 48 and CULL_STATS.fields["lod_drawn"][1] == 64
 assert CULL_STATS.fields["meshlets"][1] == 128 and CULL_STATS.fields["meshlet_drawn"][1] == 184

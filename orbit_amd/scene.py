@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import layouts as L
-from .passes import _check, lib
+from .passes import HOST_PANIC, _check, lib
 
 SKY, DIRECTIONAL, POINT = 0, 1, 2  # LightKind, scene.rs:136-141
 
@@ -75,6 +75,16 @@ def _h():
         h.orbit_host_scene_transforms.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         h.orbit_host_scene_instance_index.restype = C.c_int64
         h.orbit_host_scene_instance_index.argtypes = [C.c_void_p, C.c_uint64]
+        h.orbit_host_scene_add_entities.restype = C.c_int64
+        h.orbit_host_scene_add_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        h.orbit_host_scene_set_mesh.argtypes = [C.c_void_p, C.c_uint64, C.c_int32]
+        h.orbit_host_scene_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        h.orbit_host_scene_entity_table.restype = C.c_void_p
+        h.orbit_host_scene_entity_table.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        h.orbit_host_scene_shadow_orientations.restype = C.c_uint64
+        h.orbit_host_scene_shadow_orientations.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        h.orbit_host_scene_light_index.restype = C.c_int64
+        h.orbit_host_scene_light_index.argtypes = [C.c_void_p, C.c_uint64]
         _bound = True
     return h
 
@@ -180,6 +190,24 @@ class SceneData:
         e.name = None if name is None else name.encode()
         return int(_h().orbit_host_scene_add_entity(self._p, C.byref(e)))
 
+    def add_entities(self, table, transforms):
+        """One unnamed entity per layouts.SCENE_ENTITY row of `table` and layouts.ENTITY_TRANSFORM row of `transforms`
+        (the arrays entity_table() and transform_cache() return after update_scene_device; visibility_offset is not
+        read).  Returns the index of the first."""
+        table = np.ascontiguousarray(table, dtype=L.SCENE_ENTITY)
+        transforms = np.ascontiguousarray(transforms, dtype=L.ENTITY_TRANSFORM)
+        if len(table) != len(transforms):
+            raise ValueError("one transform per entity")
+        first = int(_h().orbit_host_scene_add_entities(self._p, table.ctypes.data_as(C.c_void_p),
+                                                       transforms.ctypes.data_as(C.c_void_p), len(table)))
+        if first < 0:
+            _check(HOST_PANIC)
+        return first
+
+    def set_mesh(self, entity, mesh):
+        """Another mesh slot for the entity, or None; the visibility words it already has stay its own."""
+        _check(_h().orbit_host_scene_set_mesh(self._p, entity, -1 if mesh is None else int(mesh)))
+
     def set_transform(self, entity, position, orientation=(0, 0, 0, 1), scale=(1, 1, 1)):
         _check(_h().orbit_host_scene_set_transform(self._p, entity, (C.c_float * 3)(*position),
                                                    (C.c_float * 4)(*orientation), (C.c_float * 3)(*scale)))
@@ -197,8 +225,32 @@ class SceneData:
         _check(_h().orbit_host_scene_update_deferred(self._p, mi.ctypes.data_as(C.c_void_p), len(mi), luminance_cutoff,
                                                      frame_index))
 
+    def update_scene_device(self, mesh_infos):
+        """What stays on the host when Engine.scene_update builds draws, rows and lights on the device: visibility
+        words for the mesh-bearing entities that have none; then entity_table() and transform_cache() hold one row per
+        entity, in entity order.  The caches of update_scene are left as they are."""
+        mi = np.ascontiguousarray(mesh_infos, dtype=L.MESH_INFO)
+        _check(_h().orbit_host_scene_update_device(self._p, mi.ctypes.data_as(C.c_void_p), len(mi)))
+
+    def entity_table(self):
+        """layouts.SCENE_ENTITY rows, one per entity in entity order (update_scene_device)."""
+        return self._cache(_h().orbit_host_scene_entity_table, L.SCENE_ENTITY)
+
+    def shadow_orientations(self):
+        """(n, 4) float32: the orientations (x, y, z, w) of the latest update's shadow commands, in their order."""
+        n = self.shadow_command_count()
+        out = np.zeros((n, 4), dtype=np.float32)
+        if n:
+            _h().orbit_host_scene_shadow_orientations(self._p, out.ctypes.data_as(C.c_void_p), n)
+        return out
+
+    def light_index(self, entity):
+        """The entity's row of light_data from the latest update_scene, or -1."""
+        return int(_h().orbit_host_scene_light_index(self._p, entity))
+
     def transform_cache(self):
-        """layouts.ENTITY_TRANSFORM rows of the drawn entities in instance order (update_scene_deferred)."""
+        """layouts.ENTITY_TRANSFORM rows of the drawn entities in instance order (update_scene_deferred), or of every
+        entity in entity order (update_scene_device)."""
         return self._cache(_h().orbit_host_scene_transforms, L.ENTITY_TRANSFORM)
 
     def instance_index(self, entity):
