@@ -85,6 +85,29 @@ pub struct OrbitClusterStats {
     pub clusters_by_lights: [u64; 5], pub reserved1: [u64; 3], pub samples_by_lights: [u64; 5], pub reserved2: [u64; 11],
 }
 
+/// meshopt::Bounds as orbit_meshlet_bounds writes it (48 B)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitMeshletBoundsFull {
+    pub center: [f32; 3], pub radius: f32, pub cone_apex: [f32; 3], pub cone_cutoff: f32, pub cone_axis: [f32; 3],
+    pub cone_axis_s8: [i8; 3], pub cone_cutoff_s8: i8,
+}
+
+pub const ORBIT_BOUNDS_KEEP_RECORDS: u32 = 1;
+
+/// orbit_meshlet_bounds' argument block (96 B, HOST): DEVICE pointers; meshlet_indices and full may be null
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitMeshletBoundsJob {
+    pub meshlets: *mut c_void, pub meshlet_data: *const u32, pub vertices: *const c_void,
+    pub meshlet_indices: *const u32, pub full: *mut OrbitMeshletBoundsFull,
+    pub first_meshlet: u64, pub meshlet_count: u64, pub meshlet_capacity: u64, pub meshlet_data_words: u64,
+    pub vertex_count: u64,
+    pub vertex_stride: u32, pub position_offset: u32, pub flags: u32, pub _pad: u32,
+}
+
+/// One mesh of orbit_mesh_bounds (12 B, DEVICE): the vertices [first_vertex, first_vertex + vertex_count)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitMeshBoundsRange { pub mesh_index: u32, pub first_vertex: u32, pub vertex_count: u32 }
+
 /// push-constant order of shaders/entity_cull.comp:17-23 (== draw_gen.rs:372-376)
 #[repr(C)]
 pub struct OrbitEntityCullBufs {
@@ -259,6 +282,15 @@ extern "C" {
     /// Writes nothing else, uses no context scratch: before, after or beside the chain.
     pub fn orbit_cluster_stats(ctx: *mut OrbitCtx, push: *const c_void, info: *const c_void, depth: *const f32,
                                lights: *const c_void, stats: *mut OrbitClusterStats, stream: *mut c_void) -> i32;
+    /// Bounding sphere, snorm8 cone axis and cutoff (bytes 0..19) of the selected Meshlet records recomputed on the
+    /// device from the vertex buffer, bit-equal to meshopt's bounds as the host mirror restates them.  Call it after a
+    /// vertex write and before orbit_meshlet_stream_update of the same range.
+    pub fn orbit_meshlet_bounds(ctx: *mut OrbitCtx, job: *const OrbitMeshletBoundsJob, stream: *mut c_void) -> i32;
+    /// Sphere and AABB of mesh_infos[mesh_index] per DEVICE range of vertices (gltf_loader.rs:480-506); then
+    /// orbit_meshlet_stream_update_meshes if a mesh side table is bound.
+    pub fn orbit_mesh_bounds(ctx: *mut OrbitCtx, ranges: *const OrbitMeshBoundsRange, range_count: u32,
+                             vertices: *const c_void, vertex_count: u64, vertex_stride: u32, position_offset: u32,
+                             mesh_infos: *mut c_void, mesh_capacity: u32, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

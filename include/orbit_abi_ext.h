@@ -735,6 +735,100 @@ ORBIT_STATIC_ASSERT(offsetof(OrbitClusterStats, reserved2) == 168, "reserved2 @1
 int32_t orbit_cluster_stats(OrbitCtx *ctx, const OrbitMarkActivePush *push, const OrbitClusterCullInfo *info,
                             const float *depth, const OrbitLightData *lights, OrbitClusterStats *stats, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* Geometry bounds on the device.  The 20 bytes of a Meshlet that decide    */
+/* the frustum, cone and HiZ tests (bounding sphere, snorm8 cone axis and   */
+/* cutoff) and the 40 bytes of a MeshInfo that decide the entity test       */
+/* (sphere, AABB) are functions of the vertex positions.  A renderer that   */
+/* moves vertices on the device (skinning, morphing, a streamed LOD)        */
+/* refits them here instead of reading the vertex buffer back.              */
+/*                                                                          */
+/* orbit_meshlet_bounds: for every selected meshlet m the device decodes    */
+/* the meshlet as the mesh shader does (forward_depth_prepass.mesh:44,55:   */
+/* global vertex = vertex_offset + meshlet_data[data_offset + local], u8    */
+/* corners from byte (data_offset + vertex_count) * 4) and computes         */
+/* meshopt_computeClusterBounds as the host mirror restates it              */
+/* (orbit_amd/host/orbit_assets.cpp compute_meshlet_bounds): the Ritter     */
+/* sphere of the corners of the non-degenerate triangles, the sphere of     */
+/* their unit normals as the cone axis, sqrt(1 - mindp^2), snorm8 with the  */
+/* cutoff rounded up.  Contract: the bytes equal the host mirror's, bit for */
+/* bit, for EVERY input (degenerate triangles, NaN, infinities, denormals,  */
+/* overflowing squares, triangle and vertex counts up to 255).  One thing   */
+/* is canonical: a float that is NaN is written as the quiet NaN 0x7FC00000 */
+/* by the device and by the host export alike (the sign and payload of an   */
+/* x86-64 NaN depend on the host compiler's operand order, not on the       */
+/* algorithm).  It writes                                                   */
+/* bytes 0..19 of record m unless ORBIT_BOUNDS_KEEP_RECORDS is set, and the */
+/* whole bounds to full[i] if `full` is given; bytes 20..31 of a record and */
+/* every unselected record are never written.  A meshlet selected twice by  */
+/* an index list is computed twice, to the same bytes.                      */
+/*                                                                          */
+/* Range checks, on the device: a selected meshlet whose index is >=        */
+/* meshlet_capacity, whose data reaches beyond meshlet_data_words, that     */
+/* names a vertex >= vertex_count (the sum is taken in 64 bits) or has a    */
+/* corner >= its own vertex_count is left unwritten, its `full` row is      */
+/* zero-filled and ORBIT_E_RANGE is latched (orbit_ctx_status); the other   */
+/* meshlets are still written.  Nothing out of range is read.               */
+/*   ORBIT_E_INVALID  job NULL; meshlets, meshlet_data or vertices NULL     */
+/*                    with meshlet_count > 0; vertex_stride <               */
+/*                    position_offset + 12; stride or offset no multiple of */
+/*                    4; meshlets not 16-B aligned, another pointer not 4-B */
+/*                    aligned; KEEP_RECORDS without `full`; unknown flags   */
+/* A count of 0 is ORBIT_OK without a launch.  The call allocates nothing,  */
+/* uses no scratch and never synchronises the host: a graph can capture it  */
+/* on its first call.  caps.arith_profile and dispatch_size do not apply.   */
+/*                                                                          */
+/* THE RECORDS ARE THE SOURCE OF THE DERIVED STREAMS: after a refit, call   */
+/* orbit_meshlet_stream_update of the same range before the next cull that  */
+/* reads a bound stream (caps.validate_streams finds a forgotten one:       */
+/* ORBIT_E_STALE).  Likewise orbit_meshlet_stream_update_meshes after       */
+/* orbit_mesh_bounds when a mesh side table is bound.                       */
+/* ------------------------------------------------------------------------ */
+typedef struct OrbitMeshletBoundsFull { /* meshopt::Bounds, 48 B */
+    float center[3], radius;
+    float cone_apex[3], cone_cutoff;
+    float cone_axis[3];
+    int8_t cone_axis_s8[3], cone_cutoff_s8;
+} OrbitMeshletBoundsFull;
+ORBIT_STATIC_ASSERT(sizeof(OrbitMeshletBoundsFull) == 48, "MeshletBoundsFull is 48 B");
+
+#define ORBIT_BOUNDS_KEEP_RECORDS 1u /* flags: compute, write `full` only */
+typedef struct OrbitMeshletBoundsJob { /* HOST block, 96 B; every pointer a DEVICE pointer */
+    void *meshlets;                  /* OrbitMeshlet[meshlet_capacity], global indexing */
+    const uint32_t *meshlet_data;    /* meshlet_data_buffer: vertex indices at data_offset, then the u8 corners */
+    const void *vertices;            /* position i = 3 floats at i * vertex_stride + position_offset */
+    const uint32_t *meshlet_indices; /* NULL: the range [first_meshlet, first_meshlet + meshlet_count);
+                                        else meshlet_count global indices (first_meshlet not used) */
+    OrbitMeshletBoundsFull *full;    /* NULL, or row i = the i-th selected meshlet */
+    uint64_t first_meshlet, meshlet_count, meshlet_capacity, meshlet_data_words, vertex_count;
+    uint32_t vertex_stride, position_offset, flags, _pad;
+} OrbitMeshletBoundsJob;
+ORBIT_STATIC_ASSERT(sizeof(OrbitMeshletBoundsJob) == 96, "MeshletBoundsJob is 96 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitMeshletBoundsJob, first_meshlet) == 40, "first_meshlet @40");
+ORBIT_STATIC_ASSERT(offsetof(OrbitMeshletBoundsJob, vertex_stride) == 80, "vertex_stride @80");
+
+/* sphere, cone axis and cutoff of the selected meshlets from the vertex buffer; see above */
+int32_t orbit_meshlet_bounds(OrbitCtx *ctx, const OrbitMeshletBoundsJob *job, void *stream);
+
+/* orbit_mesh_bounds: per range, assets::compute_mesh_bounds (gltf_loader.rs:480-506) of the vertices              */
+/* [first_vertex, first_vertex + vertex_count): the AABB, then the sphere — the AABB's centre, the radius through   */
+/* the farthest vertex.  Writes bounding_sphere[0..3], aabb_min[0..2] and aabb_max[0..2] of mesh_infos[mesh_index]; */
+/* the two w words and bytes 48..127 stay untouched.  Contract: equal to the host mirror as float VALUES for finite */
+/* positions (+0 and -0 compare equal: fmin / fmax leave a zero's sign open); an empty range gives the host's +inf, */
+/* -inf, a NaN centre and radius 0.  A range reaching beyond vertex_count, or a mesh_index >= mesh_capacity, writes */
+/* nothing for that mesh and latches ORBIT_E_RANGE.  Ranges naming the same mesh are not ordered.  Large ranges are */
+/* cut over several workgroups; the scratch is the context's, so calls on one context are ordered by their stream   */
+/* (use one stream per context for this call).  ORBIT_E_INVALID for NULL ranges, vertices or mesh_infos with a      */
+/* count above 0, a stride below position_offset + 12, a stride or offset no multiple of 4, a pointer not 4-B       */
+/* aligned (mesh_infos: 16 B).  No allocation, no host synchronisation: capturable on its first call.               */
+typedef struct OrbitMeshBoundsRange { /* DEVICE, 12 B */
+    uint32_t mesh_index, first_vertex, vertex_count;
+} OrbitMeshBoundsRange;
+ORBIT_STATIC_ASSERT(sizeof(OrbitMeshBoundsRange) == 12, "MeshBoundsRange is 12 B");
+int32_t orbit_mesh_bounds(OrbitCtx *ctx, const OrbitMeshBoundsRange *ranges, uint32_t range_count,
+                          const void *vertices, uint64_t vertex_count, uint32_t vertex_stride, uint32_t position_offset,
+                          OrbitMeshInfo *mesh_infos, uint32_t mesh_capacity, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,17 @@ class SceneUpdate(C.Structure):  # OrbitSceneUpdate
                 ("shadow_capacity", C.c_uint32), ("luminance_cutoff", C.c_float), ("shadow_index_base", C.c_uint32)]
 
 
+class MeshletBoundsJob(C.Structure):  # OrbitMeshletBoundsJob
+    _fields_ = [("meshlets", C.c_void_p), ("meshlet_data", C.c_void_p), ("vertices", C.c_void_p),
+                ("meshlet_indices", C.c_void_p), ("full", C.c_void_p), ("first_meshlet", C.c_uint64),
+                ("meshlet_count", C.c_uint64), ("meshlet_capacity", C.c_uint64), ("meshlet_data_words", C.c_uint64),
+                ("vertex_count", C.c_uint64), ("vertex_stride", C.c_uint32), ("position_offset", C.c_uint32),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+BOUNDS_KEEP_RECORDS = 1  # ORBIT_BOUNDS_KEEP_RECORDS
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -165,6 +176,9 @@ SYMBOLS = {
                                      C.POINTER(MeshletCullBufs), C.c_void_p, C.c_void_p]),
     "orbit_cluster_stats": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "orbit_meshlet_bounds": (C.c_int32, [C.c_void_p, C.POINTER(MeshletBoundsJob), C.c_void_p]),
+    "orbit_mesh_bounds": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_uint32, C.c_void_p]),
 }
 
 _lib = None

@@ -38,6 +38,31 @@ def compute_mesh_bounds(positions):
     return np.array(mn, np.float32), np.array(mx, np.float32), np.array(sp, np.float32)
 
 
+def meshlet_bounds(meshlets, meshlet_data, vertices, vertex_count, vertex_stride=12, position_offset=0, first=0,
+                   count=None, indices=None):
+    """The host reference of Engine.meshlet_bounds on host copies of the same buffers (orbit_host_meshlet_bounds: the
+    records decoded as the device decodes them, then the mirror's compute_meshlet_bounds) ->
+    (full: np[layouts.MESHLET_BOUNDS_FULL] per selected meshlet, range_error: np.int32 flags, updates: np.uint32 growth
+    updates of the meshlet's two Ritter spheres).  `vertices`: any contiguous array, read as bytes; the records are not
+    written.  A failed range check leaves a zero row."""
+    rec = np.ascontiguousarray(meshlets).view(np.uint8).reshape(-1)
+    data = np.ascontiguousarray(meshlet_data, dtype=np.uint32).reshape(-1)
+    vb = np.ascontiguousarray(vertices).view(np.uint8).reshape(-1)
+    if int(vertex_count) and (int(vertex_count) - 1) * int(vertex_stride) + int(position_offset) + 12 > vb.nbytes:
+        raise ValueError("vertex_count reaches beyond the vertex array")
+    idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    capacity = rec.nbytes // 32
+    if count is None:
+        count = len(idx) if idx is not None else capacity - first
+    full = np.zeros(count, dtype=L.MESHLET_BOUNDS_FULL)
+    err, upd = np.zeros(count, np.int32), np.zeros(count, np.uint32)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(lib().orbit_host_meshlet_bounds(p(rec), C.c_uint64(capacity), p(idx), C.c_uint64(first), C.c_uint64(count),
+                                           p(data), C.c_uint64(len(data)), p(vb), C.c_uint64(vertex_count),
+                                           C.c_uint32(vertex_stride), C.c_uint32(position_offset), p(full), p(err), p(upd)))
+    return full, err, upd
+
+
 def meshlet_triangles(meshlet, meshlet_data):
     """The global vertex indices (n_tri, 3) of one meshlet, decoded the way the mesh / vertex shaders read them:
     vertices at data_offset, u8 corners from byte (data_offset + vertex_count) * 4 — the cmd_first_index of the draw

@@ -1,0 +1,64 @@
+// abi_assets.hip — the C ABI's geometry bounds (include/orbit_abi_ext.h): orbit_meshlet_bounds and orbit_mesh_bounds,
+// the refit of Meshlet and MeshInfo bounds from a vertex buffer on the device (meshlet_bounds.hip).
+#include "abi_internal.h"
+
+namespace {
+
+// the two calls' view of a vertex buffer: 3 floats at i * stride + offset
+int32_t check_vertex_layout(OrbitCtx *ctx, const char *who, uint32_t stride, uint32_t offset) {
+    if ((uint64_t)stride < (uint64_t)offset + 12u || (stride & 3u) || (offset & 3u))
+        return fail(ctx, ORBIT_E_INVALID, "%s: vertex_stride %u, position_offset %u (multiples of 4, stride >= offset + 12)",
+                    who, stride, offset);
+    return ORBIT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+// No allocation, no scratch, no host sync: capturable on the first call.  Everything that depends on the buffers'
+// contents (indices, offsets, counts) is checked on the device and latched (ORBIT_E_RANGE).
+int32_t orbit_meshlet_bounds(OrbitCtx *ctx, const OrbitMeshletBoundsJob *job, void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "meshlet_bounds: job is NULL");
+    const OrbitMeshletBoundsJob &j = *job;
+    if (j.flags & ~ORBIT_BOUNDS_KEEP_RECORDS) return fail(ctx, ORBIT_E_INVALID, "meshlet_bounds: flags %#x", j.flags);
+    if ((j.flags & ORBIT_BOUNDS_KEEP_RECORDS) && !j.full)
+        return fail(ctx, ORBIT_E_INVALID, "meshlet_bounds: KEEP_RECORDS without `full` computes nothing");
+    if (const int32_t rc = check_vertex_layout(ctx, "meshlet_bounds", j.vertex_stride, j.position_offset)) return rc;
+    if ((uintptr_t)j.meshlets & 15u) return fail(ctx, ORBIT_E_INVALID, "meshlet_bounds: meshlets must be 16-B aligned");
+    if (((uintptr_t)j.meshlet_data | (uintptr_t)j.vertices | (uintptr_t)j.meshlet_indices | (uintptr_t)j.full) & 3u)
+        return fail(ctx, ORBIT_E_INVALID, "meshlet_bounds: every buffer must be 4-B aligned");
+    if (j.meshlet_count == 0) return ORBIT_OK;
+    if (!j.meshlets || !j.meshlet_data || !j.vertices) return fail(ctx, ORBIT_E_INVALID, "meshlet_bounds: NULL buffer");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_meshlet_bounds(j, ctx->num_cus, ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch meshlet_bounds");
+    return ORBIT_OK;
+}
+
+// Three launches per batch of ranges on the stream; the slices' partial results go through the context's scratch
+// (kMeshBoundsSlots (range, slice) pairs: few ranges are cut fine, many ranges are not cut).  No allocation, no host sync.
+int32_t orbit_mesh_bounds(OrbitCtx *ctx, const OrbitMeshBoundsRange *ranges, uint32_t range_count, const void *vertices,
+                          uint64_t vertex_count, uint32_t vertex_stride, uint32_t position_offset,
+                          OrbitMeshInfo *mesh_infos, uint32_t mesh_capacity, void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    if (const int32_t rc = check_vertex_layout(ctx, "mesh_bounds", vertex_stride, position_offset)) return rc;
+    if ((((uintptr_t)ranges | (uintptr_t)vertices) & 3u) || ((uintptr_t)mesh_infos & 15u))
+        return fail(ctx, ORBIT_E_INVALID, "mesh_bounds: ranges and vertices must be 4-B aligned, mesh_infos 16-B aligned");
+    if (range_count == 0) return ORBIT_OK;
+    if (!ranges || !vertices || !mesh_infos) return fail(ctx, ORBIT_E_INVALID, "mesh_bounds: NULL buffer");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const uint32_t slices = range_count >= kMeshBoundsSlots ? 1u : kMeshBoundsSlots / range_count > 64u ? 64u : kMeshBoundsSlots / range_count;
+    const uint32_t batch = kMeshBoundsSlots / slices;
+    for (uint32_t first = 0; first < range_count; first += batch) {
+        const uint32_t n = range_count - first < batch ? range_count - first : batch;
+        const hipError_t e = launch_mesh_bounds(ranges + first, n, slices, vertices, vertex_count, vertex_stride,
+                                                position_offset, mesh_infos, mesh_capacity, ctx->b_mesh_slices,
+                                                ctx->status, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "launch mesh_bounds");
+    }
+    return ORBIT_OK;
+}
+
+} // extern "C"

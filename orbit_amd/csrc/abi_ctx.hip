@@ -83,6 +83,7 @@ size_t layout_arena(OrbitCtx *ctx, uintptr_t base, uint64_t md32) {
     ctx->a_coarse_seg = (uint32_t)aseg;
     ctx->a_hit_cache = (uint32_t *)carve(((size_t)caps.max_clusters + kAssignPad) * kHitCache * 4);
     ctx->s_block_sums = (uint32_t *)carve((ent / 256 + 1) * 3 * 4); // last: nothing in front of it moves
+    ctx->b_mesh_slices = (float *)carve((size_t)kMeshBoundsSlots * 8 * 4); // (behind it, for the same reason)
     return off;
 }
 

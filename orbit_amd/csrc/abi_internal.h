@@ -67,6 +67,7 @@ struct OrbitCtx {
     uint32_t *m_tile_masks = nullptr, *m_chunk_sums = nullptr;
     uint32_t *m_tile_counts = nullptr, *m_tile_base = nullptr, *m_total = nullptr;
     uint32_t *s_block_sums = nullptr; // orbit_scene_update: {meshes, lights, shadow casters} per 256 entities
+    float *b_mesh_slices = nullptr;  // orbit_mesh_bounds: 8 floats per range and slice, kMeshBoundsSlots of them
     uint32_t *x_block_pop = nullptr; // orbit_expand_visible_records: survivors per 1024 records of the list
     uint32_t *c_chunk = nullptr; // compact: its own chunk counts | the ones a counting mark launch left (c_chunk_words each)
     size_t c_chunk_words = 0;
@@ -106,6 +107,9 @@ struct OrbitCtx {
 
 // orbit_expand_visible_records: a list of up to kExpandBlocks * 1024 records (64 M) can be expanded
 constexpr uint32_t kExpandBlocks = 65536;
+
+// orbit_mesh_bounds: (range, slice) pairs one batch of launches works on
+constexpr uint32_t kMeshBoundsSlots = 1024;
 
 // ------------------------------------------------------------------- errors (abi_ctx.hip)
 // The last error of the calling thread (orbit_last_error(NULL)); every failure also lands in its context's `err`.

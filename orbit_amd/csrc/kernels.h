@@ -362,6 +362,13 @@ hipError_t launch_scene_update_entities(const OrbitEntityTransform *transforms, 
                                         int32_t *status, hipStream_t s);
 // scene_full.hip: orbit_scene_update — `u` validated by the entry point; block_sums: scratch, 3 words per 256 entities
 hipError_t launch_scene_update(const OrbitSceneUpdate &u, uint32_t *block_sums, int32_t *status, hipStream_t s);
+// meshlet_bounds.hip: orbit_meshlet_bounds — `job` validated by the entry point, meshlet_count > 0
+hipError_t launch_meshlet_bounds(const OrbitMeshletBoundsJob &job, uint32_t num_cus, int32_t *status, hipStream_t s);
+// ... and orbit_mesh_bounds: range_count > 0 ranges, each cut into `slices` workgroups; scratch: 8 floats per range and slice
+hipError_t launch_mesh_bounds(const OrbitMeshBoundsRange *ranges, uint32_t range_count, uint32_t slices,
+                              const void *vertices, uint64_t vertex_count, uint32_t vertex_stride,
+                              uint32_t position_offset, OrbitMeshInfo *mesh_infos, uint32_t mesh_capacity, float *scratch,
+                              int32_t *status, hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

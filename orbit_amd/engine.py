@@ -276,6 +276,45 @@ class Engine:
         u.shadow_index_base = int(shadow_index_base) & 0xFFFFFFFF
         _lib.check(self._lib.orbit_scene_update(self._ctx, C.byref(u), _stream(stream)), self._ctx)
 
+    # -- geometry bounds from the vertex buffer on the device (orbit_meshlet_bounds, orbit_mesh_bounds)
+    def meshlet_bounds(self, meshlets, meshlet_data, vertices, vertex_count, vertex_stride=12, position_offset=0,
+                       first_meshlet=0, meshlet_count=None, meshlet_indices=None, full=None, keep_records=False,
+                       meshlet_capacity=None, meshlet_data_words=None, stream=None):
+        """Bytes 0..19 (sphere, snorm8 cone axis and cutoff) of the selected 32-B records of `meshlets` recomputed from
+        `vertices` (position i = 3 floats at byte i * vertex_stride + position_offset), bit-equal to the host mirror's
+        compute_meshlet_bounds.  The selection is the range [first_meshlet, first_meshlet + meshlet_count) or, if given,
+        the u32 global indices in the device tensor `meshlet_indices` (any dtype: its bytes are read).  full: device
+        tensor of 48-B layouts.MESHLET_BOUNDS_FULL rows, one per selected meshlet; keep_records: write `full` only.
+        The capacities default to what the tensors hold.  Enqueued on `stream`; a meshlet that points out of range is
+        left unwritten and reported by status() (ORBIT_E_RANGE).  A derived stream of these records needs
+        MeshletStream.update of the same range afterwards."""
+        nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
+        j = _lib.MeshletBoundsJob()
+        j.meshlets, j.meshlet_data, j.vertices = _ptr(meshlets), _ptr(meshlet_data), _ptr(vertices)
+        j.meshlet_indices, j.full = _ptr(meshlet_indices), _ptr(full)
+        j.meshlet_capacity = nbytes(meshlets) // 32 if meshlet_capacity is None else int(meshlet_capacity)
+        j.meshlet_data_words = nbytes(meshlet_data) // 4 if meshlet_data_words is None else int(meshlet_data_words)
+        if meshlet_count is None:
+            meshlet_count = nbytes(meshlet_indices) // 4 if meshlet_indices is not None else j.meshlet_capacity - first_meshlet
+        j.first_meshlet, j.meshlet_count, j.vertex_count = int(first_meshlet), int(meshlet_count), int(vertex_count)
+        j.vertex_stride, j.position_offset = int(vertex_stride), int(position_offset)
+        j.flags = _lib.BOUNDS_KEEP_RECORDS if keep_records else 0
+        _lib.check(self._lib.orbit_meshlet_bounds(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
+    def mesh_bounds(self, ranges, vertices, vertex_count, mesh_infos, vertex_stride=12, position_offset=0,
+                    range_count=None, mesh_capacity=None, stream=None):
+        """bounding_sphere, aabb_min.xyz and aabb_max.xyz of mesh_infos[mesh_index] for every {mesh_index, first_vertex,
+        vertex_count} (3 u32) of the device tensor `ranges`, as gltf_loader.rs:480-506 computes them; nothing else of
+        the 128-B MeshInfos is written.  range_count and mesh_capacity default to what the tensors hold.  Enqueued on
+        `stream`; a range beyond vertex_count or a mesh beyond the capacity is reported by status() (ORBIT_E_RANGE).
+        A bound mesh side table needs MeshletStream.update_meshes afterwards."""
+        nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
+        range_count = nbytes(ranges) // 12 if range_count is None else int(range_count)
+        mesh_capacity = nbytes(mesh_infos) // 128 if mesh_capacity is None else int(mesh_capacity)
+        _lib.check(self._lib.orbit_mesh_bounds(self._ctx, _ptr(ranges), range_count, _ptr(vertices), int(vertex_count),
+                                               int(vertex_stride), int(position_offset), _ptr(mesh_infos),
+                                               mesh_capacity, _stream(stream)), self._ctx)
+
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                    entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,

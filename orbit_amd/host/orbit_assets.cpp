@@ -31,6 +31,8 @@ namespace assets {
 
 namespace {
 
+thread_local uint64_t g_sphere_updates = 0; // sphere_growth_updates()
+
 // meshoptimizer computeBoundingSphere: Ritter's sphere seeded with the most distant pair among the six axis extremes.
 void compute_bounding_sphere(float result[4], const float (*points)[3], size_t count) {
     size_t pmin[3] = {0, 0, 0}, pmax[3] = {0, 0, 0};
@@ -64,6 +66,7 @@ void compute_bounding_sphere(float result[4], const float (*points)[3], size_t c
             center[1] = center[1] * k + p[1] * (1 - k);
             center[2] = center[2] * k + p[2] * (1 - k);
             radius = (radius + d) / 2;
+            g_sphere_updates++;
         }
     }
     result[0] = center[0], result[1] = center[1], result[2] = center[2], result[3] = radius;
@@ -78,6 +81,8 @@ int quantize_snorm8(float v) { // meshopt_quantizeSnorm(v, 8)
 }
 
 } // namespace
+
+uint64_t sphere_growth_updates() { return g_sphere_updates; }
 
 std::vector<RawMeshlet> build_meshlets(const uint32_t *indices, size_t index_count, size_t vertex_count,
                                        size_t max_vertices, size_t max_triangles) {

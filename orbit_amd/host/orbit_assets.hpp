@@ -47,6 +47,10 @@ std::vector<RawMeshlet> build_meshlets(const uint32_t *indices, size_t index_cou
                                        size_t max_vertices = MAX_MESHLET_VERTICES,
                                        size_t max_triangles = MAX_MESHLET_TRIANGLES);
 MeshletBounds compute_meshlet_bounds(const RawMeshlet &meshlet, const float *positions);
+// growth updates (points that enlarged a sphere) of every bounding sphere the calling thread has computed so far: a
+// meshlet's two spheres are counted by the difference around compute_meshlet_bounds (the tests' census of the order-
+// dependent part)
+uint64_t sphere_growth_updates();
 
 // assets::mesh::compute_meshlets (mesh.rs:292-338): appends to meshlet_data (vertex indices, then the u8 triangle
 // corners padded to a whole u32) and to meshlets.

@@ -498,6 +498,60 @@ void orbit_host_compute_mesh_bounds(const float *positions, uint64_t vertex_coun
     assets::compute_mesh_bounds(positions, (size_t)vertex_count, aabb_min, aabb_max, bounding_sphere);
 }
 
+int32_t orbit_host_meshlet_bounds(const OrbitMeshlet *meshlets, uint64_t meshlet_capacity, const uint32_t *indices,
+                                  uint64_t first, uint64_t count, const uint32_t *meshlet_data, uint64_t meshlet_data_words,
+                                  const void *vertices, uint64_t vertex_count, uint32_t vertex_stride,
+                                  uint32_t position_offset, OrbitMeshletBoundsFull *out, int32_t *range_error,
+                                  uint32_t *updates) {
+    return guarded([&] {
+        if (!out || (count && (!meshlets || !meshlet_data || !vertices))) throw Panic("meshlet_bounds: NULL argument");
+        if ((uint64_t)vertex_stride < (uint64_t)position_offset + 12u) throw Panic("meshlet_bounds: vertex_stride");
+        assets::RawMeshlet raw;
+        std::vector<float> positions; // of the meshlet's own vertices: `raw` indexes it with 0, 1, 2, ...
+        for (uint64_t i = 0; i < count; i++) {
+            std::memset(&out[i], 0, sizeof(out[i]));
+            if (range_error) range_error[i] = 1;
+            if (updates) updates[i] = 0u;
+            const uint64_t m = indices ? (uint64_t)indices[i] : first + i;
+            if (m >= meshlet_capacity) continue;
+            const OrbitMeshlet &rec = meshlets[m];
+            const uint64_t nv = rec.vertex_count, nt = rec.triangle_count, data_offset = rec.data_offset;
+            if (data_offset + nv + (3 * nt + 3) / 4 > meshlet_data_words) continue;
+            raw.vertices.resize(nv);
+            positions.resize(3 * nv);
+            bool ok = true;
+            for (uint64_t v = 0; v < nv && ok; v++) {
+                const uint64_t g = (uint64_t)rec.vertex_offset + meshlet_data[data_offset + v];
+                ok = g < vertex_count;
+                if (ok) std::memcpy(&positions[3 * v], (const uint8_t *)vertices + g * vertex_stride + position_offset, 12);
+                raw.vertices[v] = (uint32_t)v;
+            }
+            const uint8_t *corners = reinterpret_cast<const uint8_t *>(meshlet_data + data_offset + nv);
+            raw.triangles.assign(corners, corners + (ok ? 3 * nt : 0));
+            for (uint8_t c : raw.triangles) ok = ok && c < nv;
+            if (!ok) continue;
+            const uint64_t before = assets::sphere_growth_updates();
+            const assets::MeshletBounds b = assets::compute_meshlet_bounds(raw, positions.data());
+            if (updates) updates[i] = (uint32_t)(assets::sphere_growth_updates() - before);
+            std::memcpy(out[i].center, b.center, 12);
+            out[i].radius = b.radius;
+            std::memcpy(out[i].cone_apex, b.cone_apex, 12);
+            out[i].cone_cutoff = b.cone_cutoff;
+            std::memcpy(out[i].cone_axis, b.cone_axis, 12);
+            std::memcpy(out[i].cone_axis_s8, b.cone_axis_s8, 3);
+            out[i].cone_cutoff_s8 = b.cone_cutoff_s8;
+            // a NaN leaves as the canonical quiet NaN, as on the device: an x86-64 NaN's sign and payload depend on the
+            // operand order the compiler chose, not on the algorithm (the s8 fields never see them)
+            uint32_t words[11];
+            std::memcpy(words, &out[i], sizeof(words));
+            for (uint32_t &w : words)
+                if ((w & 0x7FFFFFFFu) > 0x7F800000u) w = 0x7FC00000u;
+            std::memcpy(&out[i], words, sizeof(words));
+            if (range_error) range_error[i] = 0;
+        }
+    });
+}
+
 // ---------------------------------------------------------------- asset ingestion (orbit_gltf.hpp), host only
 void *orbit_host_gltf_load(const char *path) {
     gltf_loader::LoadedScene *scene = nullptr;

@@ -206,6 +206,19 @@ int32_t orbit_host_compute_meshlets(const float *positions, uint64_t vertex_coun
 void orbit_host_compute_mesh_bounds(const float *positions, uint64_t vertex_count, float aabb_min[3], float aabb_max[3],
                                     float bounding_sphere[4]);
 
+/* the reference of orbit_meshlet_bounds, on HOST copies of the same buffers: decodes each selected record as the device
+ * does (global vertex = vertex_offset + meshlet_data[data_offset + local], in 64 bits; u8 corners from byte
+ * (data_offset + vertex_count) * 4), applies the device's four range checks and calls compute_meshlet_bounds.
+ * indices == NULL: the range [first, first + count).  out[i] = the i-th selected meshlet's bounds, all zero where a
+ * range check failed; the records are not written.  A NaN float is returned as 0x7FC00000, as the device writes it.
+ *  range_error (may be NULL): count flags, 1 where a check failed.
+ * updates (may be NULL): count words, the growth updates of the meshlet's two Ritter spheres (corners + normals). */
+int32_t orbit_host_meshlet_bounds(const OrbitMeshlet *meshlets, uint64_t meshlet_capacity, const uint32_t *indices,
+                                  uint64_t first, uint64_t count, const uint32_t *meshlet_data, uint64_t meshlet_data_words,
+                                  const void *vertices, uint64_t vertex_count, uint32_t vertex_stride,
+                                  uint32_t position_offset, OrbitMeshletBoundsFull *out, int32_t *range_error,
+                                  uint32_t *updates);
+
 /* ---- asset ingestion (orbit_gltf.hpp): glTF 2.0 (.glb / .gltf) -> materials, meshes with their LOD chains, entities ----
  * load_gltf (gltf_loader.rs:511-676) + GpuAssets::add_mesh (assets/mod.rs:325-476).  NULL + orbit_host_last_error()
  * on failure.  The arrays stay valid until orbit_host_gltf_free. */

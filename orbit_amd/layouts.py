@@ -48,6 +48,13 @@ MESHLET = np.dtype([
     ("vertex_offset", "<u4"), ("data_offset", "<u4"), ("material_index", "<u2"),
     ("vertex_count", "u1"), ("triangle_count", "u1"),
 ])
+# OrbitMeshletBoundsFull (include/orbit_abi_ext.h): meshopt::Bounds as orbit_meshlet_bounds writes it
+MESHLET_BOUNDS_FULL = np.dtype([
+    ("center", "<f4", (3,)), ("radius", "<f4"), ("cone_apex", "<f4", (3,)), ("cone_cutoff", "<f4"),
+    ("cone_axis", "<f4", (3,)), ("cone_axis_s8", "i1", (3,)), ("cone_cutoff_s8", "i1"),
+])
+# OrbitMeshBoundsRange: one mesh's vertices for orbit_mesh_bounds
+MESH_BOUNDS_RANGE = np.dtype([("mesh_index", "<u4"), ("first_vertex", "<u4"), ("vertex_count", "<u4")])
 # types.glsl:92-110, src/assets/mod.rs:171-191
 MATERIAL = np.dtype([
     ("base_color", "<f4", (4,)), ("emissive_factor", "<f4", (3,)), ("metallic_factor", "<f4"),
