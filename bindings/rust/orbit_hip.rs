@@ -108,6 +108,28 @@ pub struct OrbitMeshletBoundsJob {
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct OrbitMeshBoundsRange { pub mesh_index: u32, pub first_vertex: u32, pub vertex_count: u32 }
 
+/// The counters of orbit_raster_depth (32 B, DEVICE)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitRasterStats {
+    pub commands: u32, pub triangles: u32, pub clip_skipped: u32, pub guard_skipped: u32, pub back_facing: u32,
+    pub no_coverage: u32, pub fragments: u32, pub range_errors: u32,
+}
+
+pub const ORBIT_RASTER_CLEAR: u32 = 1;
+pub const ORBIT_RASTER_CULL_NONE: u32 = 2;
+pub const ORBIT_RASTER_MAX_DIM: u32 = 32768;
+
+/// orbit_raster_depth's argument block (160 B, HOST): DEVICE pointers; stats may be null
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitRasterDepth {
+    pub draw_commands: *const c_void, pub meshlet_data: *const u32, pub vertices: *const c_void,
+    pub entity_data: *const c_void, pub depth: *mut f32, pub stats: *mut OrbitRasterStats,
+    pub meshlet_data_words: u64, pub vertex_count: u64,
+    pub max_commands: u32, pub entity_count: u32, pub vertex_stride: u32, pub position_offset: u32,
+    pub width: u32, pub height: u32, pub flags: u32, pub _pad: u32,
+    pub view_proj: [f32; 16],
+}
+
 /// push-constant order of shaders/entity_cull.comp:17-23 (== draw_gen.rs:372-376)
 #[repr(C)]
 pub struct OrbitEntityCullBufs {
@@ -291,6 +313,11 @@ extern "C" {
     pub fn orbit_mesh_bounds(ctx: *mut OrbitCtx, ranges: *const OrbitMeshBoundsRange, range_count: u32,
                              vertices: *const c_void, vertex_count: u64, vertex_stride: u32, position_offset: u32,
                              mesh_infos: *mut c_void, mesh_capacity: u32, stream: *mut c_void) -> i32;
+    /// The depth prepass (forward.rs:300-356) in compute: rasterises the MeshletDrawCommandBuffer the meshlet cull wrote
+    /// (count read on the device) into width * height reversed-z floats by atomic max; ORBIT_RASTER_CLEAR clears first.
+    /// Byte-equal to the host mirror.  Near-plane clipping is out of scope: a triangle with a vertex outside w > 0,
+    /// 0 <= z <= w is not drawn.  Cull occluders with alpha_mode_flag = OPAQUE: masked materials are not alpha-tested.
+    pub fn orbit_raster_depth(ctx: *mut OrbitCtx, job: *const OrbitRasterDepth, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

@@ -829,6 +829,114 @@ int32_t orbit_mesh_bounds(OrbitCtx *ctx, const OrbitMeshBoundsRange *ranges, uin
                           const void *vertices, uint64_t vertex_count, uint32_t vertex_stride, uint32_t position_offset,
                           OrbitMeshInfo *mesh_infos, uint32_t mesh_capacity, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* Depth prepass on the device.  What turns the early cull's                */
+/* MeshletDrawCommandBuffer into the depth buffer that orbit_depth_reduce   */
+/* and the late cull read is the reference's depth prepass                  */
+/* (forward_depth_prepass.mesh / .vert plus fixed-function raster,          */
+/* forward.rs:300-356).  An Instinct part has no rasteriser:                */
+/* orbit_raster_depth is that pass in compute.  It consumes the draw        */
+/* commands exactly as orbit_meshlet_cull wrote them ({u32 count;           */
+/* OrbitMeshletDrawCommand[]}; the count is read ON THE DEVICE and clamped  */
+/* by max_commands, never read back) and writes reversed-z depth (clear     */
+/* 0.0, compare GREATER) into width * height floats, row pitch = width.     */
+/*                                                                          */
+/* ONE definition, shared by the device and the host mirror                 */
+/* (orbit_host_raster_depth); the two agree on every byte of `depth` and of */
+/* `stats`.  All arithmetic is fp32, round-to-nearest, never contracted,    */
+/* IEEE divides.                                                            */
+/*  R1 decode (forward_depth_prepass.vert / .mesh:44-59): nt =              */
+/*     cmd_index_count / 3; vcount = cmd_first_index / 4 - cmd_vertex_offset*/
+/*     (cmd_vertex_offset taken as its u32 bits); corner bytes start at     */
+/*     byte cmd_first_index of meshlet_data; global vertex =                */
+/*     meshlet_vertex_offset + meshlet_data[cmd_vertex_offset + corner], in */
+/*     64 bits; entity = cmd_first_instance.  cmd_instance_count and        */
+/*     meshlet_index are not read.                                          */
+/*  R2 mvp = view_proj x model (OpMatrixTimesMatrix), clip = mvp x (p, 1)   */
+/*     (OpMatrixTimesVector): left-to-right rounded sums.                   */
+/*  R3 per vertex w > 0 && z >= 0 && z <= w (false for NaN).  A triangle    */
+/*     with a failing vertex is NOT DRAWN (clip_skipped).  NEAR-PLANE       */
+/*     CLIPPING IS OUT OF SCOPE: skipping only leaves the depth farther,    */
+/*     the safe side for occlusion.                                         */
+/*  R4 ndc = clip.xyz / w; xs = (ndc.x * 0.5 + 0.5) * W; ys = (ndc.y * -0.5 */
+/*     + 0.5) * H (negative viewport height, commands.rs:303-313; the       */
+/*     cull's uv, entity_cull.comp:99-101); X = rint(xs * 256), Y =         */
+/*     rint(ys * 256), ties to even.  A triangle with a vertex whose        */
+/*     |xs * 256| or |ys * 256| is not below 2^23 is not drawn              */
+/*     (guard_skipped).                                                     */
+/*  R5 A = (X1-X0)(Y2-Y0) - (X2-X0)(Y1-Y0) in int64.  A == 0: no_coverage.  */
+/*     Front <=> A < 0 (cull BACK, front COUNTER_CLOCKWISE,                 */
+/*     pipeline.rs:201-202); back faces are dropped (back_facing) unless    */
+/*     ORBIT_RASTER_CULL_NONE.  The survivor is normalised to A > 0 by      */
+/*     swapping vertices 1 and 2.                                           */
+/*  R6 sample = pixel centre (256 x + 128, 256 y + 128); pixels = the       */
+/*     centres inside the snapped bounding box, clamped to the target;      */
+/*     E(a, b, p) = (bx-ax)(py-ay) - (by-ay)(px-ax) in int64; inside iff    */
+/*     for all three edges E > 0, or E == 0 and the edge is top-left        */
+/*     (dy < 0 || (dy == 0 && dx > 0)).  No inside sample: no_coverage.     */
+/*  R7 d_i = z_i / w_i; A_f = (float)(double)A;                             */
+/*     gx = ((d1-d0) * (float)(Y2-Y0) - (d2-d0) * (float)(Y1-Y0)) / A_f;    */
+/*     gy = ((d2-d0) * (float)(X1-X0) - (d1-d0) * (float)(X2-X0)) / A_f;    */
+/*     d = (d0 + gx * (float)(px-X0)) + gy * (float)(py-Y0); d = min(d, 1); */
+/*     a sample with !(d > 0) writes nothing.  fragments = inside samples   */
+/*     with d > 0.                                                          */
+/*  R8 depth[y * W + x] = max(old, d) on the u32 view (atomicMax): the      */
+/*     buffer is independent of scheduling and of command order; no counter */
+/*     depends on order.                                                    */
+/*  R9 range checks on the device, before anything is read: a command whose */
+/*     index words or corner bytes reach beyond meshlet_data_words, with    */
+/*     cmd_first_index / 4 < cmd_vertex_offset, vcount > 255, a corner >=   */
+/*     vcount, a vertex >= vertex_count or an entity >= entity_count is     */
+/*     skipped whole (range_errors) and ORBIT_E_RANGE is latched            */
+/*     (orbit_ctx_status); the other commands are still drawn.              */
+/* stats (may be NULL) is cleared by the call on the stream, then counts:   */
+/* commands = min(count, max_commands); triangles = the nt of the commands  */
+/* that passed R9 = clip_skipped + guard_skipped + no_coverage +            */
+/* back_facing + drawn (tested in that order: R3, R4, A == 0, facing, R6).  */
+/*                                                                          */
+/* ORBIT_RASTER_CLEAR is LoadOp::Clear(0.0): the call clears `depth` on the */
+/* stream first; without it the call is LoadOp::Load, the late pass, and    */
+/* `depth` must hold what an earlier call left (floats in [0, 1]).          */
+/* Masked materials cannot be alpha-tested here (no textures): an OCCLUDER  */
+/* depth should come from a cull with alpha_mode_flag = ORBIT_ALPHA_OPAQUE. */
+/*   ORBIT_E_INVALID  job, draw_commands, meshlet_data, vertices,           */
+/*                    entity_data or depth NULL; a pointer not 4-B aligned  */
+/*                    (entity_data: 16 B); vertex_stride < position_offset  */
+/*                    + 12, stride or offset no multiple of 4; width or     */
+/*                    height 0 or above ORBIT_RASTER_MAX_DIM (the target    */
+/*                    must lie inside the guard band of R4); unknown flags  */
+/* A count of 0 is ORBIT_OK (with CLEAR it still clears).  The call         */
+/* allocates nothing, uses no scratch and never synchronises the host: a    */
+/* graph can capture it on its first call.  caps.arith_profile and          */
+/* dispatch_size do not apply.                                              */
+/* ------------------------------------------------------------------------ */
+typedef struct OrbitRasterStats { /* DEVICE, 32 B */
+    uint32_t commands, triangles, clip_skipped, guard_skipped, back_facing, no_coverage, fragments, range_errors;
+} OrbitRasterStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitRasterStats) == 32, "RasterStats is 32 B");
+
+#define ORBIT_RASTER_CLEAR 1u     /* flags: LoadOp::Clear(0.0) instead of LoadOp::Load */
+#define ORBIT_RASTER_CULL_NONE 2u /* flags: draw back faces too */
+#define ORBIT_RASTER_MAX_DIM 32768u
+typedef struct OrbitRasterDepth { /* HOST block, 160 B; every pointer a DEVICE pointer */
+    const void *draw_commands;          /* {u32 count; OrbitMeshletDrawCommand[max_commands]} */
+    const uint32_t *meshlet_data;       /* meshlet_data_buffer */
+    const void *vertices;               /* position i = 3 floats at i * vertex_stride + position_offset */
+    const OrbitEntityData *entity_data; /* entity_count rows */
+    float *depth;                       /* width * height floats */
+    OrbitRasterStats *stats;            /* NULL, or the counters */
+    uint64_t meshlet_data_words, vertex_count;
+    uint32_t max_commands, entity_count, vertex_stride, position_offset, width, height, flags, _pad;
+    float view_proj[16];                /* column-major (forward_depth_prepass.mesh:14) */
+} OrbitRasterDepth;
+ORBIT_STATIC_ASSERT(sizeof(OrbitRasterDepth) == 160, "RasterDepth is 160 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitRasterDepth, meshlet_data_words) == 48, "meshlet_data_words @48");
+ORBIT_STATIC_ASSERT(offsetof(OrbitRasterDepth, max_commands) == 64, "max_commands @64");
+ORBIT_STATIC_ASSERT(offsetof(OrbitRasterDepth, view_proj) == 96, "view_proj @96");
+
+/* the depth prepass of the draw commands in compute; see above */
+int32_t orbit_raster_depth(OrbitCtx *ctx, const OrbitRasterDepth *job, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,19 @@ class MeshletBoundsJob(C.Structure):  # OrbitMeshletBoundsJob
 BOUNDS_KEEP_RECORDS = 1  # ORBIT_BOUNDS_KEEP_RECORDS
 
 
+class RasterDepth(C.Structure):  # OrbitRasterDepth
+    _fields_ = [("draw_commands", C.c_void_p), ("meshlet_data", C.c_void_p), ("vertices", C.c_void_p),
+                ("entity_data", C.c_void_p), ("depth", C.c_void_p), ("stats", C.c_void_p),
+                ("meshlet_data_words", C.c_uint64), ("vertex_count", C.c_uint64), ("max_commands", C.c_uint32),
+                ("entity_count", C.c_uint32), ("vertex_stride", C.c_uint32), ("position_offset", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32),
+                ("view_proj", C.c_float * 16)]
+
+
+RASTER_CLEAR, RASTER_CULL_NONE = 1, 2  # ORBIT_RASTER_CLEAR, ORBIT_RASTER_CULL_NONE
+RASTER_MAX_DIM = 32768                 # ORBIT_RASTER_MAX_DIM
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -179,6 +192,7 @@ SYMBOLS = {
     "orbit_meshlet_bounds": (C.c_int32, [C.c_void_p, C.POINTER(MeshletBoundsJob), C.c_void_p]),
     "orbit_mesh_bounds": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                       C.c_void_p, C.c_uint32, C.c_void_p]),
+    "orbit_raster_depth": (C.c_int32, [C.c_void_p, C.POINTER(RasterDepth), C.c_void_p]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
-// abi_assets.hip — the C ABI's geometry bounds (include/orbit_abi_ext.h): orbit_meshlet_bounds and orbit_mesh_bounds,
-// the refit of Meshlet and MeshInfo bounds from a vertex buffer on the device (meshlet_bounds.hip).
+// abi_assets.hip — the C ABI's calls that read the vertex buffer (include/orbit_abi_ext.h): orbit_meshlet_bounds and
+// orbit_mesh_bounds, the refit of Meshlet and MeshInfo bounds on the device (meshlet_bounds.hip), and orbit_raster_depth,
+// the depth prepass of the draw commands in compute (raster_depth.hip).
 #include "abi_internal.h"
 
 namespace {
@@ -58,6 +59,28 @@ int32_t orbit_mesh_bounds(OrbitCtx *ctx, const OrbitMeshBoundsRange *ranges, uin
                                                 ctx->status, (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch mesh_bounds");
     }
+    return ORBIT_OK;
+}
+
+// A clearing launch (CLEAR, stats) and the raster launch on the stream; the command count stays on the device.  No allocation, no scratch, no
+// host sync: capturable on the first call.
+int32_t orbit_raster_depth(OrbitCtx *ctx, const OrbitRasterDepth *job, void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "raster_depth: job is NULL");
+    const OrbitRasterDepth &j = *job;
+    if (j.flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE))
+        return fail(ctx, ORBIT_E_INVALID, "raster_depth: flags %#x", j.flags);
+    if (const int32_t rc = check_vertex_layout(ctx, "raster_depth", j.vertex_stride, j.position_offset)) return rc;
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "raster_depth: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if (!j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data || !j.depth)
+        return fail(ctx, ORBIT_E_INVALID, "raster_depth: NULL buffer");
+    if ((((uintptr_t)j.draw_commands | (uintptr_t)j.meshlet_data | (uintptr_t)j.vertices | (uintptr_t)j.depth |
+          (uintptr_t)j.stats) & 3u) || ((uintptr_t)j.entity_data & 15u))
+        return fail(ctx, ORBIT_E_INVALID, "raster_depth: every buffer must be 4-B aligned, entity_data 16-B aligned");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_raster_depth(j, ctx->raster_blocks, ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_depth");
     return ORBIT_OK;
 }
 

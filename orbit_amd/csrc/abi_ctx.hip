@@ -148,6 +148,7 @@ int32_t orbit_ctx_create(int32_t device_id, const OrbitCaps *caps_in, OrbitCtx *
     if (!ctx) return fail(nullptr, ORBIT_E_HIP, "out of host memory");
     ctx->device = device_id;
     ctx->num_cus = (uint32_t)prop.multiProcessorCount;
+    ctx->raster_blocks = ctx->num_cus * raster_depth_blocks_per_cu();
     ctx->caps = caps;
     ctx->rec_shift = rec_shift;
 
@@ -231,7 +232,8 @@ int32_t orbit_ctx_status(OrbitCtx *ctx, void *stream, int32_t sync) {
         if (e != hipSuccess) return hip_fail(ctx, e, "hipMemset(status)");
         return fail(ctx, v, v == ORBIT_E_CAPACITY ? "an append overflowed a caller buffer (entries dropped)"
                             : v == ORBIT_E_RANGE  ? "a meshlet outside the bound meshlet stream was culled or expanded, "
-                                                    "or a scene update named an instance index past entity_capacity"
+                                                    "or a scene update named an instance index past entity_capacity, "
+                                                    "or a raster call was handed a draw command that points out of range"
                             : v == ORBIT_E_STALE  ? "the bound meshlet stream no longer mirrors its meshlet buffer (update missing)"
                                                   : "device-latched error %d", v);
     }

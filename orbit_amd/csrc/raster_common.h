@@ -1,0 +1,111 @@
+// raster_common.h — the arithmetic of orbit_raster_depth (include/orbit_abi_ext.h R2-R7), written once
+// for the device kernel (raster_depth.hip) and the host mirror (orbit_amd/host/orbit_raster.cpp): the vertex transform
+// and snap, the triangle setup with its rejects, the edge functions and the depth plane.  Both translation units are
+// built with -ffp-contract=off and correctly rounded divides; every product and sum below is rounded on its own, in
+// the order written.  What the two sides do NOT share is how they walk the pixels: the host evaluates every edge
+// function at every sample of the box directly, the device steps them — equal integers either way.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#ifdef __HIP__
+#define ORBIT_RASTER_FN __host__ __device__ inline __attribute__((always_inline))
+#else
+#define ORBIT_RASTER_FN inline
+#endif
+
+namespace orbit {
+namespace raster {
+
+constexpr uint32_t kClipFail = 1u, kGuardFail = 2u; // Vertex::flags
+
+struct Vertex { // R3, R4: one transformed vertex
+    int32_t X, Y;   // 8 sub-pixel bits; 0 when the guard failed
+    float d;        // z / w
+    uint32_t flags; // kClipFail | kGuardFail
+};
+
+// R2: out = a x b, column by column (OpMatrixTimesMatrix: mat4_mul_col of orbit_device.h, canonical profile)
+ORBIT_RASTER_FN void mat4_mul(const float *a, const float *b, float *out) {
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 4; r++)
+            out[4 * c + r] = ((a[r] * b[4 * c] + a[4 + r] * b[4 * c + 1]) + a[8 + r] * b[4 * c + 2]) + a[12 + r] * b[4 * c + 3];
+}
+
+// R2-R4 of one position
+ORBIT_RASTER_FN Vertex transform_vertex(const float *mvp, float px, float py, float pz, float w_f, float h_f) {
+    float clip[4];
+    for (int r = 0; r < 4; r++) clip[r] = ((mvp[r] * px + mvp[4 + r] * py) + mvp[8 + r] * pz) + mvp[12 + r] * 1.0f;
+    const float x = clip[0], y = clip[1], z = clip[2], w = clip[3];
+    Vertex v;
+    v.flags = (w > 0.0f && z >= 0.0f && z <= w) ? 0u : kClipFail;
+    const float nx = x / w, ny = y / w;
+    v.d = z / w;
+    const float xs = (nx * 0.5f + 0.5f) * w_f, ys = (ny * -0.5f + 0.5f) * h_f;
+    const float xf = xs * 256.0f, yf = ys * 256.0f;
+    const bool in_guard = fabsf(xf) < 8388608.0f && fabsf(yf) < 8388608.0f; // false for NaN
+    if (!in_guard) v.flags |= kGuardFail;
+    v.X = in_guard ? (int32_t)rintf(xf) : 0;
+    v.Y = in_guard ? (int32_t)rintf(yf) : 0;
+    return v;
+}
+
+enum Outcome : uint32_t { kDraw = 0, kClipSkipped = 1, kGuardSkipped = 2, kBackFacing = 3, kNoCoverage = 4 };
+
+struct Setup { // R5-R7: a triangle that may cover samples, orientation normalised to A > 0
+    int32_t ax[3], ay[3], dx[3], dy[3]; // edge k runs from (ax, ay) by (dx, dy): v0->v1, v1->v2, v2->v0
+    int32_t nb[3];                      // 0 for a top-left edge, else 1: inside <=> E - nb >= 0 on all three
+    int32_t x_lo, x_hi, y_lo, y_hi;     // pixels whose centre lies in the snapped box, clamped to the target
+    float d0, gx, gy;
+};
+
+ORBIT_RASTER_FN int32_t imin(int32_t a, int32_t b) { return a < b ? a : b; }
+ORBIT_RASTER_FN int32_t imax(int32_t a, int32_t b) { return a > b ? a : b; }
+
+ORBIT_RASTER_FN uint32_t setup_triangle(const Vertex &v0, Vertex v1, Vertex v2, uint32_t width, uint32_t height,
+                                        bool cull_none, Setup &s) {
+    const uint32_t flags = v0.flags | v1.flags | v2.flags;
+    if (flags & kClipFail) return kClipSkipped;
+    if (flags & kGuardFail) return kGuardSkipped;
+    int64_t area = (int64_t)(v1.X - v0.X) * (int64_t)(v2.Y - v0.Y) - (int64_t)(v2.X - v0.X) * (int64_t)(v1.Y - v0.Y);
+    if (area == 0) return kNoCoverage;
+    if (area > 0 && !cull_none) return kBackFacing; // front <=> A < 0
+    if (area < 0) {
+        const Vertex t = v1;
+        v1 = v2, v2 = t;
+        area = -area;
+    }
+    const int32_t min_x = imin(v0.X, imin(v1.X, v2.X)), max_x = imax(v0.X, imax(v1.X, v2.X));
+    const int32_t min_y = imin(v0.Y, imin(v1.Y, v2.Y)), max_y = imax(v0.Y, imax(v1.Y, v2.Y));
+    // centre 256 x + 128 in [min, max]  <=>  x in [ceil((min - 128) / 256), floor((max - 128) / 256)] (>> floors)
+    s.x_lo = imax((min_x - 128 + 255) >> 8, 0), s.x_hi = imin((max_x - 128) >> 8, (int32_t)width - 1);
+    s.y_lo = imax((min_y - 128 + 255) >> 8, 0), s.y_hi = imin((max_y - 128) >> 8, (int32_t)height - 1);
+    if (s.x_lo > s.x_hi || s.y_lo > s.y_hi) return kNoCoverage;
+    s.ax[0] = v0.X, s.ax[1] = v1.X, s.ax[2] = v2.X;
+    s.ay[0] = v0.Y, s.ay[1] = v1.Y, s.ay[2] = v2.Y;
+    for (int k = 0; k < 3; k++) {
+        const int n = k == 2 ? 0 : k + 1;
+        s.dx[k] = s.ax[n] - s.ax[k], s.dy[k] = s.ay[n] - s.ay[k];
+        s.nb[k] = (s.dy[k] < 0 || (s.dy[k] == 0 && s.dx[k] > 0)) ? 0 : 1;
+    }
+    const float area_f = (float)(double)area;
+    const float d10 = v1.d - v0.d, d20 = v2.d - v0.d;
+    s.d0 = v0.d;
+    s.gx = (d10 * (float)(v2.Y - v0.Y) - d20 * (float)(v1.Y - v0.Y)) / area_f;
+    s.gy = (d20 * (float)(v1.X - v0.X) - d10 * (float)(v2.X - v0.X)) / area_f;
+    return kDraw;
+}
+
+// R6: edge k at the sample (px, py), less its top-left bias: the sample is inside iff all three are >= 0
+ORBIT_RASTER_FN int64_t edge_at(const Setup &s, int k, int32_t px, int32_t py) {
+    return (int64_t)s.dx[k] * (int64_t)(py - s.ay[k]) - (int64_t)s.dy[k] * (int64_t)(px - s.ax[k]) - (int64_t)s.nb[k];
+}
+
+// R7 at the sample (px, py); the caller writes it iff the result is > 0
+ORBIT_RASTER_FN float depth_at(const Setup &s, int32_t px, int32_t py) {
+    const float d = (s.d0 + s.gx * (float)(px - s.ax[0])) + s.gy * (float)(py - s.ay[0]);
+    return 1.0f < d ? 1.0f : d; // GLSL min(d, 1): a NaN stays a NaN
+}
+
+} // namespace raster
+} // namespace orbit

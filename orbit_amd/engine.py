@@ -315,6 +315,28 @@ class Engine:
                                                int(vertex_stride), int(position_offset), _ptr(mesh_infos),
                                                mesh_capacity, _stream(stream)), self._ctx)
 
+    # -- the depth prepass of a draw-command buffer in compute (orbit_raster_depth)
+    def raster_depth(self, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, entity_count,
+                     view_proj, depth, width, height, clear=False, cull_none=False, stats=None, vertex_stride=12,
+                     position_offset=0, meshlet_data_words=None, stream=None):
+        """Rasterises the {u32 count; 28-B commands} of the device tensor `draw_commands` (what meshlet_cull wrote; the
+        count is read on the device and clamped by max_commands) into the width x height float tensor `depth`:
+        reversed z, max-merged by atomicMax into what it holds, or into zeros with clear=True (LoadOp::Clear(0.0)).
+        `view_proj`: 16 floats, column-major; `vertices`: position i = 3 floats at i * vertex_stride + position_offset;
+        `entity_data`: 128-B rows.  `stats`: device tensor of 32 bytes (layouts.RASTER_STATS), cleared by the call.
+        Back faces are culled unless cull_none.  Byte-equal to orbit_amd.raster.host_raster_depth on host copies.
+        Enqueued on `stream`; a command that points out of range is skipped and reported by status() (ORBIT_E_RANGE)."""
+        nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
+        j = _lib.RasterDepth()
+        j.draw_commands, j.meshlet_data, j.vertices = _ptr(draw_commands), _ptr(meshlet_data), _ptr(vertices)
+        j.entity_data, j.depth, j.stats = _ptr(entity_data), _ptr(depth), _ptr(stats)
+        j.meshlet_data_words = nbytes(meshlet_data) // 4 if meshlet_data_words is None else int(meshlet_data_words)
+        j.vertex_count, j.max_commands, j.entity_count = int(vertex_count), int(max_commands), int(entity_count)
+        j.vertex_stride, j.position_offset, j.width, j.height = int(vertex_stride), int(position_offset), int(width), int(height)
+        j.flags = (_lib.RASTER_CLEAR if clear else 0) | (_lib.RASTER_CULL_NONE if cull_none else 0)
+        j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
+        _lib.check(self._lib.orbit_raster_depth(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                    entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,

@@ -9,6 +9,7 @@
 #include "orbit_host.hpp"
 #include "orbit_assets.hpp"
 #include "orbit_gltf.hpp"
+#include "orbit_raster.hpp"
 #include "orbit_scene.hpp"
 
 using namespace orbit;
@@ -549,6 +550,23 @@ int32_t orbit_host_meshlet_bounds(const OrbitMeshlet *meshlets, uint64_t meshlet
             std::memcpy(&out[i], words, sizeof(words));
             if (range_error) range_error[i] = 0;
         }
+    });
+}
+
+int32_t orbit_host_raster_depth(const void *draw_commands, uint32_t max_commands, const uint32_t *meshlet_data,
+                                uint64_t meshlet_data_words, const void *vertices, uint64_t vertex_count,
+                                uint32_t vertex_stride, uint32_t position_offset, const OrbitEntityData *entity_data,
+                                uint32_t entity_count, const float view_proj[16], float *depth, uint32_t width,
+                                uint32_t height, uint32_t flags, OrbitRasterStats *stats, int32_t *command_error) {
+    return guarded([&] {
+        raster::HostJob j;
+        j.draw_commands = (const uint32_t *)draw_commands, j.max_commands = max_commands;
+        j.meshlet_data = meshlet_data, j.meshlet_data_words = meshlet_data_words;
+        j.vertices = (const uint8_t *)vertices, j.vertex_count = vertex_count;
+        j.vertex_stride = vertex_stride, j.position_offset = position_offset;
+        j.entity_data = entity_data, j.entity_count = entity_count;
+        j.view_proj = view_proj, j.depth = depth, j.width = width, j.height = height, j.flags = flags;
+        raster::raster_depth(j, stats, command_error);
     });
 }
 

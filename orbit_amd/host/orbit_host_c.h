@@ -219,6 +219,17 @@ int32_t orbit_host_meshlet_bounds(const OrbitMeshlet *meshlets, uint64_t meshlet
                                   uint32_t position_offset, OrbitMeshletBoundsFull *out, int32_t *range_error,
                                   uint32_t *updates);
 
+/* the reference of orbit_raster_depth (include/orbit_abi_ext.h R1-R9), on HOST copies of the same buffers, sequential:
+ * the same depth bytes (cleared first with ORBIT_RASTER_CLEAR, else max-merged into what `depth` holds), the same
+ * counters.  draw_commands = {u32 count; OrbitMeshletDrawCommand[]}, the count clamped by max_commands.
+ * stats (may be NULL): overwritten.  command_error (may be NULL): min(count, max_commands) flags, 1 where the device
+ * skips the command and latches ORBIT_E_RANGE.  ORBIT_HOST_PANIC for what the device call answers with ORBIT_E_INVALID. */
+int32_t orbit_host_raster_depth(const void *draw_commands, uint32_t max_commands, const uint32_t *meshlet_data,
+                                uint64_t meshlet_data_words, const void *vertices, uint64_t vertex_count,
+                                uint32_t vertex_stride, uint32_t position_offset, const OrbitEntityData *entity_data,
+                                uint32_t entity_count, const float view_proj[16], float *depth, uint32_t width,
+                                uint32_t height, uint32_t flags, OrbitRasterStats *stats, int32_t *command_error);
+
 /* ---- asset ingestion (orbit_gltf.hpp): glTF 2.0 (.glb / .gltf) -> materials, meshes with their LOD chains, entities ----
  * load_gltf (gltf_loader.rs:511-676) + GpuAssets::add_mesh (assets/mod.rs:325-476).  NULL + orbit_host_last_error()
  * on failure.  The arrays stay valid until orbit_host_gltf_free. */

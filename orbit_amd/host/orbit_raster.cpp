@@ -1,0 +1,85 @@
+// orbit_raster.cpp — see orbit_raster.hpp.
+#include "orbit_raster.hpp"
+
+#include <cstring>
+
+#include "../csrc/raster_common.h"
+#include "orbit_host.hpp"
+
+namespace orbit {
+namespace raster {
+
+void raster_depth(const HostJob &j, OrbitRasterStats *stats, int32_t *command_error) {
+    if (!j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data || !j.depth || !j.view_proj)
+        throw Panic("raster_depth: NULL argument");
+    if ((uint64_t)j.vertex_stride < (uint64_t)j.position_offset + 12u || (j.vertex_stride & 3u) || (j.position_offset & 3u))
+        throw Panic("raster_depth: vertex_stride / position_offset");
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        throw Panic("raster_depth: target size");
+    if (j.flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE)) throw Panic("raster_depth: unknown flags");
+    if (j.flags & ORBIT_RASTER_CLEAR) std::memset(j.depth, 0, (size_t)j.width * j.height * sizeof(float));
+    OrbitRasterStats st{};
+    const bool cull_none = (j.flags & ORBIT_RASTER_CULL_NONE) != 0u;
+    const uint8_t *data_bytes = reinterpret_cast<const uint8_t *>(j.meshlet_data);
+    const uint32_t count = j.draw_commands[0] < j.max_commands ? j.draw_commands[0] : j.max_commands;
+    const float w_f = (float)j.width, h_f = (float)j.height;
+    Vertex verts[256];
+    for (uint32_t i = 0; i < count; i++) {
+        const uint32_t *cmd = j.draw_commands + 1u + 7u * (size_t)i;
+        const uint32_t index_count = cmd[0], first_index = cmd[2], index_base = cmd[3], entity = cmd[4];
+        const uint64_t vertex_base = cmd[5];
+        const uint32_t nt = index_count / 3u, first_word = first_index / 4u;
+        const uint32_t vcount = first_word - index_base;
+        st.commands++;
+        if (command_error) command_error[i] = 1;
+        // R9
+        bool bad = first_word < index_base || vcount > 255u || (uint64_t)first_word > j.meshlet_data_words ||
+                   ((uint64_t)first_index + 3ull * nt + 3ull) / 4ull > j.meshlet_data_words || entity >= j.entity_count;
+        for (uint32_t v = 0; v < vcount && !bad; v++) bad = vertex_base + j.meshlet_data[index_base + v] >= j.vertex_count;
+        for (uint64_t b = 0; b < 3ull * nt && !bad; b++) bad = data_bytes[first_index + b] >= vcount;
+        if (bad) {
+            st.range_errors++;
+            continue;
+        }
+        if (command_error) command_error[i] = 0;
+        st.triangles += nt;
+        float mvp[16];
+        mat4_mul(j.view_proj, j.entity_data[entity].model_matrix, mvp);
+        for (uint32_t v = 0; v < vcount; v++) {
+            float pos[3];
+            std::memcpy(pos, j.vertices + (vertex_base + j.meshlet_data[index_base + v]) * j.vertex_stride + j.position_offset, 12);
+            verts[v] = transform_vertex(mvp, pos[0], pos[1], pos[2], w_f, h_f);
+        }
+        for (uint32_t t = 0; t < nt; t++) {
+            const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
+            Setup s;
+            switch (setup_triangle(verts[c[0]], verts[c[1]], verts[c[2]], j.width, j.height, cull_none, s)) {
+            case kClipSkipped: st.clip_skipped++; continue;
+            case kGuardSkipped: st.guard_skipped++; continue;
+            case kBackFacing: st.back_facing++; continue;
+            case kNoCoverage: st.no_coverage++; continue;
+            default: break;
+            }
+            uint64_t inside = 0;
+            for (int32_t y = s.y_lo; y <= s.y_hi; y++)
+                for (int32_t x = s.x_lo; x <= s.x_hi; x++) {
+                    const int32_t px = 256 * x + 128, py = 256 * y + 128;
+                    if (edge_at(s, 0, px, py) < 0 || edge_at(s, 1, px, py) < 0 || edge_at(s, 2, px, py) < 0) continue;
+                    inside++;
+                    const float d = depth_at(s, px, py);
+                    if (!(d > 0.0f)) continue;
+                    st.fragments++;
+                    uint32_t bits, old;
+                    float *dst = j.depth + (size_t)y * j.width + (uint32_t)x;
+                    std::memcpy(&bits, &d, 4);
+                    std::memcpy(&old, dst, 4);
+                    if (bits > old) std::memcpy(dst, &bits, 4); // R8: max on the u32 view
+                }
+            if (inside == 0) st.no_coverage++;
+        }
+    }
+    if (stats) *stats = st;
+}
+
+} // namespace raster
+} // namespace orbit

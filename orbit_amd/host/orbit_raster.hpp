@@ -1,0 +1,34 @@
+// orbit_raster.hpp — host mirror of orbit_raster_depth (include/orbit_abi_ext.h R1-R9): the depth
+// prepass of a MeshletDrawCommandBuffer on HOST copies of the same buffers, sequential.  It is the reference of the GPU
+// tests: the same depth bytes, the same counters, and a per-command flag where the device latches ORBIT_E_RANGE.  The
+// arithmetic (transform, snap, setup, edge functions, depth plane) is ../csrc/raster_common.h, shared with the kernel;
+// this side evaluates every edge function at every sample of a triangle's box directly, command after command.
+#pragma once
+#include <cstdint>
+
+#include "../../include/orbit_abi_ext.h"
+
+namespace orbit {
+namespace raster {
+
+struct HostJob {
+    const uint32_t *draw_commands; // {count; 7 words per command}
+    uint32_t max_commands;
+    const uint32_t *meshlet_data;
+    uint64_t meshlet_data_words;
+    const uint8_t *vertices;
+    uint64_t vertex_count;
+    uint32_t vertex_stride, position_offset;
+    const OrbitEntityData *entity_data;
+    uint32_t entity_count;
+    const float *view_proj;
+    float *depth;
+    uint32_t width, height, flags;
+};
+
+// Throws Panic for what the device call answers with ORBIT_E_INVALID.  stats and command_error (min(count,
+// max_commands) flags, 1 = skipped by a range check) may be null.
+void raster_depth(const HostJob &job, OrbitRasterStats *stats, int32_t *command_error);
+
+} // namespace raster
+} // namespace orbit

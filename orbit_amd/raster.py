@@ -1,0 +1,55 @@
+"""ctypes binding of the host mirror of ``orbit_raster_depth`` (``orbit_amd/host/orbit_raster.hpp``): the depth prepass
+of a MeshletDrawCommandBuffer on host arrays, the reference of ``Engine.raster_depth``.  Python adds nothing; host only."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from . import layouts as L
+from .passes import _check, lib
+
+CLEAR, CULL_NONE = _lib.RASTER_CLEAR, _lib.RASTER_CULL_NONE
+
+
+def command_buffer(commands, capacity=None, count=None):
+    """{u32 count; 28-B commands} as np.uint32 words from np[layouts.DRAW_COMMAND] rows; `count` overrides the header."""
+    cmds = np.ascontiguousarray(commands, dtype=L.MESHLET_DRAW_COMMAND)
+    capacity = len(cmds) if capacity is None else capacity
+    buf = np.zeros(1 + 7 * capacity, np.uint32)
+    buf[0] = len(cmds) if count is None else count
+    buf[1:1 + 7 * len(cmds)] = cmds.view(np.uint32).reshape(-1)
+    return buf
+
+
+def host_raster_depth(draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, view_proj, width,
+                      height, depth=None, clear=True, cull_none=False, vertex_stride=12, position_offset=0,
+                      entity_count=None, meshlet_data_words=None):
+    """orbit_host_raster_depth on host arrays -> (depth: np.float32 (height, width), stats: np[layouts.RASTER_STATS]
+    scalar row, command_error: np.int32 per processed command).  `draw_commands`: the {count; commands} words (any
+    contiguous array, read as bytes).  `depth`: the buffer to load (copied); None needs clear=True."""
+    buf = np.ascontiguousarray(draw_commands).view(np.uint8).reshape(-1)
+    if buf.nbytes < 4 + 28 * int(max_commands):
+        raise ValueError("max_commands reaches beyond the command array")
+    data = np.ascontiguousarray(meshlet_data, dtype=np.uint32).reshape(-1)
+    vb = np.ascontiguousarray(vertices).view(np.uint8).reshape(-1)
+    if int(vertex_count) and (int(vertex_count) - 1) * int(vertex_stride) + int(position_offset) + 12 > vb.nbytes:
+        raise ValueError("vertex_count reaches beyond the vertex array")
+    ent = np.ascontiguousarray(entity_data).view(np.uint8).reshape(-1)
+    entity_count = ent.nbytes // 128 if entity_count is None else int(entity_count)
+    words = len(data) if meshlet_data_words is None else int(meshlet_data_words)
+    if depth is None:
+        if not clear:
+            raise ValueError("no depth to load")
+        out = np.zeros((height, width), np.float32)
+    else:
+        out = np.array(depth, dtype=np.float32, order="C").reshape(height, width)
+    n = min(int(buf[:4].view(np.uint32)[0]), int(max_commands))
+    stats, err = np.zeros(1, L.RASTER_STATS), np.zeros(n, np.int32)
+    vp = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(lib().orbit_host_raster_depth(p(buf), C.c_uint32(max_commands), p(data), C.c_uint64(words), p(vb),
+                                         C.c_uint64(vertex_count), C.c_uint32(vertex_stride), C.c_uint32(position_offset),
+                                         p(ent), C.c_uint32(entity_count), vp, p(out), C.c_uint32(width), C.c_uint32(height),
+                                         C.c_uint32((CLEAR if clear else 0) | (CULL_NONE if cull_none else 0)), p(stats),
+                                         p(err)))
+    return out, stats[0], err
