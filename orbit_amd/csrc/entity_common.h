@@ -177,7 +177,7 @@ struct FusedEntity {
 // A workgroup draws a chunk of kEntityBlock entity-draws (ticket), evaluates them, publishes the chunk's record
 // count, adds up the counts published for the chunks before it (one poll: a cull has a few hundred chunks at most),
 // stores its MeshletDispatch records write-through at their canonical positions and adds itself to the arrival word
-// (chunks in << 32 | records so far); the last chunk in writes the {x,1,1} header (draw_gen.rs:356-363).
+// (chunks in << 40 | records so far: handoff.h kArriveOne); the last chunk in writes the {x,1,1} header (draw_gen.rs:356-363).
 struct EntityChunksArgs {
     uint8_t *dispatch_buffer;
     uint32_t dispatch_capacity;
@@ -253,9 +253,10 @@ __device__ __forceinline__ void entity_chunks(const E &ent, const EntityChunksAr
         uint32_t chunk_total;
         S.off[threadIdx.x] = block_exclusive_scan<kEntityBlock / 64>(n, S.smem, &chunk_total);
         // What this chunk PUBLISHES is cut to capacity + 1: the flag holds the count << 2 and the arrival word adds
-        // chunks << 32 | records, so a count of 2^30 (a corrupt mesh_infos meshlet_count) would wrap the one and carry
-        // into the chunk counter of the other — the header would never be written, or tiles would start early.  Every
-        // record past the capacity is dropped anyway, and capacity + 1 is what latches ORBIT_E_CAPACITY.
+        // chunks << 40 | records (handoff.h kArriveOne), so a count of 2^30 (a corrupt mesh_infos meshlet_count) would wrap
+        // the one and, summed over the chunks of a launch, carry into the chunk counter of the other — the header would
+        // never be written, or tiles would start early.  Every record past the capacity is dropped anyway, and
+        // capacity + 1 is what latches ORBIT_E_CAPACITY.
         chunk_total = min(uniform(chunk_total), a.dispatch_capacity + 1u);
         S.proto[threadIdx.x] = pr;
         // the chunk's count first (whoever waits for it must never wait for this chunk's own look-back) ...

@@ -5,7 +5,9 @@ depth_reduce.comp in the reference repo), vectorised over all invocations, to
 cross-check the C oracle (oracle/orbit_oracle.c): two restatements by different
 means must agree bit-for-bit on visibility.  Every arithmetic step is a single
 float32 numpy ufunc (no einsum/dot), so there is no contraction or
-reassociation.  Scans are restated with plain python loops (small cases only).
+reassociation.  The entity stage's record scan is restated with repeat /
+cumsum over whole arrays, the meshlet stage's words with plain python loops
+(small cases only).
 """
 import numpy as np
 
@@ -59,14 +61,27 @@ def gmin(x, y):
     return np.where(y < x, y, x).astype(np.float32)
 
 
-def dot3(ax, ay, az, bx, by, bz):
+def dot2(ax, ay, bx, by, contract=False):
+    """`contract` (here and below): the oracle's arith_profile(1) — Dot / matrix products as fma chains in component order."""
+    if contract:
+        return fma32(ay, by, (ax * bx).astype(np.float32))
+    return ((ax * bx).astype(np.float32) + (ay * by).astype(np.float32)).astype(np.float32)
+
+
+def dot3(ax, ay, az, bx, by, bz, contract=False):
+    if contract:
+        return fma32(az, bz, fma32(ay, by, (ax * bx).astype(np.float32)))
     return ((ax * bx + ay * by).astype(np.float32) + (az * bz).astype(np.float32)).astype(np.float32)
 
 
-def mat_vec(m, v0, v1, v2, v3):
+def mat_vec(m, v0, v1, v2, v3, contract=False):
     """GLSL mat4 * vec4 for batched column-major m[..., 16] -> 4 arrays."""
     out = []
     for r in range(4):
+        if contract:
+            t = fma32(m[..., 4 + r], v1, (m[..., 0 + r] * v0).astype(np.float32))
+            out.append(fma32(m[..., 12 + r], v3, fma32(m[..., 8 + r], v2, t)))
+            continue
         t = (m[..., 0 + r] * v0 + m[..., 4 + r] * v1).astype(np.float32)
         t = (t + (m[..., 8 + r] * v2).astype(np.float32)).astype(np.float32)
         t = (t + (m[..., 12 + r] * v3).astype(np.float32)).astype(np.float32)
@@ -74,12 +89,12 @@ def mat_vec(m, v0, v1, v2, v3):
     return out
 
 
-def mat_mul(a, b):
+def mat_mul(a, b, contract=False):
     """a[16] (single) x b[n,16] -> [n,16], column-major."""
     a = np.broadcast_to(np.asarray(a, dtype=np.float32), b.shape)
     out = np.empty_like(b)
     for c in range(4):
-        col = mat_vec(a, b[..., 4 * c + 0], b[..., 4 * c + 1], b[..., 4 * c + 2], b[..., 4 * c + 3])
+        col = mat_vec(a, b[..., 4 * c + 0], b[..., 4 * c + 1], b[..., 4 * c + 2], b[..., 4 * c + 3], contract)
         for r in range(4):
             out[..., 4 * c + r] = col[r]
     return out
@@ -108,23 +123,23 @@ def fma32(a, b, c):
 RCP127 = np.frombuffer(np.array([0x3C010204], np.uint32).tobytes(), np.float32)[0]  # the compiled shaders' 1/127
 
 
-def transform_sphere(m, sph):
+def transform_sphere(m, sph, contract=False):
     one = np.ones(len(sph), dtype=np.float32)
-    p = mat_vec(m, sph[:, 0], sph[:, 1], sph[:, 2], one)
+    p = mat_vec(m, sph[:, 0], sph[:, 1], sph[:, 2], one, contract)
     with np.errstate(all="ignore"):
         x, y, z = (p[0] / p[3]).astype(F), (p[1] / p[3]).astype(F), (p[2] / p[3]).astype(F)
-    dx = dot3(m[:, 0], m[:, 1], m[:, 2], m[:, 0], m[:, 1], m[:, 2])
-    dy = dot3(m[:, 4], m[:, 5], m[:, 6], m[:, 4], m[:, 5], m[:, 6])
-    dz = dot3(m[:, 8], m[:, 9], m[:, 10], m[:, 8], m[:, 9], m[:, 10])
+    dx = dot3(m[:, 0], m[:, 1], m[:, 2], m[:, 0], m[:, 1], m[:, 2], contract)
+    dy = dot3(m[:, 4], m[:, 5], m[:, 6], m[:, 4], m[:, 5], m[:, 6], contract)
+    dz = dot3(m[:, 8], m[:, 9], m[:, 10], m[:, 8], m[:, 9], m[:, 10], contract)
     scale = np.sqrt(gmax(dx, gmax(dy, dz)), dtype=np.float32)
     return x, y, z, (sph[:, 3] * scale).astype(np.float32), scale
 
 
-def plane_test(ci, x, y, z, r):
+def plane_test(ci, x, y, z, r, contract=False):
     vis = np.ones(len(x), dtype=bool)
     for i in range(int(ci["cull_plane_count"])):
         pl = ci["cull_planes"][i]
-        d = (dot3(pl[0], pl[1], pl[2], x, y, z) + pl[3]).astype(np.float32)
+        d = (dot3(pl[0], pl[1], pl[2], x, y, z, contract) + pl[3]).astype(np.float32)
         vis &= d > -r
     return vis
 
@@ -193,7 +208,7 @@ def hiz_sample(pyr, w0, h0, u, v, lod, detail=None):
     return sampled
 
 
-def occlusion_test(ci, x, y, z, r, pyr, pw, ph, radius, scale, detail=None):
+def occlusion_test(ci, x, y, z, r, pyr, pw, ph, radius, scale, detail=None, contract=False):
     """Returns (visible, z') — z' is the possibly flipped z (persists).  Operation by operation as the reference's
     compiled shaders hold it (oracle/orbit_oracle.c occlusion_test): radius = model-space radius, r = radius * scale.
     `detail`, a dict, receives cullable (and where it is decided by equality), u, v, lod, closest and hiz_sample's
@@ -211,12 +226,10 @@ def occlusion_test(ci, x, y, z, r, pyr, pw, ph, radius, scale, detail=None):
 
             def bounds(c0, c1):
                 # cx = -C.xz ; vx = (sqrt(dot(cx,cx) - r*r), r)
-                vx = np.sqrt(fma32(-r, r, (c0 * c0 + c1 * c1).astype(F)), dtype=F)
+                vx = np.sqrt(fma32(-r, r, dot2(c0, c1, c0, c1, contract)), dtype=F)
                 vy = r
-                mn_x = ((vx * c0).astype(F) + ((-vy) * c1).astype(F)).astype(F)
-                mn_y = ((vy * c0).astype(F) + (vx * c1).astype(F)).astype(F)
-                mx_x = ((vx * c0).astype(F) + (vy * c1).astype(F)).astype(F)
-                mx_y = (((-vy) * c0).astype(F) + (vx * c1).astype(F)).astype(F)
+                mn_x, mn_y = dot2(vx, (-vy).astype(F), c0, c1, contract), dot2(vy, vx, c0, c1, contract)
+                mx_x, mx_y = dot2(vx, vy, c0, c1, contract), dot2((-vy).astype(F), vx, c0, c1, contract)
                 return mn_x, mn_y, mx_x, mx_y
             minx_x, minx_y, maxx_x, maxx_y = bounds((-x).astype(F), (-z).astype(F))
             miny_x, miny_y, maxy_x, maxy_y = bounds((-y).astype(F), (-z).astype(F))
@@ -269,9 +282,11 @@ def f2u_sat(f):
 
 
 def entity_cull(ci, scene_draws, count, entity_draw_count, mesh_infos, entities, vis_words, pyr=None, pyr_size=(0, 0),
-                detail=None):
+                detail=None, S=32, contract=False):
     """Returns (visible[g], should_draw[g], records list, new entity words or None).  `detail`, a dict, receives
-    occlusion_test's intermediates of pass 2 and `reached`, the rows that got as far as that test."""
+    occlusion_test's intermediates of pass 2 and `reached`, the rows that got as far as that test, and per draw the
+    `mesh_lod` it picks and the `meshlets` and `records` it emits.  S: MESHLET_DISPATCH_SIZE of the records (pass 0);
+    contract: the oracle's arith_profile(1)."""
     end = min(count, (entity_draw_count + 255) // 256 * 256)
     draws = scene_draws[:end]
     g = np.arange(end)
@@ -283,11 +298,11 @@ def entity_cull(ci, scene_draws, count, entity_draw_count, mesh_infos, entities,
     if op in (1, 2):
         vib = ((vis_words[g // 32] >> (g % 32).astype(np.uint32)) & 1).astype(bool)
     visible = vib.copy() if op == 1 else np.ones(end, dtype=bool)
-    mv = mat_mul(ci["view_matrix"], en["model_matrix"])
-    x, y, z, r, scale = transform_sphere(mv, mi["bounding_sphere"])
-    visible &= np.where(visible, plane_test(ci, x, y, z, r), False)
+    mv = mat_mul(ci["view_matrix"], en["model_matrix"], contract)
+    x, y, z, r, scale = transform_sphere(mv, mi["bounding_sphere"], contract)
+    visible &= np.where(visible, plane_test(ci, x, y, z, r, contract), False)
     if op == 2:
-        ov, zf = occlusion_test(ci, x, y, z, r, pyr, *pyr_size, mi["bounding_sphere"][:, 3].astype(F), scale, detail)
+        ov, zf = occlusion_test(ci, x, y, z, r, pyr, *pyr_size, mi["bounding_sphere"][:, 3].astype(F), scale, detail, contract)
         if detail is not None:
             detail["reached"] = visible.copy()
         z = np.where(visible, zf, z).astype(np.float32) if int(ci["projection_type"]) == 0 else z
@@ -298,27 +313,31 @@ def entity_cull(ci, scene_draws, count, entity_draw_count, mesh_infos, entities,
     t = ci["lod_target_pos_view_space"]
     ex, ey, ez = (t[0] - x).astype(F), (t[1] - y).astype(F), (t[2] - z).astype(F)
     with np.errstate(all="ignore"):
-        dist = (np.sqrt(dot3(ex, ey, ez, ex, ey, ez), dtype=F) - r).astype(F)
+        dist = (np.sqrt(dot3(ex, ey, ez, ex, ey, ez, contract), dtype=F) - r).astype(F)
         lf = (log2c((gmax(dist, F(0.0)) / F(ci["lod_base"])).astype(F)) / log2c(np.array([ci["lod_step"]], F))).astype(F)
         lod = f2u_sat(gmax((lf + F(1.0)).astype(F), F(0.0)))
     lod = np.minimum(np.maximum(lod, int(ci["min_mesh_lod"])), int(ci["max_mesh_lod"]))
     lod = np.minimum(lod, (mi["lod_count"].astype(np.uint64) - 1) & 0xFFFFFFFF)
     lod = np.minimum(lod, 7).astype(np.int64)
-    records = []
-    for i in np.nonzero(should)[0]:
-        off, cnt = mi["mesh_lods"][i, lod[i]]
-        vo = int(draws["visibility_offset"][i])
-        for j in range((int(cnt) + S - 1) // S):
-            c = min(int(cnt) - S * j, S)
-            records.append((int(draws["entity_index"][i]), int(off) + S * j, c, vo))
-            vo += c // S
+    if detail is not None:  # per draw: the LOD it would pick, the meshlets and records it emits
+        cnt = np.where(should, mi["mesh_lods"][g, lod, 1].astype(np.int64), 0) if end else np.zeros(0, np.int64)
+        detail.update(mesh_lod=lod, meshlets=cnt, records=(cnt + S - 1) // S)
+    # record j of a draw: every record before it is full, so its word offset has advanced by j (c // S == 1 each)
+    idx = np.nonzero(should)[0]
+    off, cnt = (mi["mesh_lods"][idx, lod[idx], k].astype(np.int64) for k in (0, 1))
+    per = (cnt + S - 1) // S
+    own = np.repeat(np.arange(len(idx)), per)
+    j = np.arange(int(per.sum())) - np.repeat(np.cumsum(per) - per, per)
+    records = np.stack([draws["entity_index"][idx][own].astype(np.int64), off[own] + S * j,
+                        np.minimum(cnt[own] - S * j, S), draws["visibility_offset"][idx][own].astype(np.int64) + j],
+                       axis=1) & 0xFFFFFFFF
     new_words = None
     if op == 2:
         new_words = vis_words.copy()
-        for w in range((end + 31) // 32):
-            bits = visible[32 * w:32 * w + 32]
-            new_words[w] = sum(int(b) << k for k, b in enumerate(bits))
-    return visible, should, np.array(records, dtype=np.uint32).reshape(-1, 4).view(L.MESHLET_DISPATCH).reshape(-1), new_words
+        bits = np.zeros((end + 31) // 32 * 32, dtype=np.uint64)
+        bits[:end] = visible
+        new_words[:len(bits) // 32] = (bits.reshape(-1, 32) << np.arange(32, dtype=np.uint64)).sum(axis=1).astype(np.uint32)
+    return visible, should, np.ascontiguousarray(records.astype(np.uint32)).view(L.MESHLET_DISPATCH).reshape(-1), new_words
 
 
 def meshlet_cull(ci, records, meshlets, entities, materials, mvis, pyr=None, pyr_size=(0, 0), detail=None):
