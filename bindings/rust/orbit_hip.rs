@@ -130,6 +130,30 @@ pub struct OrbitRasterDepth {
     pub view_proj: [f32; 16],
 }
 
+pub const ORBIT_VIS_MAX_COMMANDS: u32 = 1 << 24;
+
+/// orbit_raster_visibility's argument block (160 B, HOST): OrbitRasterDepth with the u64 buffer and command_base
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitRasterVisibility {
+    pub draw_commands: *const c_void, pub meshlet_data: *const u32, pub vertices: *const c_void,
+    pub entity_data: *const c_void, pub visibility: *mut u64, pub stats: *mut OrbitRasterStats,
+    pub meshlet_data_words: u64, pub vertex_count: u64,
+    pub max_commands: u32, pub entity_count: u32, pub vertex_stride: u32, pub position_offset: u32,
+    pub width: u32, pub height: u32, pub flags: u32, pub command_base: u32,
+    pub view_proj: [f32; 16],
+}
+
+/// The counters of orbit_visibility_resolve (16 B, DEVICE)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitVisibilityStats { pub covered_pixels: u32, pub visible_commands: u32, pub foreign_pixels: u32, pub _pad: u32 }
+
+/// orbit_visibility_resolve's argument block (48 B, HOST): DEVICE pointers; each output may be null, not all
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitVisibilityResolve {
+    pub visibility: *const u64, pub depth: *mut f32, pub command_pixels: *mut u32, pub stats: *mut OrbitVisibilityStats,
+    pub width: u32, pub height: u32, pub command_base: u32, pub max_commands: u32,
+}
+
 /// push-constant order of shaders/entity_cull.comp:17-23 (== draw_gen.rs:372-376)
 #[repr(C)]
 pub struct OrbitEntityCullBufs {
@@ -318,6 +342,11 @@ extern "C" {
     /// Byte-equal to the host mirror.  Near-plane clipping is out of scope: a triangle with a vertex outside w > 0,
     /// 0 <= z <= w is not drawn.  Cull occluders with alpha_mode_flag = OPAQUE: masked materials are not alpha-tested.
     pub fn orbit_raster_depth(ctx: *mut OrbitCtx, job: *const OrbitRasterDepth, stream: *mut c_void) -> i32;
+    /// orbit_raster_depth keeping the winner: per pixel float_bits(d) << 32 | (command_base + i) << 8 | t, merged by a
+    /// 64-bit atomic max; 0 is an uncovered pixel.  A command with more than 256 triangles is a range error.
+    pub fn orbit_raster_visibility(ctx: *mut OrbitCtx, job: *const OrbitRasterVisibility, stream: *mut c_void) -> i32;
+    /// One read of the visibility buffer: depth (the high halves), pixels per command, covered / visible / foreign counts.
+    pub fn orbit_visibility_resolve(ctx: *mut OrbitCtx, job: *const OrbitVisibilityResolve, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

@@ -937,6 +937,94 @@ ORBIT_STATIC_ASSERT(offsetof(OrbitRasterDepth, view_proj) == 96, "view_proj @96"
 /* the depth prepass of the draw commands in compute; see above */
 int32_t orbit_raster_depth(OrbitCtx *ctx, const OrbitRasterDepth *job, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* Visibility buffer on the device.  orbit_raster_visibility is             */
+/* orbit_raster_depth with the identity of the winner kept: per pixel one   */
+/* u64 holding depth, draw and triangle, merged by one 64-bit atomicMax;    */
+/* orbit_visibility_resolve turns the buffer into depth, per-command pixel  */
+/* counts and the visible set.  Same definition on the device and in the    */
+/* host mirror (orbit_host_raster_visibility, orbit_host_visibility_resolve)*/
+/*  V1 R1-R7 and R9 hold unchanged: the same decode, transform, snap,       */
+/*     rejects, coverage and depth plane (raster_common.h).                 */
+/*  V2 an inside sample with d > 0 of triangle t of command i (its position */
+/*     in the list) produces the word                                       */
+/*       (u64)float_bits(d) << 32 | (command_base + i) << 8 | t;            */
+/*     visibility[y * W + x] = max(old, word) on the u64 view (64-bit       */
+/*     atomicMax).  Cleared is 0, and 0 is an uncovered pixel: d > 0 for    */
+/*     every written word.  Equal depth resolves to the larger id.  A word  */
+/*     depends on one triangle and its position in the list only: the       */
+/*     buffer is independent of scheduling (NOT of command order: the id is */
+/*     the position), and every counter is order-free as before.            */
+/*  V3 a command with nt > 256 is skipped whole (range_errors) and latches  */
+/*     ORBIT_E_RANGE, like the R9 failures.  command_base + max_commands >  */
+/*     ORBIT_VIS_MAX_COMMANDS, or visibility NULL or not 8-B aligned, is    */
+/*     ORBIT_E_INVALID; every other argument error is orbit_raster_depth's. */
+/*  V4 consequences: the high halves equal, byte for byte, the `depth`      */
+/*     orbit_raster_depth leaves for the same job, and `stats` is identical */
+/*     as long as no command has nt > 256.                                  */
+/* ORBIT_RASTER_CLEAR clears the buffer to 0 on the stream first; without   */
+/* it the call merges into what an earlier call left (the late pass), and   */
+/* command_base keeps the late list's ids apart from the early one's.       */
+/* ORBIT_RASTER_CULL_NONE as before.  No allocation, no scratch, no host    */
+/* wait, the count is read on the device, kernels only: a graph captures    */
+/* the call on a fresh context's first call.                                */
+/*                                                                          */
+/* orbit_visibility_resolve reads each word once.  Each output may be NULL; */
+/* all three NULL is ORBIT_E_INVALID:                                       */
+/*   depth[p]           the high half of word p as a float: what            */
+/*                      orbit_depth_reduce and the late cull read           */
+/*   command_pixels[k]  k < max_commands, cleared by the call: the pixels   */
+/*                      whose winner is command command_base + k            */
+/*   stats              cleared by the call.  covered_pixels: words != 0;   */
+/*                      foreign_pixels: covered pixels whose command lies   */
+/*                      outside [command_base, command_base + max_commands);*/
+/*                      visible_commands: non-zero entries of               */
+/*                      command_pixels, 0 when command_pixels is NULL       */
+/* All outputs are integer sums: independent of scheduling.                 */
+/*   ORBIT_E_INVALID  job or visibility NULL, visibility not 8-B aligned,   */
+/*                    an output not 4-B aligned, all outputs NULL, width or */
+/*                    height 0 or above ORBIT_RASTER_MAX_DIM, command_base  */
+/*                    + max_commands > ORBIT_VIS_MAX_COMMANDS               */
+/* Capturable, with the same no-allocation and no-host-wait rules.          */
+/* ------------------------------------------------------------------------ */
+#define ORBIT_VIS_MAX_COMMANDS (1u << 24)
+typedef struct OrbitRasterVisibility { /* HOST block, 160 B; every pointer a DEVICE pointer; as OrbitRasterDepth */
+    const void *draw_commands;
+    const uint32_t *meshlet_data;
+    const void *vertices;
+    const OrbitEntityData *entity_data;
+    uint64_t *visibility;               /* width * height u64, 8-B aligned */
+    OrbitRasterStats *stats;            /* NULL, or the counters */
+    uint64_t meshlet_data_words, vertex_count;
+    uint32_t max_commands, entity_count, vertex_stride, position_offset, width, height, flags, command_base;
+    float view_proj[16];
+} OrbitRasterVisibility;
+ORBIT_STATIC_ASSERT(sizeof(OrbitRasterVisibility) == 160, "RasterVisibility is 160 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitRasterVisibility, visibility) == 32, "visibility @32");
+ORBIT_STATIC_ASSERT(offsetof(OrbitRasterVisibility, meshlet_data_words) == 48, "meshlet_data_words @48");
+ORBIT_STATIC_ASSERT(offsetof(OrbitRasterVisibility, max_commands) == 64, "max_commands @64");
+ORBIT_STATIC_ASSERT(offsetof(OrbitRasterVisibility, command_base) == 92, "command_base @92");
+ORBIT_STATIC_ASSERT(offsetof(OrbitRasterVisibility, view_proj) == 96, "view_proj @96");
+
+typedef struct OrbitVisibilityStats { /* DEVICE, 16 B */
+    uint32_t covered_pixels, visible_commands, foreign_pixels, _pad;
+} OrbitVisibilityStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitVisibilityStats) == 16, "VisibilityStats is 16 B");
+typedef struct OrbitVisibilityResolve { /* HOST block, 48 B; every pointer a DEVICE pointer */
+    const uint64_t *visibility;  /* width * height u64 */
+    float *depth;                /* NULL, or width * height floats */
+    uint32_t *command_pixels;    /* NULL, or max_commands words */
+    OrbitVisibilityStats *stats; /* NULL, or the counters */
+    uint32_t width, height, command_base, max_commands;
+} OrbitVisibilityResolve;
+ORBIT_STATIC_ASSERT(sizeof(OrbitVisibilityResolve) == 48, "VisibilityResolve is 48 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilityResolve, stats) == 24, "stats @24");
+ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilityResolve, width) == 32, "width @32");
+
+/* the visibility buffer of the draw commands in compute, and its resolve; see above */
+int32_t orbit_raster_visibility(OrbitCtx *ctx, const OrbitRasterVisibility *job, void *stream);
+int32_t orbit_visibility_resolve(OrbitCtx *ctx, const OrbitVisibilityResolve *job, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

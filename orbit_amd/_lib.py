@@ -102,6 +102,21 @@ class RasterDepth(C.Structure):  # OrbitRasterDepth
 
 RASTER_CLEAR, RASTER_CULL_NONE = 1, 2  # ORBIT_RASTER_CLEAR, ORBIT_RASTER_CULL_NONE
 RASTER_MAX_DIM = 32768                 # ORBIT_RASTER_MAX_DIM
+VIS_MAX_COMMANDS = 1 << 24             # ORBIT_VIS_MAX_COMMANDS
+
+
+class RasterVisibility(C.Structure):  # OrbitRasterVisibility: RasterDepth with visibility for depth, command_base for _pad
+    _fields_ = [("draw_commands", C.c_void_p), ("meshlet_data", C.c_void_p), ("vertices", C.c_void_p),
+                ("entity_data", C.c_void_p), ("visibility", C.c_void_p), ("stats", C.c_void_p),
+                ("meshlet_data_words", C.c_uint64), ("vertex_count", C.c_uint64), ("max_commands", C.c_uint32),
+                ("entity_count", C.c_uint32), ("vertex_stride", C.c_uint32), ("position_offset", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("command_base", C.c_uint32),
+                ("view_proj", C.c_float * 16)]
+
+
+class VisibilityResolve(C.Structure):  # OrbitVisibilityResolve
+    _fields_ = [("visibility", C.c_void_p), ("depth", C.c_void_p), ("command_pixels", C.c_void_p), ("stats", C.c_void_p),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("command_base", C.c_uint32), ("max_commands", C.c_uint32)]
 
 
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
@@ -193,6 +208,8 @@ SYMBOLS = {
     "orbit_mesh_bounds": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                       C.c_void_p, C.c_uint32, C.c_void_p]),
     "orbit_raster_depth": (C.c_int32, [C.c_void_p, C.POINTER(RasterDepth), C.c_void_p]),
+    "orbit_raster_visibility": (C.c_int32, [C.c_void_p, C.POINTER(RasterVisibility), C.c_void_p]),
+    "orbit_visibility_resolve": (C.c_int32, [C.c_void_p, C.POINTER(VisibilityResolve), C.c_void_p]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 // abi_assets.hip — the C ABI's calls that read the vertex buffer (include/orbit_abi_ext.h): orbit_meshlet_bounds and
-// orbit_mesh_bounds, the refit of Meshlet and MeshInfo bounds on the device (meshlet_bounds.hip), and orbit_raster_depth,
-// the depth prepass of the draw commands in compute (raster_depth.hip).
+// orbit_mesh_bounds, the refit of Meshlet and MeshInfo bounds on the device (meshlet_bounds.hip), orbit_raster_depth,
+// the depth prepass of the draw commands in compute (raster_depth.hip), and orbit_raster_visibility with
+// orbit_visibility_resolve, the same pass keeping the winner's identity and its resolve (raster_visibility.hip).
 #include "abi_internal.h"
 
 namespace {
@@ -81,6 +82,53 @@ int32_t orbit_raster_depth(OrbitCtx *ctx, const OrbitRasterDepth *job, void *str
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_raster_depth(j, ctx->raster_blocks, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_depth");
+    return ORBIT_OK;
+}
+
+// As orbit_raster_depth, into the u64 buffer: a clearing launch (CLEAR, stats) and the raster launch.  No allocation, no
+// scratch, no host sync: capturable on the first call.
+int32_t orbit_raster_visibility(OrbitCtx *ctx, const OrbitRasterVisibility *job, void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "raster_visibility: job is NULL");
+    const OrbitRasterVisibility &j = *job;
+    if (j.flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE))
+        return fail(ctx, ORBIT_E_INVALID, "raster_visibility: flags %#x", j.flags);
+    if (const int32_t rc = check_vertex_layout(ctx, "raster_visibility", j.vertex_stride, j.position_offset)) return rc;
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "raster_visibility: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS)
+        return fail(ctx, ORBIT_E_INVALID, "raster_visibility: command_base %u + max_commands %u > %u (24 bits of id)",
+                    j.command_base, j.max_commands, ORBIT_VIS_MAX_COMMANDS);
+    if (!j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data || !j.visibility)
+        return fail(ctx, ORBIT_E_INVALID, "raster_visibility: NULL buffer");
+    if ((((uintptr_t)j.draw_commands | (uintptr_t)j.meshlet_data | (uintptr_t)j.vertices | (uintptr_t)j.stats) & 3u) ||
+        ((uintptr_t)j.entity_data & 15u) || ((uintptr_t)j.visibility & 7u))
+        return fail(ctx, ORBIT_E_INVALID,
+                    "raster_visibility: every buffer must be 4-B aligned, visibility 8-B, entity_data 16-B aligned");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_raster_visibility(j, ctx->visibility_blocks, ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_visibility");
+    return ORBIT_OK;
+}
+
+// A clearing launch (command_pixels, stats) and the resolve launch.  No allocation, no scratch, no host sync.
+int32_t orbit_visibility_resolve(OrbitCtx *ctx, const OrbitVisibilityResolve *job, void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "visibility_resolve: job is NULL");
+    const OrbitVisibilityResolve &j = *job;
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "visibility_resolve: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS)
+        return fail(ctx, ORBIT_E_INVALID, "visibility_resolve: command_base %u + max_commands %u > %u (24 bits of id)",
+                    j.command_base, j.max_commands, ORBIT_VIS_MAX_COMMANDS);
+    if (!j.visibility || ((uintptr_t)j.visibility & 7u))
+        return fail(ctx, ORBIT_E_INVALID, "visibility_resolve: visibility is NULL or not 8-B aligned");
+    if (!j.depth && !j.command_pixels && !j.stats) return fail(ctx, ORBIT_E_INVALID, "visibility_resolve: no output");
+    if (((uintptr_t)j.depth | (uintptr_t)j.command_pixels | (uintptr_t)j.stats) & 3u)
+        return fail(ctx, ORBIT_E_INVALID, "visibility_resolve: every output must be 4-B aligned");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_visibility_resolve(j, ctx->num_cus, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_resolve");
     return ORBIT_OK;
 }
 

@@ -149,6 +149,7 @@ int32_t orbit_ctx_create(int32_t device_id, const OrbitCaps *caps_in, OrbitCtx *
     ctx->device = device_id;
     ctx->num_cus = (uint32_t)prop.multiProcessorCount;
     ctx->raster_blocks = ctx->num_cus * raster_depth_blocks_per_cu();
+    ctx->visibility_blocks = ctx->num_cus * raster_visibility_blocks_per_cu();
     ctx->caps = caps;
     ctx->rec_shift = rec_shift;
 

@@ -1,0 +1,195 @@
+// raster_walk.h — the walker of the compute rasteriser as a template on the SINK that takes an inside sample: the
+// command loop, the vertex phase, the per-lane triangle setup and the lane / wave walks of DESIGN.md §4.12.  A sink has
+//   static constexpr uint32_t kMaxTriangles   a command with more triangles is a range error (V3); ~0u: no limit
+//   bool write(const Setup &, x, y, width, id) const   R7 + the merge of one inside sample -> it is a fragment (d > 0)
+// where id = (id_base + the command's position) << 8 | triangle index.  raster_visibility.hip instantiates it.
+// raster_depth.hip still carries the copy this was lifted from: instantiated from here its kernel is allocated 149
+// VGPRs instead of 154 — a different schedule, which has to be timed on the device before it replaces a pinned kernel
+// (DESIGN.md §4.13).  Until then a change to the walk is made in both places.  The arithmetic is raster_common.h's.
+#pragma once
+#include "kernels.h"
+#include "orbit_device.h"
+#include "raster_common.h"
+
+namespace orbit {
+namespace raster {
+
+constexpr uint32_t kRasterThreads = 256, kRasterWaves = kRasterThreads / 64;
+constexpr uint32_t kMaxVertices = 256; // vcount <= 255 (R9)
+constexpr int32_t kLaneBox = 16; // samples: a box no larger is walked by the triangle's own lane (not yet tuned)
+
+struct RasterParams { // what the walker reads; the target belongs to the sink
+    const uint32_t *commands; // {count; 7 words per command}
+    const uint32_t *meshlet_data;
+    const uint8_t *vertices;
+    const float *entity_data; // 32 floats per entity, the model matrix first
+    uint32_t *stats;
+    uint64_t meshlet_data_words, vertex_count;
+    uint32_t max_commands, entity_count, vertex_stride, position_offset, width, height, flags;
+    float view_proj[16];
+    int32_t *status;
+};
+
+inline void fill_raster_params(RasterParams &p, const void *draw_commands, const uint32_t *meshlet_data, const void *vertices,
+                               const void *entity_data, void *stats, uint64_t meshlet_data_words, uint64_t vertex_count,
+                               uint32_t max_commands, uint32_t entity_count, uint32_t vertex_stride, uint32_t position_offset,
+                               uint32_t width, uint32_t height, uint32_t flags, const float *view_proj, int32_t *status) {
+    p.commands = (const uint32_t *)draw_commands;
+    p.meshlet_data = meshlet_data;
+    p.vertices = (const uint8_t *)vertices;
+    p.entity_data = (const float *)entity_data;
+    p.stats = (uint32_t *)stats;
+    p.meshlet_data_words = meshlet_data_words, p.vertex_count = vertex_count;
+    p.max_commands = max_commands, p.entity_count = entity_count;
+    p.vertex_stride = vertex_stride, p.position_offset = position_offset;
+    p.width = width, p.height = height, p.flags = flags;
+    for (int k = 0; k < 16; k++) p.view_proj[k] = view_proj[k];
+    p.status = status;
+}
+
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ Vertex lds_vertex(const int4 *verts, uint32_t i) {
+    const int4 w = verts[i];
+    Vertex v;
+    v.X = w.x, v.Y = w.y, v.d = __int_as_float(w.z), v.flags = (uint32_t)w.w;
+    return v;
+}
+
+// The samples (x_lo + x0 + k * step_x, y_lo + y0 + j * step_y) of the triangle's box: the lane path takes all of them
+// (x0 = y0 = 0, steps of 1), a lane of the wave path its own sample of every 8 x 8 tile.  -> inside samples; fragments
+// are added to `fragments`.
+template <class Sink>
+__device__ __forceinline__ uint32_t walk(const Sink &sink, uint32_t width, const Setup &s, int32_t x0, int32_t y0,
+                                         int32_t step, uint32_t id, uint32_t &fragments) {
+    uint32_t inside = 0;
+    const int64_t sx0 = -(int64_t)s.dy[0] * 256 * step, sx1 = -(int64_t)s.dy[1] * 256 * step,
+                  sx2 = -(int64_t)s.dy[2] * 256 * step; // E(px + 256 step) - E(px)
+    for (int32_t y = s.y_lo + y0; y <= s.y_hi; y += step) {
+        const int32_t x = s.x_lo + x0, py = 256 * y + 128;
+        int64_t e0 = edge_at(s, 0, 256 * x + 128, py), e1 = edge_at(s, 1, 256 * x + 128, py),
+                e2 = edge_at(s, 2, 256 * x + 128, py);
+        for (int32_t xx = x; xx <= s.x_hi; xx += step) {
+            if ((e0 | e1 | e2) >= 0) {
+                inside++;
+                fragments += sink.write(s, xx, y, width, id) ? 1u : 0u;
+            }
+            e0 += sx0, e1 += sx1, e2 += sx2;
+        }
+    }
+    return inside;
+}
+
+// The body of a raster kernel: a resident grid of wave64s striding over the command list (raster_depth.hip's header
+// names the phases).  `id_base` is added to the command's position in the list before it goes into the sample's id.
+template <class Sink>
+__device__ __forceinline__ void raster_commands(const RasterParams &p, const Sink &sink, uint32_t id_base) {
+    __shared__ int4 lds_verts[kRasterWaves][kMaxVertices];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int4 *verts = lds_verts[wave];
+    const uint8_t *data_bytes = (const uint8_t *)p.meshlet_data;
+    const uint32_t listed = p.commands[0];
+    const uint32_t count = listed < p.max_commands ? listed : p.max_commands;
+    const bool cull_none = (p.flags & ORBIT_RASTER_CULL_NONE) != 0u;
+    const float w_f = (float)p.width, h_f = (float)p.height;
+    // this lane's share of the counters, OrbitRasterStats' order
+    uint32_t n_commands = 0, n_triangles = 0, n_outcome[5] = {0, 0, 0, 0, 0}, n_fragments = 0, n_range = 0;
+    const uint32_t stride = gridDim.x * kRasterWaves;
+    if (blockIdx.x * kRasterWaves + wave >= count) return; // (wave-uniform) no command for this wave: nothing to add
+    for (uint32_t i = blockIdx.x * kRasterWaves + wave; i < count; i += stride) {
+        const uint32_t *cmd = p.commands + 1u + 7u * (size_t)i;
+        const uint32_t index_count = cmd[0], first_index = cmd[2], index_base = cmd[3], entity = cmd[4];
+        const uint64_t vertex_base = cmd[5];
+        const uint32_t nt = index_count / 3u, first_word = first_index / 4u;
+        const uint32_t vcount = first_word - index_base; // (meaningful once first_word >= index_base)
+        if (lane == 0u) n_commands++;
+        // R9 (and V3's triangle limit), the wave-uniform part: the index words [index_base, first_word) and the corner
+        // bytes lie in meshlet_data
+        bool bad = first_word < index_base || vcount > 255u || (uint64_t)first_word > p.meshlet_data_words ||
+                   ((uint64_t)first_index + 3ull * nt + 3ull) / 4ull > p.meshlet_data_words || entity >= p.entity_count ||
+                   nt > Sink::kMaxTriangles;
+        if (!bad) {
+            float mvp[16];
+            {
+                const float *model = p.entity_data + 32u * (size_t)entity;
+                float m[16];
+                for (int k = 0; k < 16; k++) m[k] = model[k];
+                mat4_mul(p.view_proj, m, mvp);
+            }
+            bool lane_bad = false;
+            for (uint32_t v = lane; v < vcount; v += 64u) {
+                const uint64_t g = vertex_base + p.meshlet_data[index_base + v];
+                Vertex out;
+                out.X = out.Y = 0, out.d = 0.f, out.flags = kClipFail;
+                if (g < p.vertex_count) {
+                    const float *src = (const float *)(p.vertices + g * p.vertex_stride + p.position_offset);
+                    out = transform_vertex(mvp, src[0], src[1], src[2], w_f, h_f);
+                } else {
+                    lane_bad = true;
+                }
+                verts[v] = make_int4(out.X, out.Y, __float_as_int(out.d), (int)out.flags);
+            }
+            for (uint32_t t = lane; t < nt; t += 64u) {
+                const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
+                if (c[0] >= vcount || c[1] >= vcount || c[2] >= vcount) lane_bad = true;
+            }
+            bad = __ballot(lane_bad) != 0ull;
+        }
+        if (bad) { // the command is skipped whole
+            if (lane == 0u) {
+                n_range++;
+                latch_status(p.status, ORBIT_E_RANGE);
+            }
+            continue;
+        }
+        if (lane == 0u) n_triangles += nt;
+        const uint32_t command_id = (id_base + i) << 8;
+        wave_lds_sync();
+        for (uint32_t base = 0; base < nt; base += 64u) {
+            const uint32_t t = base + lane;
+            Setup s;
+            uint32_t corners = 0;
+            bool draw = false;
+            if (t < nt) {
+                const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
+                corners = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
+                const uint32_t outcome = setup_triangle(lds_vertex(verts, c[0]), lds_vertex(verts, c[1]),
+                                                        lds_vertex(verts, c[2]), p.width, p.height, cull_none, s);
+                for (uint32_t k = 1; k < 5u; k++) n_outcome[k] += outcome == k ? 1u : 0u;
+                draw = outcome == kDraw;
+            }
+            // (boxes are at most 32768^2 samples: the product fits)
+            const bool small = draw && (s.x_hi - s.x_lo + 1) * (s.y_hi - s.y_lo + 1) <= kLaneBox;
+            if (small && walk(sink, p.width, s, 0, 0, 1, command_id | t, n_fragments) == 0u) n_outcome[kNoCoverage]++;
+            uint64_t large = __ballot(draw && !small);
+            while (large != 0ull) {
+                const uint32_t src = (uint32_t)__builtin_ctzll(large);
+                large &= large - 1ull;
+                const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)corners, (int)src);
+                Setup ws;
+                (void)setup_triangle(lds_vertex(verts, c & 0xFFu), lds_vertex(verts, (c >> 8) & 0xFFu),
+                                     lds_vertex(verts, c >> 16), p.width, p.height, cull_none, ws);
+                const uint32_t inside = walk(sink, p.width, ws, (int32_t)(lane & 7u), (int32_t)(lane >> 3), 8,
+                                             command_id | (base + src), n_fragments);
+                if (__ballot(inside != 0u) == 0ull && lane == 0u) n_outcome[kNoCoverage]++;
+            }
+        }
+        wave_lds_sync(); // the next command overwrites the wave's vertices
+    }
+    if (!p.stats) return;
+    uint32_t sums[8] = {n_commands,           n_triangles,           n_outcome[kClipSkipped], n_outcome[kGuardSkipped],
+                        n_outcome[kBackFacing], n_outcome[kNoCoverage], n_fragments,            n_range};
+    for (uint32_t k = 0; k < 8u; k++) {
+        uint32_t v = sums[k];
+        for (uint32_t d = 1; d < 64u; d <<= 1) v += (uint32_t)__shfl_xor((int)v, (int)d, 64);
+        if (lane == 0u && v != 0u) atomicAdd(&p.stats[k], v);
+    }
+}
+
+} // namespace raster
+} // namespace orbit

@@ -337,6 +337,41 @@ class Engine:
         j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
         _lib.check(self._lib.orbit_raster_depth(self._ctx, C.byref(j), _stream(stream)), self._ctx)
 
+    # -- the same pass keeping the winner's identity, and its resolve (orbit_raster_visibility, orbit_visibility_resolve)
+    def raster_visibility(self, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data,
+                          entity_count, view_proj, visibility, width, height, command_base=0, clear=False,
+                          cull_none=False, stats=None, vertex_stride=12, position_offset=0, meshlet_data_words=None,
+                          stream=None):
+        """raster_depth into the width x height u64 tensor `visibility` (8-B aligned): an inside sample with depth d > 0
+        of triangle t of the i-th command merges float_bits(d) << 32 | (command_base + i) << 8 | t by a 64-bit
+        atomicMax into what the buffer holds, or into zeros with clear=True; 0 is an uncovered pixel.  The high halves
+        are raster_depth's depth bytes.  A command with more than 256 triangles is skipped like one that points out of
+        range (status(): ORBIT_E_RANGE); command_base + max_commands may not exceed 2^24.  Byte-equal to
+        orbit_amd.raster.host_raster_visibility on host copies.  Enqueued on `stream`."""
+        nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
+        j = _lib.RasterVisibility()
+        j.draw_commands, j.meshlet_data, j.vertices = _ptr(draw_commands), _ptr(meshlet_data), _ptr(vertices)
+        j.entity_data, j.visibility, j.stats = _ptr(entity_data), _ptr(visibility), _ptr(stats)
+        j.meshlet_data_words = nbytes(meshlet_data) // 4 if meshlet_data_words is None else int(meshlet_data_words)
+        j.vertex_count, j.max_commands, j.entity_count = int(vertex_count), int(max_commands), int(entity_count)
+        j.vertex_stride, j.position_offset, j.width, j.height = int(vertex_stride), int(position_offset), int(width), int(height)
+        j.flags = (_lib.RASTER_CLEAR if clear else 0) | (_lib.RASTER_CULL_NONE if cull_none else 0)
+        j.command_base = int(command_base)
+        j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
+        _lib.check(self._lib.orbit_raster_visibility(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
+    def visibility_resolve(self, visibility, width, height, command_base=0, max_commands=0, depth=None,
+                           command_pixels=None, stats=None, stream=None):
+        """One read of the width x height u64 tensor `visibility`.  depth (width * height floats): the high halves, what
+        depth_reduce and the late cull read; command_pixels (max_commands u32, cleared by the call): the pixels whose
+        winner is command command_base + k; stats (16 bytes, layouts.VIS_STATS, cleared by the call): covered_pixels,
+        visible_commands (non-zero entries of command_pixels), foreign_pixels (covered, command outside the range).
+        Each output may be None, not all.  Enqueued on `stream`."""
+        j = _lib.VisibilityResolve()
+        j.visibility, j.depth, j.command_pixels, j.stats = _ptr(visibility), _ptr(depth), _ptr(command_pixels), _ptr(stats)
+        j.width, j.height, j.command_base, j.max_commands = int(width), int(height), int(command_base), int(max_commands)
+        _lib.check(self._lib.orbit_visibility_resolve(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                    entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,

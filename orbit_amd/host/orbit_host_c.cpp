@@ -570,6 +570,32 @@ int32_t orbit_host_raster_depth(const void *draw_commands, uint32_t max_commands
     });
 }
 
+int32_t orbit_host_raster_visibility(const void *draw_commands, uint32_t max_commands, const uint32_t *meshlet_data,
+                                     uint64_t meshlet_data_words, const void *vertices, uint64_t vertex_count,
+                                     uint32_t vertex_stride, uint32_t position_offset, const OrbitEntityData *entity_data,
+                                     uint32_t entity_count, const float view_proj[16], uint64_t *visibility, uint32_t width,
+                                     uint32_t height, uint32_t flags, uint32_t command_base, OrbitRasterStats *stats,
+                                     int32_t *command_error) {
+    return guarded([&] {
+        raster::HostJob j;
+        j.draw_commands = (const uint32_t *)draw_commands, j.max_commands = max_commands;
+        j.meshlet_data = meshlet_data, j.meshlet_data_words = meshlet_data_words;
+        j.vertices = (const uint8_t *)vertices, j.vertex_count = vertex_count;
+        j.vertex_stride = vertex_stride, j.position_offset = position_offset;
+        j.entity_data = entity_data, j.entity_count = entity_count;
+        j.view_proj = view_proj, j.depth = nullptr, j.width = width, j.height = height, j.flags = flags;
+        raster::raster_visibility(j, visibility, command_base, stats, command_error);
+    });
+}
+
+int32_t orbit_host_visibility_resolve(const uint64_t *visibility, uint32_t width, uint32_t height, uint32_t command_base,
+                                      uint32_t max_commands, float *depth, uint32_t *command_pixels,
+                                      OrbitVisibilityStats *stats) {
+    return guarded([&] {
+        raster::visibility_resolve(visibility, width, height, command_base, max_commands, depth, command_pixels, stats);
+    });
+}
+
 // ---------------------------------------------------------------- asset ingestion (orbit_gltf.hpp), host only
 void *orbit_host_gltf_load(const char *path) {
     gltf_loader::LoadedScene *scene = nullptr;

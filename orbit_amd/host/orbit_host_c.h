@@ -230,6 +230,20 @@ int32_t orbit_host_raster_depth(const void *draw_commands, uint32_t max_commands
                                 uint32_t entity_count, const float view_proj[16], float *depth, uint32_t width,
                                 uint32_t height, uint32_t flags, OrbitRasterStats *stats, int32_t *command_error);
 
+/* the reference of orbit_raster_visibility (V1-V4): the arguments of orbit_host_raster_depth with the width * height u64
+ * `visibility` in place of depth, and command_base.  command_error also flags a command with nt > 256 (V3). */
+int32_t orbit_host_raster_visibility(const void *draw_commands, uint32_t max_commands, const uint32_t *meshlet_data,
+                                     uint64_t meshlet_data_words, const void *vertices, uint64_t vertex_count,
+                                     uint32_t vertex_stride, uint32_t position_offset, const OrbitEntityData *entity_data,
+                                     uint32_t entity_count, const float view_proj[16], uint64_t *visibility, uint32_t width,
+                                     uint32_t height, uint32_t flags, uint32_t command_base, OrbitRasterStats *stats,
+                                     int32_t *command_error);
+/* the reference of orbit_visibility_resolve: depth (width * height), command_pixels (max_commands) and stats may be NULL,
+ * not all three. */
+int32_t orbit_host_visibility_resolve(const uint64_t *visibility, uint32_t width, uint32_t height, uint32_t command_base,
+                                      uint32_t max_commands, float *depth, uint32_t *command_pixels,
+                                      OrbitVisibilityStats *stats);
+
 /* ---- asset ingestion (orbit_gltf.hpp): glTF 2.0 (.glb / .gltf) -> materials, meshes with their LOD chains, entities ----
  * load_gltf (gltf_loader.rs:511-676) + GpuAssets::add_mesh (assets/mod.rs:325-476).  NULL + orbit_host_last_error()
  * on failure.  The arrays stay valid until orbit_host_gltf_free. */

@@ -9,15 +9,41 @@
 namespace orbit {
 namespace raster {
 
-void raster_depth(const HostJob &j, OrbitRasterStats *stats, int32_t *command_error) {
-    if (!j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data || !j.depth || !j.view_proj)
+namespace {
+
+struct DepthSink { // R8: max on the u32 view
+    static constexpr uint32_t kMaxTriangles = ~0u;
+    float *depth;
+    void clear(size_t pixels) const { std::memset(depth, 0, pixels * sizeof(float)); }
+    void write(size_t pixel, uint32_t bits, uint32_t) const {
+        uint32_t old;
+        std::memcpy(&old, depth + pixel, 4);
+        if (bits > old) std::memcpy(depth + pixel, &bits, 4);
+    }
+};
+
+struct VisibilitySink { // V2: max on the u64 view of depth bits << 32 | id
+    static constexpr uint32_t kMaxTriangles = 256u; // V3
+    uint64_t *visibility;
+    void clear(size_t pixels) const { std::memset(visibility, 0, pixels * sizeof(uint64_t)); }
+    void write(size_t pixel, uint32_t bits, uint32_t id) const {
+        const uint64_t word = (uint64_t)bits << 32 | id;
+        if (word > visibility[pixel]) visibility[pixel] = word;
+    }
+};
+
+// the one sequential walk of both calls; id = (id_base + the command's position) << 8 | triangle
+template <class Sink>
+void raster_into(const HostJob &j, const Sink &sink, bool has_target, uint32_t id_base, OrbitRasterStats *stats,
+                 int32_t *command_error) {
+    if (!j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data || !has_target || !j.view_proj)
         throw Panic("raster_depth: NULL argument");
     if ((uint64_t)j.vertex_stride < (uint64_t)j.position_offset + 12u || (j.vertex_stride & 3u) || (j.position_offset & 3u))
         throw Panic("raster_depth: vertex_stride / position_offset");
     if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
         throw Panic("raster_depth: target size");
     if (j.flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE)) throw Panic("raster_depth: unknown flags");
-    if (j.flags & ORBIT_RASTER_CLEAR) std::memset(j.depth, 0, (size_t)j.width * j.height * sizeof(float));
+    if (j.flags & ORBIT_RASTER_CLEAR) sink.clear((size_t)j.width * j.height);
     OrbitRasterStats st{};
     const bool cull_none = (j.flags & ORBIT_RASTER_CULL_NONE) != 0u;
     const uint8_t *data_bytes = reinterpret_cast<const uint8_t *>(j.meshlet_data);
@@ -32,9 +58,10 @@ void raster_depth(const HostJob &j, OrbitRasterStats *stats, int32_t *command_er
         const uint32_t vcount = first_word - index_base;
         st.commands++;
         if (command_error) command_error[i] = 1;
-        // R9
+        // R9, V3
         bool bad = first_word < index_base || vcount > 255u || (uint64_t)first_word > j.meshlet_data_words ||
-                   ((uint64_t)first_index + 3ull * nt + 3ull) / 4ull > j.meshlet_data_words || entity >= j.entity_count;
+                   ((uint64_t)first_index + 3ull * nt + 3ull) / 4ull > j.meshlet_data_words || entity >= j.entity_count ||
+                   nt > Sink::kMaxTriangles;
         for (uint32_t v = 0; v < vcount && !bad; v++) bad = vertex_base + j.meshlet_data[index_base + v] >= j.vertex_count;
         for (uint64_t b = 0; b < 3ull * nt && !bad; b++) bad = data_bytes[first_index + b] >= vcount;
         if (bad) {
@@ -69,13 +96,50 @@ void raster_depth(const HostJob &j, OrbitRasterStats *stats, int32_t *command_er
                     const float d = depth_at(s, px, py);
                     if (!(d > 0.0f)) continue;
                     st.fragments++;
-                    uint32_t bits, old;
-                    float *dst = j.depth + (size_t)y * j.width + (uint32_t)x;
+                    uint32_t bits;
                     std::memcpy(&bits, &d, 4);
-                    std::memcpy(&old, dst, 4);
-                    if (bits > old) std::memcpy(dst, &bits, 4); // R8: max on the u32 view
+                    sink.write((size_t)y * j.width + (uint32_t)x, bits, (id_base + i) << 8 | t);
                 }
             if (inside == 0) st.no_coverage++;
+        }
+    }
+    if (stats) *stats = st;
+}
+
+} // namespace
+
+void raster_depth(const HostJob &j, OrbitRasterStats *stats, int32_t *command_error) {
+    raster_into(j, DepthSink{j.depth}, j.depth != nullptr, 0u, stats, command_error);
+}
+
+void raster_visibility(const HostJob &j, uint64_t *visibility, uint32_t command_base, OrbitRasterStats *stats,
+                       int32_t *command_error) {
+    if ((uint64_t)command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS) throw Panic("raster_visibility: command_base + max_commands");
+    raster_into(j, VisibilitySink{visibility}, visibility != nullptr, command_base, stats, command_error);
+}
+
+void visibility_resolve(const uint64_t *visibility, uint32_t width, uint32_t height, uint32_t command_base,
+                        uint32_t max_commands, float *depth, uint32_t *command_pixels, OrbitVisibilityStats *stats) {
+    if (!visibility) throw Panic("visibility_resolve: NULL argument");
+    if (!depth && !command_pixels && !stats) throw Panic("visibility_resolve: no output");
+    if (width == 0 || height == 0 || width > ORBIT_RASTER_MAX_DIM || height > ORBIT_RASTER_MAX_DIM)
+        throw Panic("visibility_resolve: target size");
+    if ((uint64_t)command_base + max_commands > ORBIT_VIS_MAX_COMMANDS) throw Panic("visibility_resolve: command_base + max_commands");
+    OrbitVisibilityStats st{};
+    if (command_pixels) std::memset(command_pixels, 0, (size_t)max_commands * 4);
+    for (size_t p = 0; p < (size_t)width * height; p++) {
+        const uint64_t word = visibility[p];
+        if (depth) {
+            const uint32_t bits = (uint32_t)(word >> 32);
+            std::memcpy(depth + p, &bits, 4);
+        }
+        if (word == 0) continue;
+        st.covered_pixels++;
+        const uint32_t id = (uint32_t)(word >> 8) & 0xFFFFFFu;
+        if (id < command_base || id - command_base >= max_commands) {
+            st.foreign_pixels++;
+        } else if (command_pixels && command_pixels[id - command_base]++ == 0) {
+            st.visible_commands++;
         }
     }
     if (stats) *stats = st;

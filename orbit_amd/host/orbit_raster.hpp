@@ -1,5 +1,6 @@
-// orbit_raster.hpp — host mirror of orbit_raster_depth (include/orbit_abi_ext.h R1-R9): the depth
-// prepass of a MeshletDrawCommandBuffer on HOST copies of the same buffers, sequential.  It is the reference of the GPU
+// orbit_raster.hpp — host mirror of orbit_raster_depth (include/orbit_abi_ext.h R1-R9), and of
+// orbit_raster_visibility and orbit_visibility_resolve (V1-V4, §4.13): the depth prepass of a
+// MeshletDrawCommandBuffer, and the same pass keeping the winner, on HOST copies of the same buffers, sequential.  It is the reference of the GPU
 // tests: the same depth bytes, the same counters, and a per-command flag where the device latches ORBIT_E_RANGE.  The
 // arithmetic (transform, snap, setup, edge functions, depth plane) is ../csrc/raster_common.h, shared with the kernel;
 // this side evaluates every edge function at every sample of a triangle's box directly, command after command.
@@ -29,6 +30,14 @@ struct HostJob {
 // Throws Panic for what the device call answers with ORBIT_E_INVALID.  stats and command_error (min(count,
 // max_commands) flags, 1 = skipped by a range check) may be null.
 void raster_depth(const HostJob &job, OrbitRasterStats *stats, int32_t *command_error);
+
+// The same walk into width * height u64 words (V2); job.depth is not read.  command_error also flags V3's nt > 256.
+void raster_visibility(const HostJob &job, uint64_t *visibility, uint32_t command_base, OrbitRasterStats *stats,
+                       int32_t *command_error);
+
+// orbit_visibility_resolve on a host buffer; depth, command_pixels (max_commands words) and stats may be null, not all.
+void visibility_resolve(const uint64_t *visibility, uint32_t width, uint32_t height, uint32_t command_base,
+                        uint32_t max_commands, float *depth, uint32_t *command_pixels, OrbitVisibilityStats *stats);
 
 } // namespace raster
 } // namespace orbit

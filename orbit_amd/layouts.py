@@ -58,6 +58,8 @@ MESH_BOUNDS_RANGE = np.dtype([("mesh_index", "<u4"), ("first_vertex", "<u4"), ("
 # OrbitRasterStats: the counters of orbit_raster_depth
 RASTER_STATS = np.dtype([(n, "<u4") for n in ("commands", "triangles", "clip_skipped", "guard_skipped", "back_facing",
                                               "no_coverage", "fragments", "range_errors")])
+# OrbitVisibilityStats: the counters of orbit_visibility_resolve
+VIS_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "visible_commands", "foreign_pixels", "_pad")])
 # types.glsl:92-110, src/assets/mod.rs:171-191
 MATERIAL = np.dtype([
     ("base_color", "<f4", (4,)), ("emissive_factor", "<f4", (3,)), ("metallic_factor", "<f4"),

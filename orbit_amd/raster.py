@@ -1,5 +1,7 @@
-"""ctypes binding of the host mirror of ``orbit_raster_depth`` (``orbit_amd/host/orbit_raster.hpp``): the depth prepass
-of a MeshletDrawCommandBuffer on host arrays, the reference of ``Engine.raster_depth``.  Python adds nothing; host only."""
+"""ctypes binding of the host mirror of ``orbit_raster_depth``, ``orbit_raster_visibility`` and
+``orbit_visibility_resolve`` (``orbit_amd/host/orbit_raster.hpp``): the depth prepass of a MeshletDrawCommandBuffer on
+host arrays, the same pass keeping the winner's identity and its resolve — the references of ``Engine.raster_depth``,
+``Engine.raster_visibility`` and ``Engine.visibility_resolve``.  Python adds nothing; host only."""
 import ctypes as C
 
 import numpy as np
@@ -53,3 +55,52 @@ def host_raster_depth(draw_commands, max_commands, meshlet_data, vertices, verte
                                          C.c_uint32((CLEAR if clear else 0) | (CULL_NONE if cull_none else 0)), p(stats),
                                          p(err)))
     return out, stats[0], err
+
+
+def host_raster_visibility(draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, view_proj,
+                           width, height, visibility=None, command_base=0, clear=True, cull_none=False, vertex_stride=12,
+                           position_offset=0, entity_count=None, meshlet_data_words=None):
+    """orbit_host_raster_visibility on host arrays -> (visibility: np.uint64 (height, width), stats:
+    np[layouts.RASTER_STATS] scalar row, command_error: np.int32 per processed command).  The arguments are
+    host_raster_depth's; `visibility`: the buffer to merge into (copied); None needs clear=True."""
+    buf = np.ascontiguousarray(draw_commands).view(np.uint8).reshape(-1)
+    if buf.nbytes < 4 + 28 * int(max_commands):
+        raise ValueError("max_commands reaches beyond the command array")
+    data = np.ascontiguousarray(meshlet_data, dtype=np.uint32).reshape(-1)
+    vb = np.ascontiguousarray(vertices).view(np.uint8).reshape(-1)
+    if int(vertex_count) and (int(vertex_count) - 1) * int(vertex_stride) + int(position_offset) + 12 > vb.nbytes:
+        raise ValueError("vertex_count reaches beyond the vertex array")
+    ent = np.ascontiguousarray(entity_data).view(np.uint8).reshape(-1)
+    entity_count = ent.nbytes // 128 if entity_count is None else int(entity_count)
+    words = len(data) if meshlet_data_words is None else int(meshlet_data_words)
+    if visibility is None:
+        if not clear:
+            raise ValueError("no buffer to merge into")
+        out = np.zeros((height, width), np.uint64)
+    else:
+        out = np.array(visibility, dtype=np.uint64, order="C").reshape(height, width)
+    n = min(int(buf[:4].view(np.uint32)[0]), int(max_commands))
+    stats, err = np.zeros(1, L.RASTER_STATS), np.zeros(n, np.int32)
+    vp = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(lib().orbit_host_raster_visibility(p(buf), C.c_uint32(max_commands), p(data), C.c_uint64(words), p(vb),
+                                              C.c_uint64(vertex_count), C.c_uint32(vertex_stride),
+                                              C.c_uint32(position_offset), p(ent), C.c_uint32(entity_count), vp, p(out),
+                                              C.c_uint32(width), C.c_uint32(height),
+                                              C.c_uint32((CLEAR if clear else 0) | (CULL_NONE if cull_none else 0)),
+                                              C.c_uint32(command_base), p(stats), p(err)))
+    return out, stats[0], err
+
+
+def host_visibility_resolve(visibility, command_base=0, max_commands=0, want_command_pixels=True):
+    """orbit_host_visibility_resolve on a (height, width) np.uint64 buffer -> (depth: np.float32 (height, width),
+    command_pixels: np.uint32[max_commands] or None, stats: np[layouts.VIS_STATS] scalar row)."""
+    vis = np.ascontiguousarray(visibility, dtype=np.uint64)
+    height, width = vis.shape
+    depth = np.zeros((height, width), np.float32)
+    pixels = np.zeros(max(int(max_commands), 1), np.uint32) if want_command_pixels else None
+    stats = np.zeros(1, L.VIS_STATS)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(lib().orbit_host_visibility_resolve(p(vis), C.c_uint32(width), C.c_uint32(height), C.c_uint32(command_base),
+                                               C.c_uint32(max_commands), p(depth), p(pixels), p(stats)))
+    return depth, None if pixels is None else pixels[:int(max_commands)], stats[0]
