@@ -392,15 +392,17 @@ def meshlet_cull(ci, records, meshlets, entities, materials, mvis, pyr=None, pyr
     cmds["cmd_first_instance"] = rec["entity_index"][should]
     cmds["meshlet_vertex_offset"] = ms["vertex_offset"]
     cmds["meshlet_index"] = idx[should].astype(np.uint32)
+    if detail is not None:  # per active lane: its record, its lane, its verdict
+        detail.update(record=rid, lane=lane, should_draw=should)
     new = None
     if op == 2 and meshlet_occ:
+        # every word an active lane lies in is REPLACED by the visible bits of its lanes
         new = mvis.copy()
-        words = {}
-        for ri, ln, vb in zip(rid, lane, visible):
-            w = int(records["visibility_offset"][ri]) + ln // 32
-            words[w] = words.get(w, 0) | (int(vb) << (ln % 32))
-        for w, val in words.items():
-            new[w] = val
+        w = rec["visibility_offset"].astype(np.int64) + lane // 32
+        acc = np.zeros(len(new), dtype=np.uint32)
+        np.bitwise_or.at(acc, w, visible.astype(np.uint32) << (lane % 32).astype(np.uint32))
+        touched = np.unique(w)
+        new[touched] = acc[touched]
     return cmds, new
 
 
