@@ -106,12 +106,7 @@ VIS_MAX_COMMANDS = 1 << 24             # ORBIT_VIS_MAX_COMMANDS
 
 
 class RasterVisibility(C.Structure):  # OrbitRasterVisibility: RasterDepth with visibility for depth, command_base for _pad
-    _fields_ = [("draw_commands", C.c_void_p), ("meshlet_data", C.c_void_p), ("vertices", C.c_void_p),
-                ("entity_data", C.c_void_p), ("visibility", C.c_void_p), ("stats", C.c_void_p),
-                ("meshlet_data_words", C.c_uint64), ("vertex_count", C.c_uint64), ("max_commands", C.c_uint32),
-                ("entity_count", C.c_uint32), ("vertex_stride", C.c_uint32), ("position_offset", C.c_uint32),
-                ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("command_base", C.c_uint32),
-                ("view_proj", C.c_float * 16)]
+    _fields_ = [({"depth": "visibility", "_pad": "command_base"}.get(name, name), kind) for name, kind in RasterDepth._fields_]
 
 
 class VisibilityResolve(C.Structure):  # OrbitVisibilityResolve

@@ -14,6 +14,21 @@ int32_t check_vertex_layout(OrbitCtx *ctx, const char *who, uint32_t stride, uin
     return ORBIT_OK;
 }
 
+// what orbit_raster_depth and orbit_raster_visibility (`who`) check alike; the target buffer is the caller's to check
+int32_t check_raster_job(OrbitCtx *ctx, const char *who, uint32_t flags, uint32_t vertex_stride, uint32_t position_offset,
+                         uint32_t width, uint32_t height, const void *draw_commands, const void *meshlet_data,
+                         const void *vertices, const void *entity_data, const void *stats) {
+    if (flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE)) return fail(ctx, ORBIT_E_INVALID, "%s: flags %#x", who, flags);
+    if (const int32_t rc = check_vertex_layout(ctx, who, vertex_stride, position_offset)) return rc;
+    if (width == 0 || height == 0 || width > ORBIT_RASTER_MAX_DIM || height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "%s: target %u x %u (1..%u each)", who, width, height, ORBIT_RASTER_MAX_DIM);
+    if (!draw_commands || !meshlet_data || !vertices || !entity_data) return fail(ctx, ORBIT_E_INVALID, "%s: NULL buffer", who);
+    if ((((uintptr_t)draw_commands | (uintptr_t)meshlet_data | (uintptr_t)vertices | (uintptr_t)stats) & 3u) ||
+        ((uintptr_t)entity_data & 15u))
+        return fail(ctx, ORBIT_E_INVALID, "%s: every buffer must be 4-B aligned, entity_data 16-B aligned", who);
+    return ORBIT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -69,16 +84,10 @@ int32_t orbit_raster_depth(OrbitCtx *ctx, const OrbitRasterDepth *job, void *str
     if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
     if (!job) return fail(ctx, ORBIT_E_INVALID, "raster_depth: job is NULL");
     const OrbitRasterDepth &j = *job;
-    if (j.flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE))
-        return fail(ctx, ORBIT_E_INVALID, "raster_depth: flags %#x", j.flags);
-    if (const int32_t rc = check_vertex_layout(ctx, "raster_depth", j.vertex_stride, j.position_offset)) return rc;
-    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
-        return fail(ctx, ORBIT_E_INVALID, "raster_depth: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
-    if (!j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data || !j.depth)
-        return fail(ctx, ORBIT_E_INVALID, "raster_depth: NULL buffer");
-    if ((((uintptr_t)j.draw_commands | (uintptr_t)j.meshlet_data | (uintptr_t)j.vertices | (uintptr_t)j.depth |
-          (uintptr_t)j.stats) & 3u) || ((uintptr_t)j.entity_data & 15u))
-        return fail(ctx, ORBIT_E_INVALID, "raster_depth: every buffer must be 4-B aligned, entity_data 16-B aligned");
+    if (const int32_t rc = check_raster_job(ctx, "raster_depth", j.flags, j.vertex_stride, j.position_offset, j.width, j.height,
+                                            j.draw_commands, j.meshlet_data, j.vertices, j.entity_data, j.stats))
+        return rc;
+    if (!j.depth || ((uintptr_t)j.depth & 3u)) return fail(ctx, ORBIT_E_INVALID, "raster_depth: depth is NULL or not 4-B aligned");
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_raster_depth(j, ctx->raster_blocks, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_depth");
@@ -91,20 +100,14 @@ int32_t orbit_raster_visibility(OrbitCtx *ctx, const OrbitRasterVisibility *job,
     if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
     if (!job) return fail(ctx, ORBIT_E_INVALID, "raster_visibility: job is NULL");
     const OrbitRasterVisibility &j = *job;
-    if (j.flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE))
-        return fail(ctx, ORBIT_E_INVALID, "raster_visibility: flags %#x", j.flags);
-    if (const int32_t rc = check_vertex_layout(ctx, "raster_visibility", j.vertex_stride, j.position_offset)) return rc;
-    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
-        return fail(ctx, ORBIT_E_INVALID, "raster_visibility: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if (const int32_t rc = check_raster_job(ctx, "raster_visibility", j.flags, j.vertex_stride, j.position_offset, j.width,
+                                            j.height, j.draw_commands, j.meshlet_data, j.vertices, j.entity_data, j.stats))
+        return rc;
     if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS)
         return fail(ctx, ORBIT_E_INVALID, "raster_visibility: command_base %u + max_commands %u > %u (24 bits of id)",
                     j.command_base, j.max_commands, ORBIT_VIS_MAX_COMMANDS);
-    if (!j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data || !j.visibility)
-        return fail(ctx, ORBIT_E_INVALID, "raster_visibility: NULL buffer");
-    if ((((uintptr_t)j.draw_commands | (uintptr_t)j.meshlet_data | (uintptr_t)j.vertices | (uintptr_t)j.stats) & 3u) ||
-        ((uintptr_t)j.entity_data & 15u) || ((uintptr_t)j.visibility & 7u))
-        return fail(ctx, ORBIT_E_INVALID,
-                    "raster_visibility: every buffer must be 4-B aligned, visibility 8-B, entity_data 16-B aligned");
+    if (!j.visibility || ((uintptr_t)j.visibility & 7u))
+        return fail(ctx, ORBIT_E_INVALID, "raster_visibility: visibility is NULL or not 8-B aligned");
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_raster_visibility(j, ctx->visibility_blocks, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_visibility");

@@ -370,7 +370,8 @@ hipError_t launch_mesh_bounds(const OrbitMeshBoundsRange *ranges, uint32_t range
                               uint32_t position_offset, OrbitMeshInfo *mesh_infos, uint32_t mesh_capacity, float *scratch,
                               int32_t *status, hipStream_t s);
 // raster_depth.hip: orbit_raster_depth — `job` validated by the entry point; one launch clears depth
-// (ORBIT_RASTER_CLEAR) and stats, the next reads the command count on the device and draws
+// (ORBIT_RASTER_CLEAR) and stats, the next reads the command count on the device and draws (raster_walk.h: one walker
+// and one launch, which raster_depth.hip and raster_visibility.hip give a sink each)
 hipError_t launch_raster_depth(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
 // ... its workgroups that one CU holds at once (asked of the runtime once, when a context is created)
 uint32_t raster_depth_blocks_per_cu();

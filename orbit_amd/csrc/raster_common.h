@@ -1,5 +1,5 @@
 // raster_common.h — the arithmetic of orbit_raster_depth (include/orbit_abi_ext.h R2-R7), written once
-// for the device kernel (raster_depth.hip) and the host mirror (orbit_amd/host/orbit_raster.cpp): the vertex transform
+// for the device kernels (raster_walk.h) and the host mirror (orbit_amd/host/orbit_raster.cpp): the vertex transform
 // and snap, the triangle setup with its rejects, the edge functions and the depth plane.  Both translation units are
 // built with -ffp-contract=off and correctly rounded divides; every product and sum below is rounded on its own, in
 // the order written.  What the two sides do NOT share is how they walk the pixels: the host evaluates every edge

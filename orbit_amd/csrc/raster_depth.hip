@@ -1,199 +1,35 @@
 // raster_depth.hip — orbit_raster_depth (include/orbit_abi_ext.h): the reference's depth prepass
 // (forward_depth_prepass.mesh / .vert + fixed-function raster, forward.rs:300-356) in compute, from the draw commands
-// the meshlet cull wrote.  The arithmetic is raster_common.h's, shared with the host mirror, which is the pin: the
-// depth bytes and the counters equal orbit_host_raster_depth's for every input.
+// the meshlet cull wrote.  The host mirror is the pin: the depth bytes and the counters equal orbit_host_raster_depth's
+// for every input.
 //
-// A grid of as many wave64s as are resident at once (or fewer); a wave takes one command (= one meshlet of one entity) at a time.
-//   phase 1  the wave checks the command's ranges (R9) — nothing is read before its index is known to be in range —,
-//            computes mvp = view_proj x model, and its lanes transform the <= 255 vertices into LDS: snapped X, Y, z / w
-//            and the clip / guard flags, 16 B per vertex
-//   phase 2  a lane per triangle (chunks of 64): setup and the rejects of R3-R5, counted per lane and summed once per
-//            wave when it runs out of commands
-//   phase 3  a triangle whose pixel box holds at most kLaneBox samples is walked by its own lane (most are: two thirds
-//            of the front faces of the test scene cover no sample at all); a larger one is taken by the whole wave, one
-//            at a time (ballot, the corners broadcast, every lane repeats the setup, lanes take the 8 x 8 tiles of the
-//            box).  Edge functions are stepped in int64, the same integers as evaluating them per sample.
-// Depth is written by atomicMax on the u32 view (positive floats order as their bits), behind a relaxed atomic load that skips
-// the atomic where the buffer already holds as much: the buffer only grows, so a stale smaller value costs an atomic,
-// never a pixel.  The result does not depend on scheduling or command order.
-#include "kernels.h"
-#include "orbit_device.h"
-#include "raster_common.h"
+// The raster kernel is the walker of raster_walk.h over a sink that writes depth by atomicMax on the u32 view (positive
+// floats order as their bits), behind a relaxed atomic load that skips the atomic where the buffer already holds as
+// much: the buffer only grows, so a stale smaller value costs an atomic, never a pixel.
+#include "raster_walk.h"
 
 namespace orbit {
 namespace {
 
 using namespace raster;
 
-constexpr uint32_t kRasterThreads = 256, kRasterWaves = kRasterThreads / 64;
-constexpr uint32_t kMaxVertices = 256; // vcount <= 255 (R9)
-constexpr int32_t kLaneBox = 16; // samples: a box no larger is walked by the triangle's own lane (not yet tuned)
-
-struct RasterParams {
-    const uint32_t *commands; // {count; 7 words per command}
-    const uint32_t *meshlet_data;
-    const uint8_t *vertices;
-    const float *entity_data; // 32 floats per entity, the model matrix first
+// R7, R8 of one inside sample -> it is a fragment (d > 0)
+struct DepthSink {
+    static constexpr uint32_t kMaxTriangles = ~0u; // no limit: the depth word carries no triangle index
     uint32_t *depth;
-    uint32_t *stats;
-    uint64_t meshlet_data_words, vertex_count;
-    uint32_t max_commands, entity_count, vertex_stride, position_offset, width, height, flags;
-    float view_proj[16];
-    int32_t *status;
+    __device__ __forceinline__ bool write(const Setup &s, int32_t x, int32_t y, uint32_t width, uint32_t /*id*/) const {
+        const float d = depth_at(s, 256 * x + 128, 256 * y + 128);
+        if (!(d > 0.0f)) return false;
+        const uint32_t bits = __float_as_uint(d);
+        uint32_t *dst = depth + (size_t)y * width + (uint32_t)x;
+        // (a relaxed load beside the other waves' atomics: a stale value is a smaller one and costs an atomic, never a pixel)
+        if (bits > __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(dst, bits);
+        return true;
+    }
 };
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ Vertex lds_vertex(const int4 *verts, uint32_t i) {
-    const int4 w = verts[i];
-    Vertex v;
-    v.X = w.x, v.Y = w.y, v.d = __int_as_float(w.z), v.flags = (uint32_t)w.w;
-    return v;
-}
-
-// R7, R8 of one inside sample -> it is a fragment (d > 0)
-__device__ __forceinline__ bool write_sample(const RasterParams &p, const Setup &s, int32_t x, int32_t y) {
-    const float d = depth_at(s, 256 * x + 128, 256 * y + 128);
-    if (!(d > 0.0f)) return false;
-    const uint32_t bits = __float_as_uint(d);
-    uint32_t *dst = p.depth + (size_t)y * p.width + (uint32_t)x;
-    // (a relaxed load beside the other waves' atomics: a stale value is a smaller one and costs an atomic, never a pixel)
-    if (bits > __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(dst, bits);
-    return true;
-}
-
-// The samples (x_lo + x0 + k * step_x, y_lo + y0 + j * step_y) of the triangle's box: the lane path takes all of them
-// (x0 = y0 = 0, steps of 1), a lane of the wave path its own sample of every 8 x 8 tile.  -> inside samples; fragments
-// are added to `fragments`.
-__device__ __forceinline__ uint32_t walk(const RasterParams &p, const Setup &s, int32_t x0, int32_t y0, int32_t step,
-                                         uint32_t &fragments) {
-    uint32_t inside = 0;
-    const int64_t sx0 = -(int64_t)s.dy[0] * 256 * step, sx1 = -(int64_t)s.dy[1] * 256 * step,
-                  sx2 = -(int64_t)s.dy[2] * 256 * step; // E(px + 256 step) - E(px)
-    for (int32_t y = s.y_lo + y0; y <= s.y_hi; y += step) {
-        const int32_t x = s.x_lo + x0, py = 256 * y + 128;
-        int64_t e0 = edge_at(s, 0, 256 * x + 128, py), e1 = edge_at(s, 1, 256 * x + 128, py),
-                e2 = edge_at(s, 2, 256 * x + 128, py);
-        for (int32_t xx = x; xx <= s.x_hi; xx += step) {
-            if ((e0 | e1 | e2) >= 0) {
-                inside++;
-                fragments += write_sample(p, s, xx, y) ? 1u : 0u;
-            }
-            e0 += sx0, e1 += sx1, e2 += sx2;
-        }
-    }
-    return inside;
-}
-
-// depth[0, words) = 0.0f and, if given, the eight counters = 0
-__global__ __launch_bounds__(kRasterThreads) void raster_clear_kernel(uint32_t *depth, uint64_t words, uint32_t *stats) {
-    const uint64_t stride = (uint64_t)gridDim.x * kRasterThreads;
-    for (uint64_t i = (uint64_t)blockIdx.x * kRasterThreads + threadIdx.x; i < words; i += stride) depth[i] = 0u;
-    if (stats && blockIdx.x == 0u && threadIdx.x < 8u) stats[threadIdx.x] = 0u;
-}
-
-__global__ __launch_bounds__(kRasterThreads) void raster_depth_kernel(const RasterParams p) {
-    __shared__ int4 lds_verts[kRasterWaves][kMaxVertices];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    int4 *verts = lds_verts[wave];
-    const uint8_t *data_bytes = (const uint8_t *)p.meshlet_data;
-    const uint32_t listed = p.commands[0];
-    const uint32_t count = listed < p.max_commands ? listed : p.max_commands;
-    const bool cull_none = (p.flags & ORBIT_RASTER_CULL_NONE) != 0u;
-    const float w_f = (float)p.width, h_f = (float)p.height;
-    // this lane's share of the counters, OrbitRasterStats' order
-    uint32_t n_commands = 0, n_triangles = 0, n_outcome[5] = {0, 0, 0, 0, 0}, n_fragments = 0, n_range = 0;
-    const uint32_t stride = gridDim.x * kRasterWaves;
-    if (blockIdx.x * kRasterWaves + wave >= count) return; // (wave-uniform) no command for this wave: nothing to add
-    for (uint32_t i = blockIdx.x * kRasterWaves + wave; i < count; i += stride) {
-        const uint32_t *cmd = p.commands + 1u + 7u * (size_t)i;
-        const uint32_t index_count = cmd[0], first_index = cmd[2], index_base = cmd[3], entity = cmd[4];
-        const uint64_t vertex_base = cmd[5];
-        const uint32_t nt = index_count / 3u, first_word = first_index / 4u;
-        const uint32_t vcount = first_word - index_base; // (meaningful once first_word >= index_base)
-        if (lane == 0u) n_commands++;
-        // R9, the wave-uniform part: the index words [index_base, first_word) and the corner bytes lie in meshlet_data
-        bool bad = first_word < index_base || vcount > 255u || (uint64_t)first_word > p.meshlet_data_words ||
-                   ((uint64_t)first_index + 3ull * nt + 3ull) / 4ull > p.meshlet_data_words || entity >= p.entity_count;
-        if (!bad) {
-            float mvp[16];
-            {
-                const float *model = p.entity_data + 32u * (size_t)entity;
-                float m[16];
-                for (int k = 0; k < 16; k++) m[k] = model[k];
-                mat4_mul(p.view_proj, m, mvp);
-            }
-            bool lane_bad = false;
-            for (uint32_t v = lane; v < vcount; v += 64u) {
-                const uint64_t g = vertex_base + p.meshlet_data[index_base + v];
-                Vertex out;
-                out.X = out.Y = 0, out.d = 0.f, out.flags = kClipFail;
-                if (g < p.vertex_count) {
-                    const float *src = (const float *)(p.vertices + g * p.vertex_stride + p.position_offset);
-                    out = transform_vertex(mvp, src[0], src[1], src[2], w_f, h_f);
-                } else {
-                    lane_bad = true;
-                }
-                verts[v] = make_int4(out.X, out.Y, __float_as_int(out.d), (int)out.flags);
-            }
-            for (uint32_t t = lane; t < nt; t += 64u) {
-                const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
-                if (c[0] >= vcount || c[1] >= vcount || c[2] >= vcount) lane_bad = true;
-            }
-            bad = __ballot(lane_bad) != 0ull;
-        }
-        if (bad) { // the command is skipped whole
-            if (lane == 0u) {
-                n_range++;
-                latch_status(p.status, ORBIT_E_RANGE);
-            }
-            continue;
-        }
-        if (lane == 0u) n_triangles += nt;
-        wave_lds_sync();
-        for (uint32_t base = 0; base < nt; base += 64u) {
-            const uint32_t t = base + lane;
-            Setup s;
-            uint32_t corners = 0;
-            bool draw = false;
-            if (t < nt) {
-                const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
-                corners = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
-                const uint32_t outcome = setup_triangle(lds_vertex(verts, c[0]), lds_vertex(verts, c[1]),
-                                                        lds_vertex(verts, c[2]), p.width, p.height, cull_none, s);
-                for (uint32_t k = 1; k < 5u; k++) n_outcome[k] += outcome == k ? 1u : 0u;
-                draw = outcome == kDraw;
-            }
-            // (boxes are at most 32768^2 samples: the product fits)
-            const bool small = draw && (s.x_hi - s.x_lo + 1) * (s.y_hi - s.y_lo + 1) <= kLaneBox;
-            if (small && walk(p, s, 0, 0, 1, n_fragments) == 0u) n_outcome[kNoCoverage]++;
-            uint64_t large = __ballot(draw && !small);
-            while (large != 0ull) {
-                const uint32_t src = (uint32_t)__builtin_ctzll(large);
-                large &= large - 1ull;
-                const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)corners, (int)src);
-                Setup ws;
-                (void)setup_triangle(lds_vertex(verts, c & 0xFFu), lds_vertex(verts, (c >> 8) & 0xFFu),
-                                     lds_vertex(verts, c >> 16), p.width, p.height, cull_none, ws);
-                const uint32_t inside = walk(p, ws, (int32_t)(lane & 7u), (int32_t)(lane >> 3), 8, n_fragments);
-                if (__ballot(inside != 0u) == 0ull && lane == 0u) n_outcome[kNoCoverage]++;
-            }
-        }
-        wave_lds_sync(); // the next command overwrites the wave's vertices
-    }
-    if (!p.stats) return;
-    uint32_t sums[8] = {n_commands,           n_triangles,           n_outcome[kClipSkipped], n_outcome[kGuardSkipped],
-                        n_outcome[kBackFacing], n_outcome[kNoCoverage], n_fragments,            n_range};
-    for (uint32_t k = 0; k < 8u; k++) {
-        uint32_t v = sums[k];
-        for (uint32_t d = 1; d < 64u; d <<= 1) v += (uint32_t)__shfl_xor((int)v, (int)d, 64);
-        if (lane == 0u && v != 0u) atomicAdd(&p.stats[k], v);
-    }
+__global__ __launch_bounds__(kRasterThreads) void raster_depth_kernel(const RasterParams p, uint32_t *const depth) {
+    raster_commands(p, DepthSink{depth}, 0u);
 }
 
 } // namespace
@@ -205,38 +41,7 @@ uint32_t raster_depth_blocks_per_cu() {
 }
 
 hipError_t launch_raster_depth(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
-    // LoadOp::Clear(0.0) and the counters' clear are a launch of this unit, not memset nodes: a captured call then
-    // consists of kernel nodes only, whose arguments a replay carries by value
-    const uint64_t clear_words = (job.flags & ORBIT_RASTER_CLEAR) ? (uint64_t)job.width * job.height : 0ull;
-    if (clear_words != 0ull || job.stats) {
-        const uint64_t need = (clear_words + kRasterThreads * 4ull - 1ull) / (kRasterThreads * 4ull);
-        const uint64_t cap = resident_blocks ? resident_blocks : 512u;
-        const uint32_t blocks = (uint32_t)(need < 1ull ? 1ull : need < cap ? need : cap);
-        hipLaunchKernelGGL(raster_clear_kernel, dim3(blocks), dim3(kRasterThreads), 0, s, (uint32_t *)job.depth, clear_words,
-                           (uint32_t *)job.stats);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    if (job.max_commands == 0u) return hipSuccess;
-    RasterParams p;
-    p.commands = (const uint32_t *)job.draw_commands;
-    p.meshlet_data = job.meshlet_data;
-    p.vertices = (const uint8_t *)job.vertices;
-    p.entity_data = (const float *)job.entity_data;
-    p.depth = (uint32_t *)job.depth;
-    p.stats = (uint32_t *)job.stats;
-    p.meshlet_data_words = job.meshlet_data_words, p.vertex_count = job.vertex_count;
-    p.max_commands = job.max_commands, p.entity_count = job.entity_count;
-    p.vertex_stride = job.vertex_stride, p.position_offset = job.position_offset;
-    p.width = job.width, p.height = job.height, p.flags = job.flags;
-    for (int k = 0; k < 16; k++) p.view_proj[k] = job.view_proj[k];
-    p.status = status;
-    // the count is the device's: the grid covers max_commands, up to as many workgroups as are resident at once (the
-    // kernel's registers decide how many per CU), which stride over the list
-    const uint32_t need = (job.max_commands + kRasterWaves - 1u) / kRasterWaves;
-    const uint32_t cap = resident_blocks ? resident_blocks : 512u;
-    hipLaunchKernelGGL(raster_depth_kernel, dim3(need < cap ? need : cap), dim3(kRasterThreads), 0, s, p);
-    return hipGetLastError();
+    return launch_raster(raster_depth_kernel, job, (uint32_t *)job.depth, resident_blocks, status, s, (uint32_t *)job.depth);
 }
 
 } // namespace orbit

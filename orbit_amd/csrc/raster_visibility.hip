@@ -34,14 +34,6 @@ struct VisibilitySink {
     }
 };
 
-// visibility[0, words) = 0 and, if given, the eight counters = 0
-__global__ __launch_bounds__(kRasterThreads) void visibility_clear_kernel(unsigned long long *visibility, uint64_t words,
-                                                                          uint32_t *stats) {
-    const uint64_t stride = (uint64_t)gridDim.x * kRasterThreads;
-    for (uint64_t i = (uint64_t)blockIdx.x * kRasterThreads + threadIdx.x; i < words; i += stride) visibility[i] = 0ull;
-    if (stats && blockIdx.x == 0u && threadIdx.x < 8u) stats[threadIdx.x] = 0u;
-}
-
 __global__ __launch_bounds__(kRasterThreads) void raster_visibility_kernel(const RasterParams p, const VisibilitySink sink,
                                                                            const uint32_t command_base) {
     raster_commands(p, sink, command_base);
@@ -102,28 +94,8 @@ uint32_t raster_visibility_blocks_per_cu() {
 }
 
 hipError_t launch_raster_visibility(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
-    // the clears are a launch of this unit, not memset nodes: a captured call consists of kernel nodes only
-    const uint64_t clear_words = (job.flags & ORBIT_RASTER_CLEAR) ? (uint64_t)job.width * job.height : 0ull;
-    const uint64_t cap = resident_blocks ? resident_blocks : 512u;
-    if (clear_words != 0ull || job.stats) {
-        const uint64_t need = (clear_words + kRasterThreads * 4ull - 1ull) / (kRasterThreads * 4ull);
-        const uint32_t blocks = (uint32_t)(need < 1ull ? 1ull : need < cap ? need : cap);
-        hipLaunchKernelGGL(visibility_clear_kernel, dim3(blocks), dim3(kRasterThreads), 0, s,
-                           (unsigned long long *)job.visibility, clear_words, (uint32_t *)job.stats);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    if (job.max_commands == 0u) return hipSuccess;
-    RasterParams p;
-    fill_raster_params(p, job.draw_commands, job.meshlet_data, job.vertices, job.entity_data, job.stats, job.meshlet_data_words,
-                       job.vertex_count, job.max_commands, job.entity_count, job.vertex_stride, job.position_offset,
-                       job.width, job.height, job.flags, job.view_proj, status);
-    const VisibilitySink sink{(unsigned long long *)job.visibility};
-    // the count is the device's: the grid covers max_commands, up to as many workgroups as are resident at once
-    const uint64_t need = ((uint64_t)job.max_commands + kRasterWaves - 1u) / kRasterWaves;
-    hipLaunchKernelGGL(raster_visibility_kernel, dim3((uint32_t)(need < cap ? need : cap)), dim3(kRasterThreads), 0, s, p, sink,
-                       job.command_base);
-    return hipGetLastError();
+    return launch_raster(raster_visibility_kernel, job, (unsigned long long *)job.visibility, resident_blocks, status, s,
+                         VisibilitySink{(unsigned long long *)job.visibility}, job.command_base);
 }
 
 hipError_t launch_visibility_resolve(const OrbitVisibilityResolve &job, uint32_t num_cus, hipStream_t s) {

@@ -1,11 +1,23 @@
-// raster_walk.h — the walker of the compute rasteriser as a template on the SINK that takes an inside sample: the
-// command loop, the vertex phase, the per-lane triangle setup and the lane / wave walks of DESIGN.md §4.12.  A sink has
+// raster_walk.h — the compute rasteriser of DESIGN.md §4.12 / §4.13, the one owner of its walker: a template on the SINK
+// that takes an inside sample, with the clear kernel and the launch that every raster call shares.  raster_depth.hip and
+// raster_visibility.hip add a sink and a one-line kernel each.  The arithmetic is raster_common.h's, shared with the
+// host mirror, which is the pin.
+//
+// A grid of as many wave64s as are resident at once (or fewer); a wave takes one command (= one meshlet of one entity) at a time.
+//   phase 1  the wave checks the command's ranges (R9, and the sink's triangle limit) — nothing is read before its index
+//            is known to be in range —, computes mvp = view_proj x model, and its lanes transform the <= 255 vertices into
+//            LDS: snapped X, Y, z / w and the clip / guard flags, 16 B per vertex
+//   phase 2  a lane per triangle (chunks of 64): setup and the rejects of R3-R5, counted per lane and summed once per
+//            wave when it runs out of commands
+//   phase 3  a triangle whose pixel box holds at most kLaneBox samples is walked by its own lane (most are: two thirds
+//            of the front faces of the test scene cover no sample at all); a larger one is taken by the whole wave, one
+//            at a time (ballot, the corners broadcast, every lane repeats the setup, lanes take the 8 x 8 tiles of the
+//            box).  Edge functions are stepped in int64, the same integers as evaluating them per sample.
+// A sink has
 //   static constexpr uint32_t kMaxTriangles   a command with more triangles is a range error (V3); ~0u: no limit
 //   bool write(const Setup &, x, y, width, id) const   R7 + the merge of one inside sample -> it is a fragment (d > 0)
-// where id = (id_base + the command's position) << 8 | triangle index.  raster_visibility.hip instantiates it.
-// raster_depth.hip still carries the copy this was lifted from: instantiated from here its kernel is allocated 149
-// VGPRs instead of 154 — a different schedule, which has to be timed on the device before it replaces a pinned kernel
-// (DESIGN.md §4.13).  Until then a change to the walk is made in both places.  The arithmetic is raster_common.h's.
+// where id = (id_base + the command's position) << 8 | triangle index.  Both sinks merge by atomicMax: the result does
+// not depend on scheduling or command order.
 #pragma once
 #include "kernels.h"
 #include "orbit_device.h"
@@ -30,20 +42,19 @@ struct RasterParams { // what the walker reads; the target belongs to the sink
     int32_t *status;
 };
 
-inline void fill_raster_params(RasterParams &p, const void *draw_commands, const uint32_t *meshlet_data, const void *vertices,
-                               const void *entity_data, void *stats, uint64_t meshlet_data_words, uint64_t vertex_count,
-                               uint32_t max_commands, uint32_t entity_count, uint32_t vertex_stride, uint32_t position_offset,
-                               uint32_t width, uint32_t height, uint32_t flags, const float *view_proj, int32_t *status) {
-    p.commands = (const uint32_t *)draw_commands;
-    p.meshlet_data = meshlet_data;
-    p.vertices = (const uint8_t *)vertices;
-    p.entity_data = (const float *)entity_data;
-    p.stats = (uint32_t *)stats;
-    p.meshlet_data_words = meshlet_data_words, p.vertex_count = vertex_count;
-    p.max_commands = max_commands, p.entity_count = entity_count;
-    p.vertex_stride = vertex_stride, p.position_offset = position_offset;
-    p.width = width, p.height = height, p.flags = flags;
-    for (int k = 0; k < 16; k++) p.view_proj[k] = view_proj[k];
+// (OrbitRasterDepth and OrbitRasterVisibility name these fields alike)
+template <class Job>
+inline void fill_raster_params(RasterParams &p, const Job &job, int32_t *status) {
+    p.commands = (const uint32_t *)job.draw_commands;
+    p.meshlet_data = job.meshlet_data;
+    p.vertices = (const uint8_t *)job.vertices;
+    p.entity_data = (const float *)job.entity_data;
+    p.stats = (uint32_t *)job.stats;
+    p.meshlet_data_words = job.meshlet_data_words, p.vertex_count = job.vertex_count;
+    p.max_commands = job.max_commands, p.entity_count = job.entity_count;
+    p.vertex_stride = job.vertex_stride, p.position_offset = job.position_offset;
+    p.width = job.width, p.height = job.height, p.flags = job.flags;
+    for (int k = 0; k < 16; k++) p.view_proj[k] = job.view_proj[k];
     p.status = status;
 }
 
@@ -84,8 +95,8 @@ __device__ __forceinline__ uint32_t walk(const Sink &sink, uint32_t width, const
     return inside;
 }
 
-// The body of a raster kernel: a resident grid of wave64s striding over the command list (raster_depth.hip's header
-// names the phases).  `id_base` is added to the command's position in the list before it goes into the sample's id.
+// The body of a raster kernel: a resident grid of wave64s striding over the command list, in the phases named at the
+// top.  `id_base` is added to the command's position in the list before it goes into the sample's id.
 template <class Sink>
 __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sink &sink, uint32_t id_base) {
     __shared__ int4 lds_verts[kRasterWaves][kMaxVertices];
@@ -189,6 +200,40 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
         for (uint32_t d = 1; d < 64u; d <<= 1) v += (uint32_t)__shfl_xor((int)v, (int)d, 64);
         if (lane == 0u && v != 0u) atomicAdd(&p.stats[k], v);
     }
+}
+
+// target[0, words) = 0 and, if given, the eight counters = 0
+template <class Word>
+__global__ __launch_bounds__(kRasterThreads) void raster_clear_kernel(Word *target, uint64_t words, uint32_t *stats) {
+    const uint64_t stride = (uint64_t)gridDim.x * kRasterThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kRasterThreads + threadIdx.x; i < words; i += stride) target[i] = 0;
+    if (stats && blockIdx.x == 0u && threadIdx.x < 8u) stats[threadIdx.x] = 0u;
+}
+
+// A raster call on the stream: one launch clears `target` (ORBIT_RASTER_CLEAR) and the counters, the next is `kernel`
+// over (the job's RasterParams, args...).  LoadOp::Clear(0.0) and the counters' clear are a launch, not memset nodes: a
+// captured call then consists of kernel nodes only, whose arguments a replay carries by value.
+template <class Job, class Word, class... Args>
+inline hipError_t launch_raster(void (*kernel)(RasterParams, Args...), const Job &job, Word *target, uint32_t resident_blocks,
+                                int32_t *status, hipStream_t s, Args... args) {
+    const uint64_t clear_words = (job.flags & ORBIT_RASTER_CLEAR) ? (uint64_t)job.width * job.height : 0ull;
+    const uint64_t cap = resident_blocks ? resident_blocks : 512u;
+    if (clear_words != 0ull || job.stats) {
+        const uint64_t need = (clear_words + kRasterThreads * 4ull - 1ull) / (kRasterThreads * 4ull);
+        const uint32_t blocks = (uint32_t)(need < 1ull ? 1ull : need < cap ? need : cap);
+        hipLaunchKernelGGL(raster_clear_kernel<Word>, dim3(blocks), dim3(kRasterThreads), 0, s, target, clear_words,
+                           (uint32_t *)job.stats);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (job.max_commands == 0u) return hipSuccess;
+    RasterParams p;
+    fill_raster_params(p, job, status);
+    // the count is the device's: the grid covers max_commands, up to as many workgroups as are resident at once (the
+    // kernel's registers decide how many per CU), which stride over the list
+    const uint64_t need = ((uint64_t)job.max_commands + kRasterWaves - 1u) / kRasterWaves;
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)(need < cap ? need : cap)), dim3(kRasterThreads), 0, s, p, args...);
+    return hipGetLastError();
 }
 
 } // namespace raster

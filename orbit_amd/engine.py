@@ -36,6 +36,20 @@ def _host_bytes(x, nbytes):
     return a
 
 
+def _raster_job(j, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, entity_count, view_proj,
+                width, height, clear, cull_none, stats, vertex_stride, position_offset, meshlet_data_words):
+    """The fields that _lib.RasterDepth and _lib.RasterVisibility share, filled into `j` -> j."""
+    nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
+    j.draw_commands, j.meshlet_data, j.vertices = _ptr(draw_commands), _ptr(meshlet_data), _ptr(vertices)
+    j.entity_data, j.stats = _ptr(entity_data), _ptr(stats)
+    j.meshlet_data_words = nbytes(meshlet_data) // 4 if meshlet_data_words is None else int(meshlet_data_words)
+    j.vertex_count, j.max_commands, j.entity_count = int(vertex_count), int(max_commands), int(entity_count)
+    j.vertex_stride, j.position_offset, j.width, j.height = int(vertex_stride), int(position_offset), int(width), int(height)
+    j.flags = (_lib.RASTER_CLEAR if clear else 0) | (_lib.RASTER_CULL_NONE if cull_none else 0)
+    j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
+    return j
+
+
 def depth_pyramid_desc(screen_width, screen_height):
     """DepthPyramid::new geometry (src/passes/draw_gen.rs:457-459)."""
     d = _lib.DepthPyramidDesc()
@@ -326,15 +340,10 @@ class Engine:
         `entity_data`: 128-B rows.  `stats`: device tensor of 32 bytes (layouts.RASTER_STATS), cleared by the call.
         Back faces are culled unless cull_none.  Byte-equal to orbit_amd.raster.host_raster_depth on host copies.
         Enqueued on `stream`; a command that points out of range is skipped and reported by status() (ORBIT_E_RANGE)."""
-        nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
-        j = _lib.RasterDepth()
-        j.draw_commands, j.meshlet_data, j.vertices = _ptr(draw_commands), _ptr(meshlet_data), _ptr(vertices)
-        j.entity_data, j.depth, j.stats = _ptr(entity_data), _ptr(depth), _ptr(stats)
-        j.meshlet_data_words = nbytes(meshlet_data) // 4 if meshlet_data_words is None else int(meshlet_data_words)
-        j.vertex_count, j.max_commands, j.entity_count = int(vertex_count), int(max_commands), int(entity_count)
-        j.vertex_stride, j.position_offset, j.width, j.height = int(vertex_stride), int(position_offset), int(width), int(height)
-        j.flags = (_lib.RASTER_CLEAR if clear else 0) | (_lib.RASTER_CULL_NONE if cull_none else 0)
-        j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
+        j = _raster_job(_lib.RasterDepth(), draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data,
+                        entity_count, view_proj, width, height, clear, cull_none, stats, vertex_stride, position_offset,
+                        meshlet_data_words)
+        j.depth = _ptr(depth)
         _lib.check(self._lib.orbit_raster_depth(self._ctx, C.byref(j), _stream(stream)), self._ctx)
 
     # -- the same pass keeping the winner's identity, and its resolve (orbit_raster_visibility, orbit_visibility_resolve)
@@ -348,16 +357,10 @@ class Engine:
         are raster_depth's depth bytes.  A command with more than 256 triangles is skipped like one that points out of
         range (status(): ORBIT_E_RANGE); command_base + max_commands may not exceed 2^24.  Byte-equal to
         orbit_amd.raster.host_raster_visibility on host copies.  Enqueued on `stream`."""
-        nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
-        j = _lib.RasterVisibility()
-        j.draw_commands, j.meshlet_data, j.vertices = _ptr(draw_commands), _ptr(meshlet_data), _ptr(vertices)
-        j.entity_data, j.visibility, j.stats = _ptr(entity_data), _ptr(visibility), _ptr(stats)
-        j.meshlet_data_words = nbytes(meshlet_data) // 4 if meshlet_data_words is None else int(meshlet_data_words)
-        j.vertex_count, j.max_commands, j.entity_count = int(vertex_count), int(max_commands), int(entity_count)
-        j.vertex_stride, j.position_offset, j.width, j.height = int(vertex_stride), int(position_offset), int(width), int(height)
-        j.flags = (_lib.RASTER_CLEAR if clear else 0) | (_lib.RASTER_CULL_NONE if cull_none else 0)
-        j.command_base = int(command_base)
-        j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
+        j = _raster_job(_lib.RasterVisibility(), draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data,
+                        entity_count, view_proj, width, height, clear, cull_none, stats, vertex_stride, position_offset,
+                        meshlet_data_words)
+        j.visibility, j.command_base = _ptr(visibility), int(command_base)
         _lib.check(self._lib.orbit_raster_visibility(self._ctx, C.byref(j), _stream(stream)), self._ctx)
 
     def visibility_resolve(self, visibility, width, height, command_base=0, max_commands=0, depth=None,

@@ -23,12 +23,11 @@ def command_buffer(commands, capacity=None, count=None):
     return buf
 
 
-def host_raster_depth(draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, view_proj, width,
-                      height, depth=None, clear=True, cull_none=False, vertex_stride=12, position_offset=0,
-                      entity_count=None, meshlet_data_words=None):
-    """orbit_host_raster_depth on host arrays -> (depth: np.float32 (height, width), stats: np[layouts.RASTER_STATS]
-    scalar row, command_error: np.int32 per processed command).  `draw_commands`: the {count; commands} words (any
-    contiguous array, read as bytes).  `depth`: the buffer to load (copied); None needs clear=True."""
+def _host_raster(call, dtype, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, view_proj,
+                 width, height, target, no_target, clear, cull_none, vertex_stride, position_offset, entity_count,
+                 meshlet_data_words, *extra):
+    """What the two raster calls of the host mirror share: the arguments as the C call takes them (`extra` goes between
+    the flags and the stats), the target loaded (copied) or cleared, -> (target, stats row, command_error)."""
     buf = np.ascontiguousarray(draw_commands).view(np.uint8).reshape(-1)
     if buf.nbytes < 4 + 28 * int(max_commands):
         raise ValueError("max_commands reaches beyond the command array")
@@ -39,22 +38,32 @@ def host_raster_depth(draw_commands, max_commands, meshlet_data, vertices, verte
     ent = np.ascontiguousarray(entity_data).view(np.uint8).reshape(-1)
     entity_count = ent.nbytes // 128 if entity_count is None else int(entity_count)
     words = len(data) if meshlet_data_words is None else int(meshlet_data_words)
-    if depth is None:
+    if target is None:
         if not clear:
-            raise ValueError("no depth to load")
-        out = np.zeros((height, width), np.float32)
+            raise ValueError(no_target)
+        out = np.zeros((height, width), dtype)
     else:
-        out = np.array(depth, dtype=np.float32, order="C").reshape(height, width)
+        out = np.array(target, dtype=dtype, order="C").reshape(height, width)
     n = min(int(buf[:4].view(np.uint32)[0]), int(max_commands))
     stats, err = np.zeros(1, L.RASTER_STATS), np.zeros(n, np.int32)
     vp = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    _check(lib().orbit_host_raster_depth(p(buf), C.c_uint32(max_commands), p(data), C.c_uint64(words), p(vb),
-                                         C.c_uint64(vertex_count), C.c_uint32(vertex_stride), C.c_uint32(position_offset),
-                                         p(ent), C.c_uint32(entity_count), vp, p(out), C.c_uint32(width), C.c_uint32(height),
-                                         C.c_uint32((CLEAR if clear else 0) | (CULL_NONE if cull_none else 0)), p(stats),
-                                         p(err)))
+    _check(call(p(buf), C.c_uint32(max_commands), p(data), C.c_uint64(words), p(vb), C.c_uint64(vertex_count),
+                C.c_uint32(vertex_stride), C.c_uint32(position_offset), p(ent), C.c_uint32(entity_count), vp, p(out),
+                C.c_uint32(width), C.c_uint32(height), C.c_uint32((CLEAR if clear else 0) | (CULL_NONE if cull_none else 0)),
+                *extra, p(stats), p(err)))
     return out, stats[0], err
+
+
+def host_raster_depth(draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, view_proj, width,
+                      height, depth=None, clear=True, cull_none=False, vertex_stride=12, position_offset=0,
+                      entity_count=None, meshlet_data_words=None):
+    """orbit_host_raster_depth on host arrays -> (depth: np.float32 (height, width), stats: np[layouts.RASTER_STATS]
+    scalar row, command_error: np.int32 per processed command).  `draw_commands`: the {count; commands} words (any
+    contiguous array, read as bytes).  `depth`: the buffer to load (copied); None needs clear=True."""
+    return _host_raster(lib().orbit_host_raster_depth, np.float32, draw_commands, max_commands, meshlet_data, vertices,
+                        vertex_count, entity_data, view_proj, width, height, depth, "no depth to load", clear, cull_none,
+                        vertex_stride, position_offset, entity_count, meshlet_data_words)
 
 
 def host_raster_visibility(draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, view_proj,
@@ -63,33 +72,9 @@ def host_raster_visibility(draw_commands, max_commands, meshlet_data, vertices, 
     """orbit_host_raster_visibility on host arrays -> (visibility: np.uint64 (height, width), stats:
     np[layouts.RASTER_STATS] scalar row, command_error: np.int32 per processed command).  The arguments are
     host_raster_depth's; `visibility`: the buffer to merge into (copied); None needs clear=True."""
-    buf = np.ascontiguousarray(draw_commands).view(np.uint8).reshape(-1)
-    if buf.nbytes < 4 + 28 * int(max_commands):
-        raise ValueError("max_commands reaches beyond the command array")
-    data = np.ascontiguousarray(meshlet_data, dtype=np.uint32).reshape(-1)
-    vb = np.ascontiguousarray(vertices).view(np.uint8).reshape(-1)
-    if int(vertex_count) and (int(vertex_count) - 1) * int(vertex_stride) + int(position_offset) + 12 > vb.nbytes:
-        raise ValueError("vertex_count reaches beyond the vertex array")
-    ent = np.ascontiguousarray(entity_data).view(np.uint8).reshape(-1)
-    entity_count = ent.nbytes // 128 if entity_count is None else int(entity_count)
-    words = len(data) if meshlet_data_words is None else int(meshlet_data_words)
-    if visibility is None:
-        if not clear:
-            raise ValueError("no buffer to merge into")
-        out = np.zeros((height, width), np.uint64)
-    else:
-        out = np.array(visibility, dtype=np.uint64, order="C").reshape(height, width)
-    n = min(int(buf[:4].view(np.uint32)[0]), int(max_commands))
-    stats, err = np.zeros(1, L.RASTER_STATS), np.zeros(n, np.int32)
-    vp = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
-    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    _check(lib().orbit_host_raster_visibility(p(buf), C.c_uint32(max_commands), p(data), C.c_uint64(words), p(vb),
-                                              C.c_uint64(vertex_count), C.c_uint32(vertex_stride),
-                                              C.c_uint32(position_offset), p(ent), C.c_uint32(entity_count), vp, p(out),
-                                              C.c_uint32(width), C.c_uint32(height),
-                                              C.c_uint32((CLEAR if clear else 0) | (CULL_NONE if cull_none else 0)),
-                                              C.c_uint32(command_base), p(stats), p(err)))
-    return out, stats[0], err
+    return _host_raster(lib().orbit_host_raster_visibility, np.uint64, draw_commands, max_commands, meshlet_data, vertices,
+                        vertex_count, entity_data, view_proj, width, height, visibility, "no buffer to merge into", clear,
+                        cull_none, vertex_stride, position_offset, entity_count, meshlet_data_words, C.c_uint32(command_base))
 
 
 def host_visibility_resolve(visibility, command_base=0, max_commands=0, want_command_pixels=True):

@@ -11,6 +11,7 @@ import pytest
 
 import raster_cases as rc
 import raster_scene as rs
+import raster_vis_cases as vc
 from orbit_amd import _lib, passes, raster
 from orbit_amd import layouts as L
 
@@ -41,6 +42,18 @@ def test_host_mirror_equals_the_restatement_on_the_census(case):
     pk = rc.Packed(case)
     assert_same(case.name, pk.host(), pk.restated())
     assert not rc.check_claims(case, *pk.host(), pk.restated()[3])  # the claims hold on the mirror's own output too
+
+
+def test_host_mirror_draws_a_command_of_more_than_256_triangles():
+    """The depth call has no triangle limit: the case whose middle command the visibility call skips (V3) is drawn whole,
+    by the mirror and by the restatement alike.  tests/test_raster_depth_gpu.py runs the device against this mirror."""
+    pk = rc.Packed(next(c for c in vc.new_cases() if c.name == "nt_257_between_neighbours"))
+    assert (pk.case.width, pk.case.height) == (64, 48) and [len(m.corners) for m in pk.case.meshlets] == [1, 257, 1]
+    got = pk.host()
+    assert_same(pk.case.name, got, pk.restated())
+    assert not got[2].any()
+    assert (int(got[1]["range_errors"]), int(got[1]["commands"]), int(got[1]["triangles"])) == (0, 3, 259)
+    assert (got[0] > 0).sum() > 90  # more than the two neighbours' 45 pixels each: the strip is in the buffer
 
 
 @pytest.mark.parametrize("stride,offset", [(32, 0), (32, 20)])

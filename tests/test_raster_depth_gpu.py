@@ -8,6 +8,7 @@ import pytest
 
 import raster_cases as rc
 import raster_scene as rs
+import raster_vis_cases as vc
 from orbit_amd import _lib, raster
 from orbit_amd import layouts as L
 from test_gpu_parity import dev, host
@@ -104,6 +105,20 @@ def test_every_case_equals_the_host_mirror(torch_mod, engine, stride, offset):
         assert latched(engine) == (_lib.E_RANGE if err.any() else 0), case.name
         assert_equal(case.name, got_depth, got_stats, want_depth, want_stats)
         assert not rc.check_claims(case, got_depth, got_stats, err, pk.restated()[3] if case.extra else None), case.name
+
+
+def test_a_command_of_more_than_256_triangles_is_drawn(torch_mod, engine):
+    """The depth call has no triangle limit (V3 is the visibility call's): the 257-triangle strip between two neighbours
+    is drawn, where orbit_raster_visibility skips it.  The reference is held to tests/raster_ref.py by
+    tests/test_raster_depth_cpu.py on the same case."""
+    assert latched(engine) == 0
+    pk = rc.Packed(next(c for c in vc.new_cases() if c.name == "nt_257_between_neighbours"))
+    assert (pk.case.width, pk.case.height) == (64, 48) and [len(m.corners) for m in pk.case.meshlets] == [1, 257, 1]
+    want_depth, want_stats, err = pk.host()
+    got_depth, got_stats = run_case(torch_mod, engine, pk)
+    assert latched(engine) == 0 and not err.any()
+    assert_equal(pk.case.name, got_depth, got_stats, want_depth, want_stats)
+    assert (int(got_stats["range_errors"]), int(got_stats["commands"]), int(got_stats["triangles"])) == (0, 3, 259)
 
 
 def test_no_stats_and_a_loaded_buffer(torch_mod, engine):
