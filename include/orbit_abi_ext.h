@@ -858,6 +858,46 @@ int32_t orbit_mesh_bounds(OrbitCtx *ctx, const OrbitMeshBoundsRange *ranges, uin
 /*     with a failing vertex is NOT DRAWN (clip_skipped).  NEAR-PLANE       */
 /*     CLIPPING IS OUT OF SCOPE: skipping only leaves the depth farther,    */
 /*     the safe side for occlusion.                                         */
+/*  R3c only with ORBIT_RASTER_CLIP_NEAR (without it R3 stands as above):   */
+/*     a triangle with a failing vertex is cut at the near plane z = w.     */
+/*     c_k = (x, y, z, w) are R2's clip coordinates, in_k is R3's test.     */
+/*     All three in: nothing changes.  Otherwise the triangle is ELIGIBLE   */
+/*     iff all twelve coordinates are finite, every z_k >= 0 and at least   */
+/*     one in_k holds; not eligible is clip_skipped as before (all three    */
+/*     out, a NaN or infinity, a vertex beyond the far plane).              */
+/*     New vertices: b_k = w_k - z_k.  N(i, o), on the edge from an in      */
+/*     vertex i to an out vertex o: den = b_i - b_o; !(den > 0): the whole  */
+/*     triangle is clip_skipped; t = b_i / den; x = x_i + t * (x_o - x_i),  */
+/*     y and w alike; !(w > 0): the whole triangle is clip_skipped; its     */
+/*     depth is d = 1.0f exactly (it lies on the near plane; its z is not   */
+/*     computed); X, Y and the guard flag are R4's on (x, y, w).  N depends */
+/*     on the ordered pair (in, out) only, not on the winding: two          */
+/*     triangles sharing a crossing edge get the same vertex, the mesh      */
+/*     stays watertight.                                                    */
+/*     Pieces: (v0, v1, v2) is rotated cyclically to (a, b, c), a the lone  */
+/*     vertex (the only in vertex, or the only out vertex).  One in:        */
+/*     piece0 = (a, N(a,b), N(a,c)).  One out: P = N(b,a), Q = N(c,a),      */
+/*     piece0 = (b, c, Q), piece1 = (b, Q, P).  Both forms keep the         */
+/*     orientation.  Each piece goes through R4's guard test and R5-R8 as   */
+/*     a triangle of its own (area, facing, box, edges, depth plane); in    */
+/*     the visibility word every piece carries the ORIGINAL triangle's t.   */
+/*     The diagonal b-Q is shared with identical snapped ends: the          */
+/*     top-left rule gives each sample on it to exactly one piece.          */
+/*     Counters: a clipped triangle is counted ONCE, under the best         */
+/*     outcome of its pieces, in the priority drawn, guard_skipped,         */
+/*     back_facing, no_coverage (guard_skipped only when no piece drew      */
+/*     and one failed R4's guard); triangles = clip_skipped +               */
+/*     guard_skipped + no_coverage + back_facing + drawn still holds;       */
+/*     fragments sums over the pieces.                                      */
+/*     Consequences: a triangle R3 accepts goes through unchanged, so the   */
+/*     flagged result is pixel-wise >= the unflagged one on the u32 view;   */
+/*     with the flag on both calls V4 holds unchanged (high halves = the    */
+/*     depth call's bytes, equal stats); everything still depends on one    */
+/*     triangle only: independent of scheduling.  Clipping against the      */
+/*     SIDE planes stays out of scope: a piece whose vertex leaves R4's     */
+/*     guard band is guard_skipped, the safe side.  With a near plane at    */
+/*     0.01 that is every crossing triangle further than about              */
+/*     0.01 * 2^15 / (W / 2) to the side of the eye.                        */
 /*  R4 ndc = clip.xyz / w; xs = (ndc.x * 0.5 + 0.5) * W; ys = (ndc.y * -0.5 */
 /*     + 0.5) * H (negative viewport height, commands.rs:303-313; the       */
 /*     cull's uv, entity_cull.comp:99-101); X = rint(xs * 256), Y =         */
@@ -892,7 +932,8 @@ int32_t orbit_mesh_bounds(OrbitCtx *ctx, const OrbitMeshBoundsRange *ranges, uin
 /* stats (may be NULL) is cleared by the call on the stream, then counts:   */
 /* commands = min(count, max_commands); triangles = the nt of the commands  */
 /* that passed R9 = clip_skipped + guard_skipped + no_coverage +            */
-/* back_facing + drawn (tested in that order: R3, R4, A == 0, facing, R6).  */
+/* back_facing + drawn (tested in that order: R3, R4, A == 0, facing, R6;   */
+/* with ORBIT_RASTER_CLIP_NEAR a cut triangle counts once, see R3c).        */
 /*                                                                          */
 /* ORBIT_RASTER_CLEAR is LoadOp::Clear(0.0): the call clears `depth` on the */
 /* stream first; without it the call is LoadOp::Load, the late pass, and    */
@@ -917,6 +958,8 @@ ORBIT_STATIC_ASSERT(sizeof(OrbitRasterStats) == 32, "RasterStats is 32 B");
 
 #define ORBIT_RASTER_CLEAR 1u     /* flags: LoadOp::Clear(0.0) instead of LoadOp::Load */
 #define ORBIT_RASTER_CULL_NONE 2u /* flags: draw back faces too */
+/* (bit 2, value 4, is not a flag: it stays unknown and rejected, the value the tests of unknown flags use) */
+#define ORBIT_RASTER_CLIP_NEAR 8u /* flags: R3c, near-plane clipping of the triangles R3 rejects */
 #define ORBIT_RASTER_MAX_DIM 32768u
 typedef struct OrbitRasterDepth { /* HOST block, 160 B; every pointer a DEVICE pointer */
     const void *draw_commands;          /* {u32 count; OrbitMeshletDrawCommand[max_commands]} */
@@ -965,7 +1008,8 @@ int32_t orbit_raster_depth(OrbitCtx *ctx, const OrbitRasterDepth *job, void *str
 /* ORBIT_RASTER_CLEAR clears the buffer to 0 on the stream first; without   */
 /* it the call merges into what an earlier call left (the late pass), and   */
 /* command_base keeps the late list's ids apart from the early one's.       */
-/* ORBIT_RASTER_CULL_NONE as before.  No allocation, no scratch, no host    */
+/* ORBIT_RASTER_CULL_NONE and ORBIT_RASTER_CLIP_NEAR (R3c) as before.  No   */
+/* allocation, no scratch, no host                                          */
 /* wait, the count is read on the device, kernels only: a graph captures    */
 /* the call on a fresh context's first call.                                */
 /*                                                                          */

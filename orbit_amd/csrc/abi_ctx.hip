@@ -148,8 +148,10 @@ int32_t orbit_ctx_create(int32_t device_id, const OrbitCaps *caps_in, OrbitCtx *
     if (!ctx) return fail(nullptr, ORBIT_E_HIP, "out of host memory");
     ctx->device = device_id;
     ctx->num_cus = (uint32_t)prop.multiProcessorCount;
-    ctx->raster_blocks = ctx->num_cus * raster_depth_blocks_per_cu();
-    ctx->visibility_blocks = ctx->num_cus * raster_visibility_blocks_per_cu();
+    ctx->raster_blocks = ctx->num_cus * raster_depth_blocks_per_cu(false);
+    ctx->visibility_blocks = ctx->num_cus * raster_visibility_blocks_per_cu(false);
+    ctx->raster_clip_blocks = ctx->num_cus * raster_depth_blocks_per_cu(true);
+    ctx->visibility_clip_blocks = ctx->num_cus * raster_visibility_blocks_per_cu(true);
     ctx->caps = caps;
     ctx->rec_shift = rec_shift;
 

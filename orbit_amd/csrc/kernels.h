@@ -373,11 +373,18 @@ hipError_t launch_mesh_bounds(const OrbitMeshBoundsRange *ranges, uint32_t range
 // (ORBIT_RASTER_CLEAR) and stats, the next reads the command count on the device and draws (raster_walk.h: one walker
 // and one launch, which raster_depth.hip and raster_visibility.hip give a sink each)
 hipError_t launch_raster_depth(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
-// ... its workgroups that one CU holds at once (asked of the runtime once, when a context is created)
-uint32_t raster_depth_blocks_per_cu();
+// ... its workgroups that one CU holds at once (asked of the runtime once, when a context is created); clip_near: of
+// the kernel that ORBIT_RASTER_CLIP_NEAR launches (R3c), which `resident_blocks` must then be of, too
+uint32_t raster_depth_blocks_per_cu(bool clip_near);
+// raster_depth_clip.hip: what the two above hand ORBIT_RASTER_CLIP_NEAR over to
+hipError_t launch_raster_depth_clip(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
+uint32_t raster_depth_clip_blocks_per_cu();
 // raster_visibility.hip: orbit_raster_visibility — as launch_raster_depth, into the u64 buffer (V1-V4)
 hipError_t launch_raster_visibility(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
-uint32_t raster_visibility_blocks_per_cu();
+uint32_t raster_visibility_blocks_per_cu(bool clip_near);
+// raster_visibility_clip.hip: the same for ORBIT_RASTER_CLIP_NEAR
+hipError_t launch_raster_visibility_clip(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
+uint32_t raster_visibility_clip_blocks_per_cu();
 // ... and orbit_visibility_resolve: one launch clears command_pixels and stats, the next reads every word once
 hipError_t launch_visibility_resolve(const OrbitVisibilityResolve &job, uint32_t num_cus, hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the

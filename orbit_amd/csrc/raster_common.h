@@ -32,15 +32,30 @@ ORBIT_RASTER_FN void mat4_mul(const float *a, const float *b, float *out) {
             out[4 * c + r] = ((a[r] * b[4 * c] + a[4 + r] * b[4 * c + 1]) + a[8 + r] * b[4 * c + 2]) + a[12 + r] * b[4 * c + 3];
 }
 
-// R2-R4 of one position
-ORBIT_RASTER_FN Vertex transform_vertex(const float *mvp, float px, float py, float pz, float w_f, float h_f) {
+struct Clip { // R2: the clip coordinates of one position
+    float x, y, z, w;
+};
+
+// R2 of one position
+ORBIT_RASTER_FN Clip clip_position(const float *mvp, float px, float py, float pz) {
     float clip[4];
     for (int r = 0; r < 4; r++) clip[r] = ((mvp[r] * px + mvp[4 + r] * py) + mvp[8 + r] * pz) + mvp[12 + r] * 1.0f;
-    const float x = clip[0], y = clip[1], z = clip[2], w = clip[3];
+    Clip c;
+    c.x = clip[0], c.y = clip[1], c.z = clip[2], c.w = clip[3];
+    return c;
+}
+
+// R3: w > 0 && z >= 0 && z <= w (false for NaN)
+ORBIT_RASTER_FN bool clip_in(const Clip &c) { return c.w > 0.0f && c.z >= 0.0f && c.z <= c.w; }
+
+// R3, R4 of clip coordinates.  on_near_plane (R3c's new vertices): the depth is 1 exactly, c.z is not read and R3 is
+// not asked; X, Y and the guard flag are R4's all the same.
+ORBIT_RASTER_FN Vertex vertex_from_clip(const Clip &c, float w_f, float h_f, bool on_near_plane = false) {
+    const float x = c.x, y = c.y, z = c.z, w = c.w;
     Vertex v;
-    v.flags = (w > 0.0f && z >= 0.0f && z <= w) ? 0u : kClipFail;
+    v.flags = on_near_plane ? 0u : (w > 0.0f && z >= 0.0f && z <= w) ? 0u : kClipFail;
     const float nx = x / w, ny = y / w;
-    v.d = z / w;
+    v.d = on_near_plane ? 1.0f : z / w;
     const float xs = (nx * 0.5f + 0.5f) * w_f, ys = (ny * -0.5f + 0.5f) * h_f;
     const float xf = xs * 256.0f, yf = ys * 256.0f;
     const bool in_guard = fabsf(xf) < 8388608.0f && fabsf(yf) < 8388608.0f; // false for NaN
@@ -48,6 +63,11 @@ ORBIT_RASTER_FN Vertex transform_vertex(const float *mvp, float px, float py, fl
     v.X = in_guard ? (int32_t)rintf(xf) : 0;
     v.Y = in_guard ? (int32_t)rintf(yf) : 0;
     return v;
+}
+
+// R2-R4 of one position
+ORBIT_RASTER_FN Vertex transform_vertex(const float *mvp, float px, float py, float pz, float w_f, float h_f) {
+    return vertex_from_clip(clip_position(mvp, px, py, pz), w_f, h_f);
 }
 
 enum Outcome : uint32_t { kDraw = 0, kClipSkipped = 1, kGuardSkipped = 2, kBackFacing = 3, kNoCoverage = 4 };
@@ -106,6 +126,77 @@ ORBIT_RASTER_FN float depth_at(const Setup &s, int32_t px, int32_t py) {
     const float d = (s.d0 + s.gx * (float)(px - s.ax[0])) + s.gy * (float)(py - s.ay[0]);
     return 1.0f < d ? 1.0f : d; // GLSL min(d, 1): a NaN stays a NaN
 }
+
+// ---- R3c (ORBIT_RASTER_CLIP_NEAR): a triangle R3 rejects, cut at the near plane z = w -----------------------------
+// The pieces as a fan of up to four vertices: piece 0 = (u[0], u[1], u[2]), piece 1 = (u[0], u[2], u[3]).  Both keep
+// the triangle's orientation; the diagonal u[0]-u[2] is shared with identical snapped ends.
+struct Pieces {
+    Vertex u[4];
+    uint32_t count; // 0: the triangle stays clip_skipped
+};
+
+ORBIT_RASTER_FN Clip select_clip(bool first, const Clip &a, const Clip &b) {
+    Clip c;
+    c.x = first ? a.x : b.x, c.y = first ? a.y : b.y, c.z = first ? a.z : b.z, c.w = first ? a.w : b.w;
+    return c;
+}
+
+ORBIT_RASTER_FN bool clip_finite(const Clip &c) {
+    return fabsf(c.x) < INFINITY && fabsf(c.y) < INFINITY && fabsf(c.z) < INFINITY && fabsf(c.w) < INFINITY; // false for NaN
+}
+
+// N(i, o): the new vertex on the edge from the in vertex i to the out vertex o — a function of the ordered pair
+// only, so two triangles sharing the edge get the same vertex.  -> false: the whole triangle is clip_skipped.
+ORBIT_RASTER_FN bool clip_new_vertex(const Clip &i, const Clip &o, float w_f, float h_f, Vertex &n) {
+    const float b_i = i.w - i.z, b_o = o.w - o.z;
+    const float den = b_i - b_o;
+    if (!(den > 0.0f)) return false;
+    const float t = b_i / den;
+    Clip c; // on the near plane; its z is not computed
+    c.x = i.x + t * (o.x - i.x), c.y = i.y + t * (o.y - i.y), c.z = 0.0f, c.w = i.w + t * (o.w - i.w);
+    if (!(c.w > 0.0f)) return false;
+    n = vertex_from_clip(c, w_f, h_f, true);
+    return true;
+}
+
+// The pieces of a triangle with at least one vertex failing R3.  The rotation to (a, b, c), a the lone vertex, is
+// made of selects: no indexed array.
+ORBIT_RASTER_FN void clip_near_pieces(const Clip &c0, const Clip &c1, const Clip &c2, float w_f, float h_f, Pieces &p) {
+    p.count = 0u;
+    const bool in0 = clip_in(c0), in1 = clip_in(c1), in2 = clip_in(c2);
+    const uint32_t n_in = (in0 ? 1u : 0u) + (in1 ? 1u : 0u) + (in2 ? 1u : 0u);
+    if (n_in == 0u || n_in == 3u) return;
+    if (!(clip_finite(c0) && clip_finite(c1) && clip_finite(c2))) return;
+    if (!(c0.z >= 0.0f && c1.z >= 0.0f && c2.z >= 0.0f)) return;
+    const bool one_in = n_in == 1u;
+    // the lone vertex is the one whose test differs from the other two
+    const bool lone0 = in0 == one_in, lone1 = !lone0 && in1 == one_in;
+    const Clip a = select_clip(lone0, c0, select_clip(lone1, c1, c2));
+    const Clip b = select_clip(lone0, c1, select_clip(lone1, c2, c0));
+    const Clip c = select_clip(lone0, c2, select_clip(lone1, c0, c1));
+    // one in: N(a, b), N(a, c); one out: Q = N(c, a), P = N(b, a)
+    Vertex n0, n1;
+    if (!clip_new_vertex(select_clip(one_in, a, c), select_clip(one_in, b, a), w_f, h_f, n0)) return;
+    if (!clip_new_vertex(select_clip(one_in, a, b), select_clip(one_in, c, a), w_f, h_f, n1)) return;
+    if (one_in) { // (a, N(a,b), N(a,c))
+        p.u[0] = vertex_from_clip(a, w_f, h_f), p.u[1] = n0, p.u[2] = n1, p.u[3] = n1;
+        p.count = 1u;
+    } else { // (b, c, Q), (b, Q, P)
+        p.u[0] = vertex_from_clip(b, w_f, h_f), p.u[1] = vertex_from_clip(c, w_f, h_f), p.u[2] = n0, p.u[3] = n1;
+        p.count = 2u;
+    }
+}
+
+// piece q of p
+ORBIT_RASTER_FN void piece_vertices(const Pieces &p, uint32_t q, Vertex &v0, Vertex &v1, Vertex &v2) {
+    v0 = p.u[0];
+    v1 = q ? p.u[2] : p.u[1];
+    v2 = q ? p.u[3] : p.u[2];
+}
+
+// A clipped triangle is counted once, under the best outcome of its pieces: drawn, guard_skipped, back_facing,
+// no_coverage — the order of the Outcome values.
+ORBIT_RASTER_FN uint32_t better_outcome(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
 } // namespace raster
 } // namespace orbit

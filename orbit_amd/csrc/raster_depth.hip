@@ -8,6 +8,10 @@
 // much: the buffer only grows, so a stale smaller value costs an atomic, never a pixel.
 #include "raster_walk.h"
 
+#ifndef ORBIT_RASTER_CLIP
+#define ORBIT_RASTER_CLIP 0 // 1: raster_depth_clip.hip compiles this file into the ORBIT_RASTER_CLIP_NEAR kernel and its launch
+#endif
+
 namespace orbit {
 namespace {
 
@@ -28,20 +32,38 @@ struct DepthSink {
     }
 };
 
+#if !ORBIT_RASTER_CLIP
 __global__ __launch_bounds__(kRasterThreads) void raster_depth_kernel(const RasterParams p, uint32_t *const depth) {
-    raster_commands(p, DepthSink{depth}, 0u);
+    raster_commands<false>(p, DepthSink{depth}, 0u);
 }
+#define ORBIT_RASTER_DEPTH_KERNEL raster_depth_kernel
+#else // ORBIT_RASTER_CLIP_NEAR (R3c), a translation unit of its own (raster_depth_clip.hip)
+__global__ __launch_bounds__(kRasterThreads) void raster_depth_clip_kernel(const RasterParams p, uint32_t *const depth) {
+    raster_commands<true>(p, DepthSink{depth}, 0u);
+}
+#define ORBIT_RASTER_DEPTH_KERNEL raster_depth_clip_kernel
+#endif
 
 } // namespace
 
-uint32_t raster_depth_blocks_per_cu() {
+#if !ORBIT_RASTER_CLIP
+uint32_t raster_depth_blocks_per_cu(bool clip_near) {
+    if (clip_near) return raster_depth_clip_blocks_per_cu();
+#else
+uint32_t raster_depth_clip_blocks_per_cu() {
+#endif
     int n = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, raster_depth_kernel, (int)kRasterThreads, 0);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ORBIT_RASTER_DEPTH_KERNEL, (int)kRasterThreads, 0);
     return e == hipSuccess && n > 0 ? (uint32_t)n : 2u;
 }
 
+#if !ORBIT_RASTER_CLIP
 hipError_t launch_raster_depth(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
-    return launch_raster(raster_depth_kernel, job, (uint32_t *)job.depth, resident_blocks, status, s, (uint32_t *)job.depth);
+    if (job.flags & ORBIT_RASTER_CLIP_NEAR) return launch_raster_depth_clip(job, resident_blocks, status, s);
+#else
+hipError_t launch_raster_depth_clip(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
+#endif
+    return launch_raster(ORBIT_RASTER_DEPTH_KERNEL, job, (uint32_t *)job.depth, resident_blocks, status, s, (uint32_t *)job.depth);
 }
 
 } // namespace orbit

@@ -71,6 +71,27 @@ __device__ __forceinline__ Vertex lds_vertex(const int4 *verts, uint32_t i) {
     return v;
 }
 
+__device__ __forceinline__ Vertex readlane_vertex(const Vertex &v, uint32_t src) {
+    Vertex out;
+    out.X = __builtin_amdgcn_readlane(v.X, (int)src), out.Y = __builtin_amdgcn_readlane(v.Y, (int)src);
+    out.d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.d), (int)src));
+    out.flags = (uint32_t)__builtin_amdgcn_readlane((int)v.flags, (int)src);
+    return out;
+}
+
+// The wave's mvp beyond phase 1: the clip path reads it again in phase 2; without kClipNear there is nothing to keep
+template <bool kKeep>
+struct KeptMvp {
+    float m[16];
+    __device__ __forceinline__ void keep(const float *mvp) {
+        for (int k = 0; k < 16; k++) m[k] = mvp[k];
+    }
+};
+template <>
+struct KeptMvp<false> {
+    __device__ __forceinline__ void keep(const float *) {}
+};
+
 // The samples (x_lo + x0 + k * step_x, y_lo + y0 + j * step_y) of the triangle's box: the lane path takes all of them
 // (x0 = y0 = 0, steps of 1), a lane of the wave path its own sample of every 8 x 8 tile.  -> inside samples; fragments
 // are added to `fragments`.
@@ -97,7 +118,13 @@ __device__ __forceinline__ uint32_t walk(const Sink &sink, uint32_t width, const
 
 // The body of a raster kernel: a resident grid of wave64s striding over the command list, in the phases named at the
 // top.  `id_base` is added to the command's position in the list before it goes into the sample's id.
-template <class Sink>
+//
+// kClipNear (ORBIT_RASTER_CLIP_NEAR, R3c): a lane whose triangle R3 rejects with a vertex in reads the three positions
+// again through the index words phase 1 checked, recomputes their clip coordinates from the wave's mvp and builds its
+// pieces in registers (raster_common.h); each piece then takes the route above.  The wave walk broadcasts a piece's
+// three Vertex records from the owning lane, as its vertices are not in LDS.  Without kClipNear the body is the code
+// as it was before the flag existed.
+template <bool kClipNear, class Sink>
 __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sink &sink, uint32_t id_base) {
     __shared__ int4 lds_verts[kRasterWaves][kMaxVertices];
     const uint32_t lane = threadIdx.x & 63u;
@@ -124,6 +151,7 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
         bool bad = first_word < index_base || vcount > 255u || (uint64_t)first_word > p.meshlet_data_words ||
                    ((uint64_t)first_index + 3ull * nt + 3ull) / 4ull > p.meshlet_data_words || entity >= p.entity_count ||
                    nt > Sink::kMaxTriangles;
+        KeptMvp<kClipNear> kept; // (set when !bad)
         if (!bad) {
             float mvp[16];
             {
@@ -131,6 +159,7 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
                 float m[16];
                 for (int k = 0; k < 16; k++) m[k] = model[k];
                 mat4_mul(p.view_proj, m, mvp);
+                kept.keep(mvp);
             }
             bool lane_bad = false;
             for (uint32_t v = lane; v < vcount; v += 64u) {
@@ -161,33 +190,89 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
         if (lane == 0u) n_triangles += nt;
         const uint32_t command_id = (id_base + i) << 8;
         wave_lds_sync();
-        for (uint32_t base = 0; base < nt; base += 64u) {
-            const uint32_t t = base + lane;
-            Setup s;
-            uint32_t corners = 0;
-            bool draw = false;
-            if (t < nt) {
-                const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
-                corners = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
-                const uint32_t outcome = setup_triangle(lds_vertex(verts, c[0]), lds_vertex(verts, c[1]),
-                                                        lds_vertex(verts, c[2]), p.width, p.height, cull_none, s);
-                for (uint32_t k = 1; k < 5u; k++) n_outcome[k] += outcome == k ? 1u : 0u;
-                draw = outcome == kDraw;
+        if constexpr (!kClipNear) {
+            for (uint32_t base = 0; base < nt; base += 64u) {
+                const uint32_t t = base + lane;
+                Setup s;
+                uint32_t corners = 0;
+                bool draw = false;
+                if (t < nt) {
+                    const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
+                    corners = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
+                    const uint32_t outcome = setup_triangle(lds_vertex(verts, c[0]), lds_vertex(verts, c[1]),
+                                                            lds_vertex(verts, c[2]), p.width, p.height, cull_none, s);
+                    for (uint32_t k = 1; k < 5u; k++) n_outcome[k] += outcome == k ? 1u : 0u;
+                    draw = outcome == kDraw;
+                }
+                // (boxes are at most 32768^2 samples: the product fits)
+                const bool small = draw && (s.x_hi - s.x_lo + 1) * (s.y_hi - s.y_lo + 1) <= kLaneBox;
+                if (small && walk(sink, p.width, s, 0, 0, 1, command_id | t, n_fragments) == 0u) n_outcome[kNoCoverage]++;
+                uint64_t large = __ballot(draw && !small);
+                while (large != 0ull) {
+                    const uint32_t src = (uint32_t)__builtin_ctzll(large);
+                    large &= large - 1ull;
+                    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)corners, (int)src);
+                    Setup ws;
+                    (void)setup_triangle(lds_vertex(verts, c & 0xFFu), lds_vertex(verts, (c >> 8) & 0xFFu),
+                                         lds_vertex(verts, c >> 16), p.width, p.height, cull_none, ws);
+                    const uint32_t inside = walk(sink, p.width, ws, (int32_t)(lane & 7u), (int32_t)(lane >> 3), 8,
+                                                 command_id | (base + src), n_fragments);
+                    if (__ballot(inside != 0u) == 0ull && lane == 0u) n_outcome[kNoCoverage]++;
+                }
             }
-            // (boxes are at most 32768^2 samples: the product fits)
-            const bool small = draw && (s.x_hi - s.x_lo + 1) * (s.y_hi - s.y_lo + 1) <= kLaneBox;
-            if (small && walk(sink, p.width, s, 0, 0, 1, command_id | t, n_fragments) == 0u) n_outcome[kNoCoverage]++;
-            uint64_t large = __ballot(draw && !small);
-            while (large != 0ull) {
-                const uint32_t src = (uint32_t)__builtin_ctzll(large);
-                large &= large - 1ull;
-                const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)corners, (int)src);
-                Setup ws;
-                (void)setup_triangle(lds_vertex(verts, c & 0xFFu), lds_vertex(verts, (c >> 8) & 0xFFu),
-                                     lds_vertex(verts, c >> 16), p.width, p.height, cull_none, ws);
-                const uint32_t inside = walk(sink, p.width, ws, (int32_t)(lane & 7u), (int32_t)(lane >> 3), 8,
-                                             command_id | (base + src), n_fragments);
-                if (__ballot(inside != 0u) == 0ull && lane == 0u) n_outcome[kNoCoverage]++;
+        } else {
+            for (uint32_t base = 0; base < nt; base += 64u) {
+                const uint32_t t = base + lane;
+                Pieces pc;
+                pc.count = 0u;
+                for (int k = 0; k < 4; k++) pc.u[k].X = pc.u[k].Y = 0, pc.u[k].d = 0.f, pc.u[k].flags = 0u;
+                if (t < nt) {
+                    const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
+                    pc.u[0] = lds_vertex(verts, c[0]), pc.u[1] = lds_vertex(verts, c[1]), pc.u[2] = lds_vertex(verts, c[2]);
+                    pc.u[3] = pc.u[2];
+                    const uint32_t any_out = (pc.u[0].flags | pc.u[1].flags | pc.u[2].flags) & kClipFail;
+                    const uint32_t all_out = pc.u[0].flags & pc.u[1].flags & pc.u[2].flags & kClipFail;
+                    if (any_out == 0u) {
+                        pc.count = 1u;
+                    } else if (all_out == 0u) { // R3c: a vertex in, a vertex out
+                        Clip cc[3];
+                        for (int k = 0; k < 3; k++) {
+                            const uint64_t g = vertex_base + p.meshlet_data[index_base + c[k]]; // in range: phase 1
+                            const float *src = (const float *)(p.vertices + g * p.vertex_stride + p.position_offset);
+                            cc[k] = clip_position(kept.m, src[0], src[1], src[2]);
+                        }
+                        clip_near_pieces(cc[0], cc[1], cc[2], w_f, h_f, pc);
+                    }
+                    if (pc.count == 0u) n_outcome[kClipSkipped]++;
+                }
+                uint32_t best = kNoCoverage; // of this lane's pieces; counted once below
+                const uint32_t rounds = __ballot(pc.count > 1u) != 0ull ? 2u : 1u;
+#pragma nounroll
+                for (uint32_t q = 0; q < rounds; q++) {
+                    Vertex v0, v1, v2;
+                    piece_vertices(pc, q, v0, v1, v2);
+                    Setup s;
+                    bool draw = false;
+                    if (q < pc.count) {
+                        const uint32_t outcome = setup_triangle(v0, v1, v2, p.width, p.height, cull_none, s);
+                        draw = outcome == kDraw;
+                        if (!draw) best = better_outcome(best, outcome);
+                    }
+                    const bool small = draw && (s.x_hi - s.x_lo + 1) * (s.y_hi - s.y_lo + 1) <= kLaneBox;
+                    if (small && walk(sink, p.width, s, 0, 0, 1, command_id | t, n_fragments) != 0u) best = kDraw;
+                    uint64_t large = __ballot(draw && !small);
+                    while (large != 0ull) {
+                        const uint32_t src = (uint32_t)__builtin_ctzll(large);
+                        large &= large - 1ull;
+                        const Vertex b0 = readlane_vertex(v0, src), b1 = readlane_vertex(v1, src), b2 = readlane_vertex(v2, src);
+                        Setup ws;
+                        (void)setup_triangle(b0, b1, b2, p.width, p.height, cull_none, ws);
+                        const uint32_t inside = walk(sink, p.width, ws, (int32_t)(lane & 7u), (int32_t)(lane >> 3), 8,
+                                                     command_id | (base + src), n_fragments);
+                        if (__ballot(inside != 0u) != 0ull && lane == src) best = kDraw;
+                    }
+                }
+                if (pc.count != 0u && best != kDraw) n_outcome[best]++;
             }
         }
         wave_lds_sync(); // the next command overwrites the wave's vertices

@@ -42,14 +42,15 @@ void raster_into(const HostJob &j, const Sink &sink, bool has_target, uint32_t i
         throw Panic("raster_depth: vertex_stride / position_offset");
     if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
         throw Panic("raster_depth: target size");
-    if (j.flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE)) throw Panic("raster_depth: unknown flags");
+    if (j.flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE | ORBIT_RASTER_CLIP_NEAR)) throw Panic("raster_depth: unknown flags");
     if (j.flags & ORBIT_RASTER_CLEAR) sink.clear((size_t)j.width * j.height);
     OrbitRasterStats st{};
-    const bool cull_none = (j.flags & ORBIT_RASTER_CULL_NONE) != 0u;
+    const bool cull_none = (j.flags & ORBIT_RASTER_CULL_NONE) != 0u, clip_near = (j.flags & ORBIT_RASTER_CLIP_NEAR) != 0u;
     const uint8_t *data_bytes = reinterpret_cast<const uint8_t *>(j.meshlet_data);
     const uint32_t count = j.draw_commands[0] < j.max_commands ? j.draw_commands[0] : j.max_commands;
     const float w_f = (float)j.width, h_f = (float)j.height;
     Vertex verts[256];
+    Clip clips[256]; // R3c reads them; a Vertex does not keep them
     for (uint32_t i = 0; i < count; i++) {
         const uint32_t *cmd = j.draw_commands + 1u + 7u * (size_t)i;
         const uint32_t index_count = cmd[0], first_index = cmd[2], index_base = cmd[3], entity = cmd[4];
@@ -75,32 +76,50 @@ void raster_into(const HostJob &j, const Sink &sink, bool has_target, uint32_t i
         for (uint32_t v = 0; v < vcount; v++) {
             float pos[3];
             std::memcpy(pos, j.vertices + (vertex_base + j.meshlet_data[index_base + v]) * j.vertex_stride + j.position_offset, 12);
-            verts[v] = transform_vertex(mvp, pos[0], pos[1], pos[2], w_f, h_f);
+            clips[v] = clip_position(mvp, pos[0], pos[1], pos[2]);
+            verts[v] = vertex_from_clip(clips[v], w_f, h_f);
         }
         for (uint32_t t = 0; t < nt; t++) {
             const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
-            Setup s;
-            switch (setup_triangle(verts[c[0]], verts[c[1]], verts[c[2]], j.width, j.height, cull_none, s)) {
-            case kClipSkipped: st.clip_skipped++; continue;
-            case kGuardSkipped: st.guard_skipped++; continue;
-            case kBackFacing: st.back_facing++; continue;
-            case kNoCoverage: st.no_coverage++; continue;
+            // the triangle itself, or with ORBIT_RASTER_CLIP_NEAR the pieces of one that R3 rejects (R3c)
+            Pieces pc;
+            pc.u[0] = verts[c[0]], pc.u[1] = verts[c[1]], pc.u[2] = pc.u[3] = verts[c[2]];
+            pc.count = 1u;
+            if (clip_near && ((pc.u[0].flags | pc.u[1].flags | pc.u[2].flags) & kClipFail))
+                clip_near_pieces(clips[c[0]], clips[c[1]], clips[c[2]], w_f, h_f, pc);
+            uint32_t best = kNoCoverage; // counted once, under the best outcome of the pieces
+            for (uint32_t q = 0; q < pc.count; q++) {
+                Vertex v0, v1, v2;
+                piece_vertices(pc, q, v0, v1, v2);
+                Setup s;
+                const uint32_t outcome = setup_triangle(v0, v1, v2, j.width, j.height, cull_none, s);
+                if (outcome != kDraw) {
+                    best = better_outcome(best, outcome);
+                    continue;
+                }
+                uint64_t inside = 0;
+                for (int32_t y = s.y_lo; y <= s.y_hi; y++)
+                    for (int32_t x = s.x_lo; x <= s.x_hi; x++) {
+                        const int32_t px = 256 * x + 128, py = 256 * y + 128;
+                        if (edge_at(s, 0, px, py) < 0 || edge_at(s, 1, px, py) < 0 || edge_at(s, 2, px, py) < 0) continue;
+                        inside++;
+                        const float d = depth_at(s, px, py);
+                        if (!(d > 0.0f)) continue;
+                        st.fragments++;
+                        uint32_t bits;
+                        std::memcpy(&bits, &d, 4);
+                        sink.write((size_t)y * j.width + (uint32_t)x, bits, (id_base + i) << 8 | t);
+                    }
+                if (inside != 0) best = kDraw;
+            }
+            if (pc.count == 0u) best = kClipSkipped;
+            switch (best) {
+            case kClipSkipped: st.clip_skipped++; break;
+            case kGuardSkipped: st.guard_skipped++; break;
+            case kBackFacing: st.back_facing++; break;
+            case kNoCoverage: st.no_coverage++; break;
             default: break;
             }
-            uint64_t inside = 0;
-            for (int32_t y = s.y_lo; y <= s.y_hi; y++)
-                for (int32_t x = s.x_lo; x <= s.x_hi; x++) {
-                    const int32_t px = 256 * x + 128, py = 256 * y + 128;
-                    if (edge_at(s, 0, px, py) < 0 || edge_at(s, 1, px, py) < 0 || edge_at(s, 2, px, py) < 0) continue;
-                    inside++;
-                    const float d = depth_at(s, px, py);
-                    if (!(d > 0.0f)) continue;
-                    st.fragments++;
-                    uint32_t bits;
-                    std::memcpy(&bits, &d, 4);
-                    sink.write((size_t)y * j.width + (uint32_t)x, bits, (id_base + i) << 8 | t);
-                }
-            if (inside == 0) st.no_coverage++;
         }
     }
     if (stats) *stats = st;

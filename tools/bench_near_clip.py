@@ -1,0 +1,124 @@
+"""What ORBIT_RASTER_CLIP_NEAR costs on the device.  GPU box; prints one JSON line and writes it to --out.
+
+Scene: tests/raster_scene.glb_scene(instances) at width x height, the pass-0 draw list of the oracle's culls, uploaded
+once.  Two cameras: the OUTSIDE camera of tools/bench_raster_visibility.py, where no triangle crosses the near plane
+that the flag could draw — there the flagged call against the unflagged one is the cost of the flag itself (the other
+kernel, its registers, its occupancy) —, and the INSIDE camera of tools/count_near_clip.py, flagged and unflagged.
+Each call clears its target and counts into its stats.  The four (call, flag) pairs of a camera are timed in the same
+process, alternating, `rounds` times after a round that is dropped; a figure is the median of the event-timed calls.
+  outside / inside: {depth_us, depth_clip_us, visibility_us, visibility_clip_us, depth_clip_over_plain,
+                     visibility_clip_over_plain, clip_skipped, clip_skipped_flagged, guard_skipped_flagged}
+  device_equals_host    the flagged results of both cameras against the host mirror, byte for byte
+No target is fixed.  Usage: python tools/bench_near_clip.py [--instances 200] [--width 1920] [--height 1080] [--iters 20]
+"""
+import argparse
+import importlib.util
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+
+def _timed(torch, fn, iters):
+    """Device times of `fn`'s work between two events, in µs (a sleep kernel keeps the stream busy while the host
+    enqueues every (event, work, event) triple)."""
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    torch.cuda._sleep(50_000_000)
+    for a, b in evs:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return [a.elapsed_time(b) * 1e3 for a, b in evs]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--instances", type=int, default=200)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "near_clip_mi355x.json"))
+    args = ap.parse_args()
+    import torch
+
+    import raster_scene as rs
+    from oracle import oracle
+    from orbit_amd import layouts as L
+    from orbit_amd import raster
+    from orbit_amd.engine import Engine
+
+    spec = importlib.util.spec_from_file_location("count_near_clip", os.path.join(ROOT, "tools", "count_near_clip.py"))
+    count_tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(count_tool)
+    oracle.build()
+    oracle.lib()
+    scene, (w, h) = rs.glb_scene(args.instances), (args.width, args.height)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).cuda()  # noqa: E731
+    d_data, d_vb, d_ent = up(scene.meshlet_data), up(scene.vertices), up(scene.entities)
+    depth = torch.zeros(w * h, dtype=torch.float32, device="cuda")
+    vis = torch.zeros(w * h, dtype=torch.int64, device="cuda")
+    stats = torch.zeros(32, dtype=torch.uint8, device="cuda")
+    eng = Engine(0, max_entities=4096, max_dispatches=1024, max_draws=1024)
+    line = {"instances": args.instances, "width": w, "height": h, "iters": args.iters, "rounds": args.rounds,
+            "device": torch.cuda.get_device_name(0)}
+    same = True
+    for name, cam in (("outside", rs.camera(w, h)), ("inside", rs.camera(w, h, count_tool.CAMERAS[1]))):
+        _, _, draw, _, _ = scene.cull(oracle, cam, 0)
+        n = int(draw[:4].view(np.uint32)[0])
+        d_draw = up(draw[:4 + 28 * n])
+        job = (d_draw, n, d_data, d_vb, len(scene.vertices), d_ent, scene.entity_count, rs.view_proj(cam))
+        calls = {
+            "depth": lambda: eng.raster_depth(*job, depth, w, h, clear=True, stats=stats),
+            "depth_clip": lambda: eng.raster_depth(*job, depth, w, h, clear=True, stats=stats, clip_near=True),
+            "visibility": lambda: eng.raster_visibility(*job, vis, w, h, clear=True, stats=stats),
+            "visibility_clip": lambda: eng.raster_visibility(*job, vis, w, h, clear=True, stats=stats, clip_near=True)}
+        for _ in range(3):
+            for fn in calls.values():
+                fn()
+        torch.cuda.synchronize()
+        eng.status()
+        samples = {k: [] for k in calls}
+        for r in range(1 + args.rounds):  # the first round also settles the clocks: its figures are dropped
+            for k, fn in calls.items():
+                t = _timed(torch, fn, args.iters)
+                if r:
+                    samples[k] += t
+        us = {k: float(np.median(t)) for k, t in samples.items()}
+        host_args = (draw, n, scene.meshlet_data, scene.vertices, len(scene.vertices), scene.entities, rs.view_proj(cam), w, h)
+        want_vis, want_stats, err = raster.host_raster_visibility(*host_args, clip_near=True)
+        _, off_stats, _ = raster.host_raster_visibility(*host_args)
+        depth.fill_(1), vis.fill_(1)
+        calls["depth_clip"]()
+        d_stats = stats.cpu().numpy().copy()
+        calls["visibility_clip"]()
+        torch.cuda.synchronize()
+        eng.status()
+        ok = bool(not err.any() and vis.cpu().numpy().view(np.uint64).tobytes() == want_vis.tobytes()
+                  and stats.cpu().numpy().tobytes() == want_stats.tobytes() == d_stats.tobytes()
+                  and depth.cpu().numpy().view(np.uint32).tobytes() == (want_vis >> np.uint64(32)).astype(np.uint32).tobytes())
+        same = same and ok
+        line[name] = {"commands": n, "triangles": int(want_stats["triangles"]),
+                      **{f"{k}_us": round(v, 1) for k, v in us.items()},
+                      "depth_clip_over_plain": round(us["depth_clip"] / us["depth"], 3),
+                      "visibility_clip_over_plain": round(us["visibility_clip"] / us["visibility"], 3),
+                      "clip_skipped": int(off_stats["clip_skipped"]), "clip_skipped_flagged": int(want_stats["clip_skipped"]),
+                      "guard_skipped": int(off_stats["guard_skipped"]), "guard_skipped_flagged": int(want_stats["guard_skipped"]),
+                      "fragments": int(off_stats["fragments"]), "fragments_flagged": int(want_stats["fragments"]),
+                      "device_equals_host": ok}
+    eng.close()
+    line["device_equals_host"] = same
+    text = json.dumps(line)
+    print(text)
+    with open(args.out, "w") as fh:
+        fh.write(text + "\n")
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
