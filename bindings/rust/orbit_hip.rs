@@ -118,6 +118,7 @@ pub struct OrbitRasterStats {
 pub const ORBIT_RASTER_CLEAR: u32 = 1;
 pub const ORBIT_RASTER_CULL_NONE: u32 = 2;
 pub const ORBIT_RASTER_CLIP_NEAR: u32 = 8; // (4 is no flag)
+pub const ORBIT_RASTER_WIDE_GUARD: u32 = 32; // (16 is no flag)
 pub const ORBIT_RASTER_MAX_DIM: u32 = 32768;
 
 /// orbit_raster_depth's argument block (160 B, HOST): DEVICE pointers; stats may be null

@@ -904,6 +904,43 @@ int32_t orbit_mesh_bounds(OrbitCtx *ctx, const OrbitMeshBoundsRange *ranges, uin
 /*     rint(ys * 256), ties to even.  A triangle with a vertex whose        */
 /*     |xs * 256| or |ys * 256| is not below 2^23 is not drawn              */
 /*     (guard_skipped).                                                     */
+/*  R4w only with ORBIT_RASTER_WIDE_GUARD (without it R4 stands as above):   */
+/*     xf = xs * 256 and yf = ys * 256 are R4's floats.  A vertex is NARROW  */
+/*     if |xf| < 2^23 and |yf| < 2^23 (R4's test, R4's X, Y); otherwise WIDE */
+/*     if |xf| < 2^60 and |yf| < 2^60 (false for NaN and infinity), with     */
+/*     X = (int64)rintf(xf), Y = (int64)rintf(yf) — exact, as a float of     */
+/*     2^23 or more is an integer (a coordinate still below 2^23 beside a    */
+/*     wide one rounds as in R4); anything else is OUT OF BAND.  A triangle, */
+/*     or a piece of R3c, whose vertices are all narrow goes through R5-R8   */
+/*     unchanged: the same bytes and counters as without the flag.  One with */
+/*     a vertex out of band is guard_skipped.  Any other is a WIDE TRIANGLE: */
+/*      R5w A is R5's expression in 128-bit integers; A == 0, the facing and */
+/*          the swap to A > 0 as in R5.                                      */
+/*      R6w the box is R6's formula on the int64 X, Y, clamped to the        */
+/*          target; E is R6's expression in 128-bit integers, with the same  */
+/*          top-left rule.  |X|, |Y| < 2^60, so a difference is below 2^61,  */
+/*          a product below 2^122 and A or an edge value below 2^123:        */
+/*          nothing overflows.                                               */
+/*      R7w the depth plane in double precision, every operation rounded on  */
+/*          its own, never contracted (d_i are R7's floats):                 */
+/*          A_d = (double)(int64)(A >> 64) * 2^64 + (double)(uint64)A;       */
+/*          D10 = (double)d1 - (double)d0; D20 = (double)d2 - (double)d0;    */
+/*          gx = (D10 * (double)(Y2-Y0) - D20 * (double)(Y1-Y0)) / A_d;      */
+/*          gy = (D20 * (double)(X1-X0) - D10 * (double)(X2-X0)) / A_d;      */
+/*          d = (float)(((double)d0 + gx * (double)(px-X0))                  */
+/*                      + gy * (double)(py-Y0));                             */
+/*          then d = min(d, 1), d > 0, R8 / V2 as before.                    */
+/*     Counters as before; in R3c's best-outcome rule guard_skipped now      */
+/*     means "a vertex out of band".  Consequences: a triangle R4 accepts is */
+/*     untouched, so the flagged result is pixel-wise >= the unflagged one   */
+/*     on the u32 view; V4 holds with the flag on both calls; a word still   */
+/*     depends on one triangle only.  An edge shared by a narrow and a wide  */
+/*     triangle has two narrow ends, hence the same integers on both sides;  */
+/*     an edge with a wide end is shared by two wide triangles that snap it  */
+/*     alike; E is the same expression either way, so the top-left rule      */
+/*     gives every sample on a shared edge to exactly one side: the mesh     */
+/*     stays watertight.  No vertex and no piece is added: the side planes   */
+/*     are still not clipped, the integers are wide enough not to need it.   */
 /*  R5 A = (X1-X0)(Y2-Y0) - (X2-X0)(Y1-Y0) in int64.  A == 0: no_coverage.  */
 /*     Front <=> A < 0 (cull BACK, front COUNTER_CLOCKWISE,                 */
 /*     pipeline.rs:201-202); back faces are dropped (back_facing) unless    */
@@ -960,6 +997,8 @@ ORBIT_STATIC_ASSERT(sizeof(OrbitRasterStats) == 32, "RasterStats is 32 B");
 #define ORBIT_RASTER_CULL_NONE 2u /* flags: draw back faces too */
 /* (bit 2, value 4, is not a flag: it stays unknown and rejected, the value the tests of unknown flags use) */
 #define ORBIT_RASTER_CLIP_NEAR 8u /* flags: R3c, near-plane clipping of the triangles R3 rejects */
+/* (bit 4, value 16, is not a flag either) */
+#define ORBIT_RASTER_WIDE_GUARD 32u /* flags: R4w, triangles with a vertex beyond R4's guard band are drawn */
 #define ORBIT_RASTER_MAX_DIM 32768u
 typedef struct OrbitRasterDepth { /* HOST block, 160 B; every pointer a DEVICE pointer */
     const void *draw_commands;          /* {u32 count; OrbitMeshletDrawCommand[max_commands]} */
@@ -1008,7 +1047,8 @@ int32_t orbit_raster_depth(OrbitCtx *ctx, const OrbitRasterDepth *job, void *str
 /* ORBIT_RASTER_CLEAR clears the buffer to 0 on the stream first; without   */
 /* it the call merges into what an earlier call left (the late pass), and   */
 /* command_base keeps the late list's ids apart from the early one's.       */
-/* ORBIT_RASTER_CULL_NONE and ORBIT_RASTER_CLIP_NEAR (R3c) as before.  No   */
+/* ORBIT_RASTER_CULL_NONE, ORBIT_RASTER_CLIP_NEAR (R3c) and                 */
+/* ORBIT_RASTER_WIDE_GUARD (R4w) as before.  No                             */
 /* allocation, no scratch, no host                                          */
 /* wait, the count is read on the device, kernels only: a graph captures    */
 /* the call on a fresh context's first call.                                */

@@ -102,6 +102,7 @@ class RasterDepth(C.Structure):  # OrbitRasterDepth
 
 RASTER_CLEAR, RASTER_CULL_NONE = 1, 2  # ORBIT_RASTER_CLEAR, ORBIT_RASTER_CULL_NONE
 RASTER_CLIP_NEAR = 8                   # ORBIT_RASTER_CLIP_NEAR (4 is no flag)
+RASTER_WIDE_GUARD = 32                 # ORBIT_RASTER_WIDE_GUARD (16 is no flag)
 RASTER_MAX_DIM = 32768                 # ORBIT_RASTER_MAX_DIM
 VIS_MAX_COMMANDS = 1 << 24             # ORBIT_VIS_MAX_COMMANDS
 

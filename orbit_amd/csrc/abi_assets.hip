@@ -18,7 +18,7 @@ int32_t check_vertex_layout(OrbitCtx *ctx, const char *who, uint32_t stride, uin
 int32_t check_raster_job(OrbitCtx *ctx, const char *who, uint32_t flags, uint32_t vertex_stride, uint32_t position_offset,
                          uint32_t width, uint32_t height, const void *draw_commands, const void *meshlet_data,
                          const void *vertices, const void *entity_data, const void *stats) {
-    if (flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE | ORBIT_RASTER_CLIP_NEAR)) return fail(ctx, ORBIT_E_INVALID, "%s: flags %#x", who, flags);
+    if (flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE | ORBIT_RASTER_CLIP_NEAR | ORBIT_RASTER_WIDE_GUARD)) return fail(ctx, ORBIT_E_INVALID, "%s: flags %#x", who, flags);
     if (const int32_t rc = check_vertex_layout(ctx, who, vertex_stride, position_offset)) return rc;
     if (width == 0 || height == 0 || width > ORBIT_RASTER_MAX_DIM || height > ORBIT_RASTER_MAX_DIM)
         return fail(ctx, ORBIT_E_INVALID, "%s: target %u x %u (1..%u each)", who, width, height, ORBIT_RASTER_MAX_DIM);
@@ -27,6 +27,11 @@ int32_t check_raster_job(OrbitCtx *ctx, const char *who, uint32_t flags, uint32_
         ((uintptr_t)entity_data & 15u))
         return fail(ctx, ORBIT_E_INVALID, "%s: every buffer must be 4-B aligned, entity_data 16-B aligned", who);
     return ORBIT_OK;
+}
+
+// the resident grid of the kernel that `flags` launch: R4w's, R3c's or the plain one
+uint32_t blocks_of_flags(uint32_t flags, uint32_t wide, uint32_t clip, uint32_t plain) {
+    return (flags & ORBIT_RASTER_WIDE_GUARD) ? wide : (flags & ORBIT_RASTER_CLIP_NEAR) ? clip : plain;
 }
 
 } // namespace
@@ -89,7 +94,7 @@ int32_t orbit_raster_depth(OrbitCtx *ctx, const OrbitRasterDepth *job, void *str
         return rc;
     if (!j.depth || ((uintptr_t)j.depth & 3u)) return fail(ctx, ORBIT_E_INVALID, "raster_depth: depth is NULL or not 4-B aligned");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_raster_depth(j, (j.flags & ORBIT_RASTER_CLIP_NEAR) ? ctx->raster_clip_blocks : ctx->raster_blocks, ctx->status, (hipStream_t)stream);
+    const hipError_t e = launch_raster_depth(j, blocks_of_flags(j.flags, ctx->raster_wide_blocks, ctx->raster_clip_blocks, ctx->raster_blocks), ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_depth");
     return ORBIT_OK;
 }
@@ -109,7 +114,7 @@ int32_t orbit_raster_visibility(OrbitCtx *ctx, const OrbitRasterVisibility *job,
     if (!j.visibility || ((uintptr_t)j.visibility & 7u))
         return fail(ctx, ORBIT_E_INVALID, "raster_visibility: visibility is NULL or not 8-B aligned");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_raster_visibility(j, (j.flags & ORBIT_RASTER_CLIP_NEAR) ? ctx->visibility_clip_blocks : ctx->visibility_blocks, ctx->status, (hipStream_t)stream);
+    const hipError_t e = launch_raster_visibility(j, blocks_of_flags(j.flags, ctx->visibility_wide_blocks, ctx->visibility_clip_blocks, ctx->visibility_blocks), ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_visibility");
     return ORBIT_OK;
 }

@@ -152,6 +152,8 @@ int32_t orbit_ctx_create(int32_t device_id, const OrbitCaps *caps_in, OrbitCtx *
     ctx->visibility_blocks = ctx->num_cus * raster_visibility_blocks_per_cu(false);
     ctx->raster_clip_blocks = ctx->num_cus * raster_depth_blocks_per_cu(true);
     ctx->visibility_clip_blocks = ctx->num_cus * raster_visibility_blocks_per_cu(true);
+    ctx->raster_wide_blocks = ctx->num_cus * raster_depth_wide_blocks_per_cu();
+    ctx->visibility_wide_blocks = ctx->num_cus * raster_visibility_wide_blocks_per_cu();
     ctx->caps = caps;
     ctx->rec_shift = rec_shift;
 

@@ -379,12 +379,18 @@ uint32_t raster_depth_blocks_per_cu(bool clip_near);
 // raster_depth_clip.hip: what the two above hand ORBIT_RASTER_CLIP_NEAR over to
 hipError_t launch_raster_depth_clip(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
 uint32_t raster_depth_clip_blocks_per_cu();
+// raster_depth_wide.hip: what launch_raster_depth hands ORBIT_RASTER_WIDE_GUARD over to (R4w; with or without CLIP_NEAR)
+hipError_t launch_raster_depth_wide(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
+uint32_t raster_depth_wide_blocks_per_cu();
 // raster_visibility.hip: orbit_raster_visibility — as launch_raster_depth, into the u64 buffer (V1-V4)
 hipError_t launch_raster_visibility(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
 uint32_t raster_visibility_blocks_per_cu(bool clip_near);
 // raster_visibility_clip.hip: the same for ORBIT_RASTER_CLIP_NEAR
 hipError_t launch_raster_visibility_clip(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
 uint32_t raster_visibility_clip_blocks_per_cu();
+// raster_visibility_wide.hip: the same for ORBIT_RASTER_WIDE_GUARD
+hipError_t launch_raster_visibility_wide(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
+uint32_t raster_visibility_wide_blocks_per_cu();
 // ... and orbit_visibility_resolve: one launch clears command_pixels and stats, the next reads every word once
 hipError_t launch_visibility_resolve(const OrbitVisibilityResolve &job, uint32_t num_cus, hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the

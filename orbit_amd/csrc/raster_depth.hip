@@ -10,7 +10,7 @@
 
 #ifndef ORBIT_RASTER_CLIP
 #define ORBIT_RASTER_CLIP 0 // 1: raster_depth_clip.hip compiles this file into the ORBIT_RASTER_CLIP_NEAR kernel and its launch
-#endif
+#endif                      // 2: raster_depth_wide.hip, into the ORBIT_RASTER_WIDE_GUARD kernel (with or without CLIP_NEAR)
 
 namespace orbit {
 namespace {
@@ -21,7 +21,8 @@ using namespace raster;
 struct DepthSink {
     static constexpr uint32_t kMaxTriangles = ~0u; // no limit: the depth word carries no triangle index
     uint32_t *depth;
-    __device__ __forceinline__ bool write(const Setup &s, int32_t x, int32_t y, uint32_t width, uint32_t /*id*/) const {
+    template <class AnySetup> // Setup (R7) or SetupW (R7w)
+    __device__ __forceinline__ bool write(const AnySetup &s, int32_t x, int32_t y, uint32_t width, uint32_t /*id*/) const {
         const float d = depth_at(s, 256 * x + 128, 256 * y + 128);
         if (!(d > 0.0f)) return false;
         const uint32_t bits = __float_as_uint(d);
@@ -37,11 +38,16 @@ __global__ __launch_bounds__(kRasterThreads) void raster_depth_kernel(const Rast
     raster_commands<false>(p, DepthSink{depth}, 0u);
 }
 #define ORBIT_RASTER_DEPTH_KERNEL raster_depth_kernel
-#else // ORBIT_RASTER_CLIP_NEAR (R3c), a translation unit of its own (raster_depth_clip.hip)
+#elif ORBIT_RASTER_CLIP == 1 // ORBIT_RASTER_CLIP_NEAR (R3c), a translation unit of its own (raster_depth_clip.hip)
 __global__ __launch_bounds__(kRasterThreads) void raster_depth_clip_kernel(const RasterParams p, uint32_t *const depth) {
     raster_commands<true>(p, DepthSink{depth}, 0u);
 }
 #define ORBIT_RASTER_DEPTH_KERNEL raster_depth_clip_kernel
+#else // ORBIT_RASTER_WIDE_GUARD (R4w), a translation unit of its own (raster_depth_wide.hip)
+__global__ __launch_bounds__(kRasterThreads) void raster_depth_wide_kernel(const RasterParams p, uint32_t *const depth) {
+    raster_commands<false, DepthSink, true>(p, DepthSink{depth}, 0u);
+}
+#define ORBIT_RASTER_DEPTH_KERNEL raster_depth_wide_kernel
 #endif
 
 } // namespace
@@ -49,8 +55,10 @@ __global__ __launch_bounds__(kRasterThreads) void raster_depth_clip_kernel(const
 #if !ORBIT_RASTER_CLIP
 uint32_t raster_depth_blocks_per_cu(bool clip_near) {
     if (clip_near) return raster_depth_clip_blocks_per_cu();
-#else
+#elif ORBIT_RASTER_CLIP == 1
 uint32_t raster_depth_clip_blocks_per_cu() {
+#else
+uint32_t raster_depth_wide_blocks_per_cu() {
 #endif
     int n = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ORBIT_RASTER_DEPTH_KERNEL, (int)kRasterThreads, 0);
@@ -59,9 +67,12 @@ uint32_t raster_depth_clip_blocks_per_cu() {
 
 #if !ORBIT_RASTER_CLIP
 hipError_t launch_raster_depth(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
+    if (job.flags & ORBIT_RASTER_WIDE_GUARD) return launch_raster_depth_wide(job, resident_blocks, status, s);
     if (job.flags & ORBIT_RASTER_CLIP_NEAR) return launch_raster_depth_clip(job, resident_blocks, status, s);
-#else
+#elif ORBIT_RASTER_CLIP == 1
 hipError_t launch_raster_depth_clip(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
+#else
+hipError_t launch_raster_depth_wide(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
 #endif
     return launch_raster(ORBIT_RASTER_DEPTH_KERNEL, job, (uint32_t *)job.depth, resident_blocks, status, s, (uint32_t *)job.depth);
 }

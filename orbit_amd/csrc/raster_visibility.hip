@@ -15,7 +15,7 @@
 
 #ifndef ORBIT_RASTER_CLIP
 #define ORBIT_RASTER_CLIP 0 // 1: raster_visibility_clip.hip compiles this file into the ORBIT_RASTER_CLIP_NEAR kernel and its launch
-#endif
+#endif                      // 2: raster_visibility_wide.hip, into the ORBIT_RASTER_WIDE_GUARD kernel (with or without CLIP_NEAR)
 
 namespace orbit {
 namespace {
@@ -28,7 +28,8 @@ constexpr uint32_t kResolveThreads = 256, kResolveWaves = kResolveThreads / 64;
 struct VisibilitySink {
     static constexpr uint32_t kMaxTriangles = 256u; // V3: the triangle index has 8 bits
     unsigned long long *visibility;
-    __device__ __forceinline__ bool write(const Setup &s, int32_t x, int32_t y, uint32_t width, uint32_t id) const {
+    template <class AnySetup> // Setup (R7) or SetupW (R7w)
+    __device__ __forceinline__ bool write(const AnySetup &s, int32_t x, int32_t y, uint32_t width, uint32_t id) const {
         const float d = depth_at(s, 256 * x + 128, 256 * y + 128);
         if (!(d > 0.0f)) return false;
         const unsigned long long word = (unsigned long long)__float_as_uint(d) << 32 | id;
@@ -44,13 +45,19 @@ __global__ __launch_bounds__(kRasterThreads) void raster_visibility_kernel(const
     raster_commands<false>(p, sink, command_base);
 }
 #define ORBIT_RASTER_VISIBILITY_KERNEL raster_visibility_kernel
-#else // ORBIT_RASTER_CLIP_NEAR (R3c), a translation unit of its own (raster_visibility_clip.hip): every piece carries
-      // the original triangle's index
+#elif ORBIT_RASTER_CLIP == 1 // ORBIT_RASTER_CLIP_NEAR (R3c), a translation unit of its own (raster_visibility_clip.hip): every
+                             // piece carries the original triangle's index
 __global__ __launch_bounds__(kRasterThreads) void raster_visibility_clip_kernel(const RasterParams p, const VisibilitySink sink,
                                                                                 const uint32_t command_base) {
     raster_commands<true>(p, sink, command_base);
 }
 #define ORBIT_RASTER_VISIBILITY_KERNEL raster_visibility_clip_kernel
+#else // ORBIT_RASTER_WIDE_GUARD (R4w), a translation unit of its own (raster_visibility_wide.hip)
+__global__ __launch_bounds__(kRasterThreads) void raster_visibility_wide_kernel(const RasterParams p, const VisibilitySink sink,
+                                                                                const uint32_t command_base) {
+    raster_commands<false, VisibilitySink, true>(p, sink, command_base);
+}
+#define ORBIT_RASTER_VISIBILITY_KERNEL raster_visibility_wide_kernel
 #endif
 
 #if !ORBIT_RASTER_CLIP
@@ -107,8 +114,10 @@ __global__ __launch_bounds__(kResolveThreads) void visibility_resolve_kernel(con
 #if !ORBIT_RASTER_CLIP
 uint32_t raster_visibility_blocks_per_cu(bool clip_near) {
     if (clip_near) return raster_visibility_clip_blocks_per_cu();
-#else
+#elif ORBIT_RASTER_CLIP == 1
 uint32_t raster_visibility_clip_blocks_per_cu() {
+#else
+uint32_t raster_visibility_wide_blocks_per_cu() {
 #endif
     int n = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ORBIT_RASTER_VISIBILITY_KERNEL, (int)kRasterThreads, 0);
@@ -117,9 +126,12 @@ uint32_t raster_visibility_clip_blocks_per_cu() {
 
 #if !ORBIT_RASTER_CLIP
 hipError_t launch_raster_visibility(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
+    if (job.flags & ORBIT_RASTER_WIDE_GUARD) return launch_raster_visibility_wide(job, resident_blocks, status, s);
     if (job.flags & ORBIT_RASTER_CLIP_NEAR) return launch_raster_visibility_clip(job, resident_blocks, status, s);
-#else
+#elif ORBIT_RASTER_CLIP == 1
 hipError_t launch_raster_visibility_clip(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
+#else
+hipError_t launch_raster_visibility_wide(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
 #endif
     return launch_raster(ORBIT_RASTER_VISIBILITY_KERNEL, job, (unsigned long long *)job.visibility, resident_blocks, status, s,
                          VisibilitySink{(unsigned long long *)job.visibility}, job.command_base);

@@ -13,9 +13,12 @@
 //            of the front faces of the test scene cover no sample at all); a larger one is taken by the whole wave, one
 //            at a time (ballot, the corners broadcast, every lane repeats the setup, lanes take the 8 x 8 tiles of the
 //            box).  Edge functions are stepped in int64, the same integers as evaluating them per sample.
+// Behind ORBIT_RASTER_WIDE_GUARD (kWide, R4w) a triangle with a vertex beyond R4's band is taken by the whole wave as well,
+// but not box by box: walk_wide rejects 64 x 64 blocks, then 8 x 8 tiles, and evaluates samples only in the tiles left.
 // A sink has
 //   static constexpr uint32_t kMaxTriangles   a command with more triangles is a range error (V3); ~0u: no limit
-//   bool write(const Setup &, x, y, width, id) const   R7 + the merge of one inside sample -> it is a fragment (d > 0)
+//   bool write(const Setup &, x, y, width, id) const   R7 + the merge of one inside sample -> it is a fragment (d > 0);
+//                                                      and the same for a SetupW (R7w)
 // where id = (id_base + the command's position) << 8 | triangle index.  Both sinks merge by atomicMax: the result does
 // not depend on scheduling or command order.
 #pragma once
@@ -116,6 +119,49 @@ __device__ __forceinline__ uint32_t walk(const Sink &sink, uint32_t width, const
     return inside;
 }
 
+// R6w-R7w of one wide triangle by the whole wave (`s` is wave-uniform).  A near-cut triangle has a box that is most of
+// the target and a coverage that is a wedge of it, so the box is not stepped: a lane takes a 64 x 64 block of it (on the
+// target's grid) and asks rect_outside_wide; of each block that stays a lane takes an 8 x 8 tile and asks again; of each
+// tile that stays a lane takes a sample.  The rectangle test is exact in the direction used (raster_common.h), so the
+// samples found inside are the samples inside.  -> this lane's inside samples.
+template <class Sink>
+__device__ __forceinline__ uint32_t walk_wide(const Sink &sink, uint32_t width, const SetupW &s, uint32_t lane, uint32_t id,
+                                              uint32_t &fragments) {
+    uint32_t inside = 0;
+    const int32_t bx0 = s.x_lo >> 6, by0 = s.y_lo >> 6;
+    const uint32_t blocks_x = (uint32_t)((s.x_hi >> 6) - bx0 + 1), blocks = blocks_x * (uint32_t)((s.y_hi >> 6) - by0 + 1); // <= 512^2
+    for (uint32_t first = 0; first < blocks; first += 64u) {
+        const uint32_t b = first + lane;
+        int32_t ox = 0, oy = 0; // the block's first pixel
+        bool live = false;
+        if (b < blocks) { // (every block of the range holds pixels of the box)
+            ox = (bx0 + (int32_t)(b % blocks_x)) << 6, oy = (by0 + (int32_t)(b / blocks_x)) << 6;
+            live = !rect_outside_wide(s, imax(ox, s.x_lo), imax(oy, s.y_lo), imin(ox + 63, s.x_hi), imin(oy + 63, s.y_hi));
+        }
+        uint64_t live_blocks = __ballot(live);
+        while (live_blocks != 0ull) {
+            const uint32_t src = (uint32_t)__builtin_ctzll(live_blocks);
+            live_blocks &= live_blocks - 1ull;
+            const int32_t wx = __builtin_amdgcn_readlane(ox, (int)src), wy = __builtin_amdgcn_readlane(oy, (int)src);
+            const int32_t tx = wx + 8 * (int32_t)(lane & 7u), ty = wy + 8 * (int32_t)(lane >> 3);
+            const int32_t x0 = imax(tx, s.x_lo), y0 = imax(ty, s.y_lo), x1 = imin(tx + 7, s.x_hi), y1 = imin(ty + 7, s.y_hi);
+            uint64_t live_tiles = __ballot(x0 <= x1 && y0 <= y1 && !rect_outside_wide(s, x0, y0, x1, y1));
+            while (live_tiles != 0ull) {
+                const uint32_t tile = (uint32_t)__builtin_ctzll(live_tiles);
+                live_tiles &= live_tiles - 1ull;
+                const int32_t x = wx + 8 * (int32_t)(tile & 7u) + (int32_t)(lane & 7u);
+                const int32_t y = wy + 8 * (int32_t)(tile >> 3) + (int32_t)(lane >> 3);
+                // (inside the box: inside the target)
+                if (x >= s.x_lo && x <= s.x_hi && y >= s.y_lo && y <= s.y_hi && inside_wide(s, x, y)) {
+                    inside++;
+                    fragments += sink.write(s, x, y, width, id) ? 1u : 0u;
+                }
+            }
+        }
+    }
+    return inside;
+}
+
 // The body of a raster kernel: a resident grid of wave64s striding over the command list, in the phases named at the
 // top.  `id_base` is added to the command's position in the list before it goes into the sample's id.
 //
@@ -124,7 +170,13 @@ __device__ __forceinline__ uint32_t walk(const Sink &sink, uint32_t width, const
 // pieces in registers (raster_common.h); each piece then takes the route above.  The wave walk broadcasts a piece's
 // three Vertex records from the owning lane, as its vertices are not in LDS.  Without kClipNear the body is the code
 // as it was before the flag existed.
-template <bool kClipNear, class Sink>
+//
+// kWide (ORBIT_RASTER_WIDE_GUARD, R4w): phase 1 keeps a guard-failing vertex's xf, yf in its LDS record; phase 2 is the
+// kClipNear form with ORBIT_RASTER_CLIP_NEAR read from the flag word (a wave-uniform branch, so the flag pair costs two
+// kernels, not four); a piece with every vertex narrow takes the routes above unchanged, one with a vertex out of band
+// is guard_skipped, and a wide one is taken by the whole wave (walk_wide), its three Vertex records broadcast from the
+// owning lane and its setup wave-uniform.  Without kWide nothing of this is compiled.
+template <bool kClipNear, class Sink, bool kWide = false>
 __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sink &sink, uint32_t id_base) {
     __shared__ int4 lds_verts[kRasterWaves][kMaxVertices];
     const uint32_t lane = threadIdx.x & 63u;
@@ -151,7 +203,7 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
         bool bad = first_word < index_base || vcount > 255u || (uint64_t)first_word > p.meshlet_data_words ||
                    ((uint64_t)first_index + 3ull * nt + 3ull) / 4ull > p.meshlet_data_words || entity >= p.entity_count ||
                    nt > Sink::kMaxTriangles;
-        KeptMvp<kClipNear> kept; // (set when !bad)
+        KeptMvp<kClipNear || kWide> kept; // (set when !bad)
         if (!bad) {
             float mvp[16];
             {
@@ -168,7 +220,7 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
                 out.X = out.Y = 0, out.d = 0.f, out.flags = kClipFail;
                 if (g < p.vertex_count) {
                     const float *src = (const float *)(p.vertices + g * p.vertex_stride + p.position_offset);
-                    out = transform_vertex(mvp, src[0], src[1], src[2], w_f, h_f);
+                    out = transform_vertex(mvp, src[0], src[1], src[2], w_f, h_f, kWide);
                 } else {
                     lane_bad = true;
                 }
@@ -190,7 +242,77 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
         if (lane == 0u) n_triangles += nt;
         const uint32_t command_id = (id_base + i) << 8;
         wave_lds_sync();
-        if constexpr (!kClipNear) {
+        if constexpr (kWide) {
+            const bool clip_near = (p.flags & ORBIT_RASTER_CLIP_NEAR) != 0u; // (wave-uniform)
+            for (uint32_t base = 0; base < nt; base += 64u) {
+                const uint32_t t = base + lane;
+                Pieces pc;
+                pc.count = 0u;
+                for (int k = 0; k < 4; k++) pc.u[k].X = pc.u[k].Y = 0, pc.u[k].d = 0.f, pc.u[k].flags = 0u;
+                if (t < nt) {
+                    const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
+                    pc.u[0] = lds_vertex(verts, c[0]), pc.u[1] = lds_vertex(verts, c[1]), pc.u[2] = lds_vertex(verts, c[2]);
+                    pc.u[3] = pc.u[2];
+                    const uint32_t any_out = (pc.u[0].flags | pc.u[1].flags | pc.u[2].flags) & kClipFail;
+                    const uint32_t all_out = pc.u[0].flags & pc.u[1].flags & pc.u[2].flags & kClipFail;
+                    if (any_out == 0u) {
+                        pc.count = 1u;
+                    } else if (clip_near && all_out == 0u) { // R3c: a vertex in, a vertex out
+                        Clip cc[3];
+                        for (int k = 0; k < 3; k++) {
+                            const uint64_t g = vertex_base + p.meshlet_data[index_base + c[k]]; // in range: phase 1
+                            const float *src = (const float *)(p.vertices + g * p.vertex_stride + p.position_offset);
+                            cc[k] = clip_position(kept.m, src[0], src[1], src[2]);
+                        }
+                        clip_near_pieces(cc[0], cc[1], cc[2], w_f, h_f, pc, true);
+                    }
+                    if (pc.count == 0u) n_outcome[kClipSkipped]++;
+                }
+                uint32_t best = kNoCoverage; // of this lane's pieces; counted once below
+                const uint32_t rounds = __ballot(pc.count > 1u) != 0ull ? 2u : 1u;
+#pragma nounroll
+                for (uint32_t q = 0; q < rounds; q++) {
+                    Vertex v0, v1, v2;
+                    piece_vertices(pc, q, v0, v1, v2);
+                    Setup s;
+                    bool draw = false, wide = false;
+                    if (q < pc.count) {
+                        wide = is_wide_triangle(v0, v1, v2);
+                        if (!wide) { // all narrow, or a vertex out of band: guard_skipped
+                            const uint32_t outcome = setup_triangle(v0, v1, v2, p.width, p.height, cull_none, s);
+                            draw = outcome == kDraw;
+                            if (!draw) best = better_outcome(best, outcome);
+                        }
+                    }
+                    const bool small = draw && (s.x_hi - s.x_lo + 1) * (s.y_hi - s.y_lo + 1) <= kLaneBox;
+                    if (small && walk(sink, p.width, s, 0, 0, 1, command_id | t, n_fragments) != 0u) best = kDraw;
+                    uint64_t large = __ballot(draw && !small);
+                    while (large != 0ull) {
+                        const uint32_t src = (uint32_t)__builtin_ctzll(large);
+                        large &= large - 1ull;
+                        const Vertex b0 = readlane_vertex(v0, src), b1 = readlane_vertex(v1, src), b2 = readlane_vertex(v2, src);
+                        Setup ws;
+                        (void)setup_triangle(b0, b1, b2, p.width, p.height, cull_none, ws);
+                        const uint32_t inside = walk(sink, p.width, ws, (int32_t)(lane & 7u), (int32_t)(lane >> 3), 8,
+                                                     command_id | (base + src), n_fragments);
+                        if (__ballot(inside != 0u) != 0ull && lane == src) best = kDraw;
+                    }
+                    uint64_t wides = __ballot(wide);
+                    while (wides != 0ull) {
+                        const uint32_t src = (uint32_t)__builtin_ctzll(wides);
+                        wides &= wides - 1ull;
+                        const Vertex b0 = readlane_vertex(v0, src), b1 = readlane_vertex(v1, src), b2 = readlane_vertex(v2, src);
+                        SetupW ws;
+                        const uint32_t outcome = setup_triangle_wide(b0, b1, b2, p.width, p.height, cull_none, ws); // (wave-uniform)
+                        uint32_t inside = 0;
+                        if (outcome == kDraw) inside = walk_wide(sink, p.width, ws, lane, command_id | (base + src), n_fragments);
+                        const bool covered = __ballot(inside != 0u) != 0ull;
+                        if (lane == src) best = covered ? (uint32_t)kDraw : better_outcome(best, outcome == kDraw ? (uint32_t)kNoCoverage : outcome);
+                    }
+                }
+                if (pc.count != 0u && best != kDraw) n_outcome[best]++;
+            }
+        } else if constexpr (!kClipNear) {
             for (uint32_t base = 0; base < nt; base += 64u) {
                 const uint32_t t = base + lane;
                 Setup s;

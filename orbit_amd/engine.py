@@ -37,7 +37,8 @@ def _host_bytes(x, nbytes):
 
 
 def _raster_job(j, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, entity_count, view_proj,
-                width, height, clear, cull_none, stats, vertex_stride, position_offset, meshlet_data_words, clip_near=False):
+                width, height, clear, cull_none, stats, vertex_stride, position_offset, meshlet_data_words, clip_near=False,
+                wide_guard=False):
     """The fields that _lib.RasterDepth and _lib.RasterVisibility share, filled into `j` -> j."""
     nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
     j.draw_commands, j.meshlet_data, j.vertices = _ptr(draw_commands), _ptr(meshlet_data), _ptr(vertices)
@@ -46,7 +47,7 @@ def _raster_job(j, draw_commands, max_commands, meshlet_data, vertices, vertex_c
     j.vertex_count, j.max_commands, j.entity_count = int(vertex_count), int(max_commands), int(entity_count)
     j.vertex_stride, j.position_offset, j.width, j.height = int(vertex_stride), int(position_offset), int(width), int(height)
     j.flags = ((_lib.RASTER_CLEAR if clear else 0) | (_lib.RASTER_CULL_NONE if cull_none else 0)
-               | (_lib.RASTER_CLIP_NEAR if clip_near else 0))
+               | (_lib.RASTER_CLIP_NEAR if clip_near else 0) | (_lib.RASTER_WIDE_GUARD if wide_guard else 0))
     j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
     return j
 
@@ -333,18 +334,20 @@ class Engine:
     # -- the depth prepass of a draw-command buffer in compute (orbit_raster_depth)
     def raster_depth(self, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, entity_count,
                      view_proj, depth, width, height, clear=False, cull_none=False, stats=None, vertex_stride=12,
-                     position_offset=0, meshlet_data_words=None, stream=None, clip_near=False):
+                     position_offset=0, meshlet_data_words=None, stream=None, clip_near=False, wide_guard=False):
         """Rasterises the {u32 count; 28-B commands} of the device tensor `draw_commands` (what meshlet_cull wrote; the
         count is read on the device and clamped by max_commands) into the width x height float tensor `depth`:
         reversed z, max-merged by atomicMax into what it holds, or into zeros with clear=True (LoadOp::Clear(0.0)).
         `view_proj`: 16 floats, column-major; `vertices`: position i = 3 floats at i * vertex_stride + position_offset;
         `entity_data`: 128-B rows.  `stats`: device tensor of 32 bytes (layouts.RASTER_STATS), cleared by the call.
         Back faces are culled unless cull_none.  clip_near (ORBIT_RASTER_CLIP_NEAR): a triangle crossing the near plane
-        is cut there and drawn instead of skipped.  Byte-equal to orbit_amd.raster.host_raster_depth on host copies.
-        Enqueued on `stream`; a command that points out of range is skipped and reported by status() (ORBIT_E_RANGE)."""
+        is cut there and drawn instead of skipped.  wide_guard (ORBIT_RASTER_WIDE_GUARD): a triangle with a vertex
+        beyond the guard band (up to 2^60 sub-pixel units) is drawn instead of guard_skipped.  Byte-equal to
+        orbit_amd.raster.host_raster_depth on host copies.  Enqueued on `stream`; a command that points out of range is
+        skipped and reported by status() (ORBIT_E_RANGE)."""
         j = _raster_job(_lib.RasterDepth(), draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data,
                         entity_count, view_proj, width, height, clear, cull_none, stats, vertex_stride, position_offset,
-                        meshlet_data_words, clip_near)
+                        meshlet_data_words, clip_near, wide_guard)
         j.depth = _ptr(depth)
         _lib.check(self._lib.orbit_raster_depth(self._ctx, C.byref(j), _stream(stream)), self._ctx)
 
@@ -352,17 +355,17 @@ class Engine:
     def raster_visibility(self, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data,
                           entity_count, view_proj, visibility, width, height, command_base=0, clear=False,
                           cull_none=False, stats=None, vertex_stride=12, position_offset=0, meshlet_data_words=None,
-                          stream=None, clip_near=False):
+                          stream=None, clip_near=False, wide_guard=False):
         """raster_depth into the width x height u64 tensor `visibility` (8-B aligned): an inside sample with depth d > 0
         of triangle t of the i-th command merges float_bits(d) << 32 | (command_base + i) << 8 | t by a 64-bit
         atomicMax into what the buffer holds, or into zeros with clear=True; 0 is an uncovered pixel.  The high halves
         are raster_depth's depth bytes.  A command with more than 256 triangles is skipped like one that points out of
-        range (status(): ORBIT_E_RANGE); command_base + max_commands may not exceed 2^24.  clip_near as raster_depth's: the
-        pieces of a cut triangle carry its own index.  Byte-equal to
+        range (status(): ORBIT_E_RANGE); command_base + max_commands may not exceed 2^24.  clip_near and wide_guard as
+        raster_depth's: the pieces of a cut triangle carry its own index.  Byte-equal to
         orbit_amd.raster.host_raster_visibility on host copies.  Enqueued on `stream`."""
         j = _raster_job(_lib.RasterVisibility(), draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data,
                         entity_count, view_proj, width, height, clear, cull_none, stats, vertex_stride, position_offset,
-                        meshlet_data_words, clip_near)
+                        meshlet_data_words, clip_near, wide_guard)
         j.visibility, j.command_base = _ptr(visibility), int(command_base)
         _lib.check(self._lib.orbit_raster_visibility(self._ctx, C.byref(j), _stream(stream)), self._ctx)
 

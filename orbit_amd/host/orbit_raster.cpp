@@ -42,10 +42,11 @@ void raster_into(const HostJob &j, const Sink &sink, bool has_target, uint32_t i
         throw Panic("raster_depth: vertex_stride / position_offset");
     if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
         throw Panic("raster_depth: target size");
-    if (j.flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE | ORBIT_RASTER_CLIP_NEAR)) throw Panic("raster_depth: unknown flags");
+    if (j.flags & ~(ORBIT_RASTER_CLEAR | ORBIT_RASTER_CULL_NONE | ORBIT_RASTER_CLIP_NEAR | ORBIT_RASTER_WIDE_GUARD)) throw Panic("raster_depth: unknown flags");
     if (j.flags & ORBIT_RASTER_CLEAR) sink.clear((size_t)j.width * j.height);
     OrbitRasterStats st{};
     const bool cull_none = (j.flags & ORBIT_RASTER_CULL_NONE) != 0u, clip_near = (j.flags & ORBIT_RASTER_CLIP_NEAR) != 0u;
+    const bool wide = (j.flags & ORBIT_RASTER_WIDE_GUARD) != 0u; // R4w
     const uint8_t *data_bytes = reinterpret_cast<const uint8_t *>(j.meshlet_data);
     const uint32_t count = j.draw_commands[0] < j.max_commands ? j.draw_commands[0] : j.max_commands;
     const float w_f = (float)j.width, h_f = (float)j.height;
@@ -77,7 +78,7 @@ void raster_into(const HostJob &j, const Sink &sink, bool has_target, uint32_t i
             float pos[3];
             std::memcpy(pos, j.vertices + (vertex_base + j.meshlet_data[index_base + v]) * j.vertex_stride + j.position_offset, 12);
             clips[v] = clip_position(mvp, pos[0], pos[1], pos[2]);
-            verts[v] = vertex_from_clip(clips[v], w_f, h_f);
+            verts[v] = vertex_from_clip(clips[v], w_f, h_f, false, wide);
         }
         for (uint32_t t = 0; t < nt; t++) {
             const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
@@ -86,11 +87,38 @@ void raster_into(const HostJob &j, const Sink &sink, bool has_target, uint32_t i
             pc.u[0] = verts[c[0]], pc.u[1] = verts[c[1]], pc.u[2] = pc.u[3] = verts[c[2]];
             pc.count = 1u;
             if (clip_near && ((pc.u[0].flags | pc.u[1].flags | pc.u[2].flags) & kClipFail))
-                clip_near_pieces(clips[c[0]], clips[c[1]], clips[c[2]], w_f, h_f, pc);
+                clip_near_pieces(clips[c[0]], clips[c[1]], clips[c[2]], w_f, h_f, pc, wide);
             uint32_t best = kNoCoverage; // counted once, under the best outcome of the pieces
             for (uint32_t q = 0; q < pc.count; q++) {
                 Vertex v0, v1, v2;
                 piece_vertices(pc, q, v0, v1, v2);
+                if (wide && is_wide_triangle(v0, v1, v2)) { // R5w-R7w: 8 x 8 tiles of the box, those no edge rules out sample by sample
+                    SetupW ws;
+                    const uint32_t outcome = setup_triangle_wide(v0, v1, v2, j.width, j.height, cull_none, ws);
+                    if (outcome != kDraw) {
+                        best = better_outcome(best, outcome);
+                        continue;
+                    }
+                    uint64_t inside = 0;
+                    for (int32_t ty = ws.y_lo; ty <= ws.y_hi; ty += 8)
+                        for (int32_t tx = ws.x_lo; tx <= ws.x_hi; tx += 8) {
+                            const int32_t x1 = imin(tx + 7, ws.x_hi), y1 = imin(ty + 7, ws.y_hi);
+                            if (rect_outside_wide(ws, tx, ty, x1, y1)) continue;
+                            for (int32_t y = ty; y <= y1; y++)
+                                for (int32_t x = tx; x <= x1; x++) {
+                                    if (!inside_wide(ws, x, y)) continue;
+                                    inside++;
+                                    const float d = depth_at(ws, 256 * x + 128, 256 * y + 128);
+                                    if (!(d > 0.0f)) continue;
+                                    st.fragments++;
+                                    uint32_t bits;
+                                    std::memcpy(&bits, &d, 4);
+                                    sink.write((size_t)y * j.width + (uint32_t)x, bits, (id_base + i) << 8 | t);
+                                }
+                        }
+                    if (inside != 0) best = kDraw;
+                    continue;
+                }
                 Setup s;
                 const uint32_t outcome = setup_triangle(v0, v1, v2, j.width, j.height, cull_none, s);
                 if (outcome != kDraw) {

@@ -3,7 +3,8 @@
 // MeshletDrawCommandBuffer, and the same pass keeping the winner, on HOST copies of the same buffers, sequential.  It is the reference of the GPU
 // tests: the same depth bytes, the same counters, and a per-command flag where the device latches ORBIT_E_RANGE.  The
 // arithmetic (transform, snap, setup, edge functions, depth plane) is ../csrc/raster_common.h, shared with the kernel;
-// this side evaluates every edge function at every sample of a triangle's box directly, command after command.
+// this side evaluates every edge function at every sample of a triangle's box directly, command after command (for a
+// wide triangle of ORBIT_RASTER_WIDE_GUARD, R4w: at every sample of the 8 x 8 tiles of the box that no edge rules out).
 #pragma once
 #include <cstdint>
 

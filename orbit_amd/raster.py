@@ -11,6 +11,7 @@ from . import layouts as L
 from .passes import _check, lib
 
 CLEAR, CULL_NONE, CLIP_NEAR = _lib.RASTER_CLEAR, _lib.RASTER_CULL_NONE, _lib.RASTER_CLIP_NEAR
+WIDE_GUARD = _lib.RASTER_WIDE_GUARD
 
 
 def command_buffer(commands, capacity=None, count=None):
@@ -25,7 +26,7 @@ def command_buffer(commands, capacity=None, count=None):
 
 def _host_raster(call, dtype, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, view_proj,
                  width, height, target, no_target, clear, cull_none, vertex_stride, position_offset, entity_count,
-                 meshlet_data_words, clip_near, *extra):
+                 meshlet_data_words, clip_near, wide_guard, *extra):
     """What the two raster calls of the host mirror share: the arguments as the C call takes them (`extra` goes between
     the flags and the stats), the target loaded (copied) or cleared, -> (target, stats row, command_error)."""
     buf = np.ascontiguousarray(draw_commands).view(np.uint8).reshape(-1)
@@ -48,35 +49,38 @@ def _host_raster(call, dtype, draw_commands, max_commands, meshlet_data, vertice
     stats, err = np.zeros(1, L.RASTER_STATS), np.zeros(n, np.int32)
     vp = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    flags = ((CLEAR if clear else 0) | (CULL_NONE if cull_none else 0) | (CLIP_NEAR if clip_near else 0)
+             | (WIDE_GUARD if wide_guard else 0))
     _check(call(p(buf), C.c_uint32(max_commands), p(data), C.c_uint64(words), p(vb), C.c_uint64(vertex_count),
                 C.c_uint32(vertex_stride), C.c_uint32(position_offset), p(ent), C.c_uint32(entity_count), vp, p(out),
-                C.c_uint32(width), C.c_uint32(height), C.c_uint32((CLEAR if clear else 0) | (CULL_NONE if cull_none else 0) | (CLIP_NEAR if clip_near else 0)),
+                C.c_uint32(width), C.c_uint32(height), C.c_uint32(flags),
                 *extra, p(stats), p(err)))
     return out, stats[0], err
 
 
 def host_raster_depth(draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, view_proj, width,
                       height, depth=None, clear=True, cull_none=False, vertex_stride=12, position_offset=0,
-                      entity_count=None, meshlet_data_words=None, clip_near=False):
+                      entity_count=None, meshlet_data_words=None, clip_near=False, wide_guard=False):
     """orbit_host_raster_depth on host arrays -> (depth: np.float32 (height, width), stats: np[layouts.RASTER_STATS]
     scalar row, command_error: np.int32 per processed command).  `draw_commands`: the {count; commands} words (any
     contiguous array, read as bytes).  `depth`: the buffer to load (copied); None needs clear=True.  clip_near:
-    ORBIT_RASTER_CLIP_NEAR."""
+    ORBIT_RASTER_CLIP_NEAR; wide_guard: ORBIT_RASTER_WIDE_GUARD."""
     return _host_raster(lib().orbit_host_raster_depth, np.float32, draw_commands, max_commands, meshlet_data, vertices,
                         vertex_count, entity_data, view_proj, width, height, depth, "no depth to load", clear, cull_none,
-                        vertex_stride, position_offset, entity_count, meshlet_data_words, clip_near)
+                        vertex_stride, position_offset, entity_count, meshlet_data_words, clip_near, wide_guard)
 
 
 def host_raster_visibility(draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, view_proj,
                            width, height, visibility=None, command_base=0, clear=True, cull_none=False, vertex_stride=12,
-                           position_offset=0, entity_count=None, meshlet_data_words=None, clip_near=False):
+                           position_offset=0, entity_count=None, meshlet_data_words=None, clip_near=False,
+                           wide_guard=False):
     """orbit_host_raster_visibility on host arrays -> (visibility: np.uint64 (height, width), stats:
     np[layouts.RASTER_STATS] scalar row, command_error: np.int32 per processed command).  The arguments are
     host_raster_depth's; `visibility`: the buffer to merge into (copied); None needs clear=True."""
     return _host_raster(lib().orbit_host_raster_visibility, np.uint64, draw_commands, max_commands, meshlet_data, vertices,
                         vertex_count, entity_data, view_proj, width, height, visibility, "no buffer to merge into", clear,
                         cull_none, vertex_stride, position_offset, entity_count, meshlet_data_words, clip_near,
-                        C.c_uint32(command_base))
+                        wide_guard, C.c_uint32(command_base))
 
 
 def host_visibility_resolve(visibility, command_base=0, max_commands=0, want_command_pixels=True):
