@@ -29,9 +29,19 @@ int32_t check_raster_job(OrbitCtx *ctx, const char *who, uint32_t flags, uint32_
     return ORBIT_OK;
 }
 
-// the resident grid of the kernel that `flags` launch: R4w's, R3c's or the plain one
-uint32_t blocks_of_flags(uint32_t flags, uint32_t wide, uint32_t clip, uint32_t plain) {
-    return (flags & ORBIT_RASTER_WIDE_GUARD) ? wide : (flags & ORBIT_RASTER_CLIP_NEAR) ? clip : plain;
+// The kernel of job.flags on that kernel's own resident grid, both picked by the one variant (resident_blocks: the
+// context's row of the call)
+hipError_t launch_raster_depth_by_flags(const OrbitRasterDepth &job, const uint32_t (&resident_blocks)[kRasterVariants],
+                                        int32_t *status, hipStream_t s) {
+    return with_raster_variant(raster_variant(job.flags), [&](auto v) {
+        return launch_raster_depth<v.value>(job, resident_blocks[(uint32_t)v.value], status, s);
+    });
+}
+hipError_t launch_raster_visibility_by_flags(const OrbitRasterVisibility &job,
+                                             const uint32_t (&resident_blocks)[kRasterVariants], int32_t *status, hipStream_t s) {
+    return with_raster_variant(raster_variant(job.flags), [&](auto v) {
+        return launch_raster_visibility<v.value>(job, resident_blocks[(uint32_t)v.value], status, s);
+    });
 }
 
 } // namespace
@@ -94,7 +104,7 @@ int32_t orbit_raster_depth(OrbitCtx *ctx, const OrbitRasterDepth *job, void *str
         return rc;
     if (!j.depth || ((uintptr_t)j.depth & 3u)) return fail(ctx, ORBIT_E_INVALID, "raster_depth: depth is NULL or not 4-B aligned");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_raster_depth(j, blocks_of_flags(j.flags, ctx->raster_wide_blocks, ctx->raster_clip_blocks, ctx->raster_blocks), ctx->status, (hipStream_t)stream);
+    const hipError_t e = launch_raster_depth_by_flags(j, ctx->raster_blocks, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_depth");
     return ORBIT_OK;
 }
@@ -114,7 +124,7 @@ int32_t orbit_raster_visibility(OrbitCtx *ctx, const OrbitRasterVisibility *job,
     if (!j.visibility || ((uintptr_t)j.visibility & 7u))
         return fail(ctx, ORBIT_E_INVALID, "raster_visibility: visibility is NULL or not 8-B aligned");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_raster_visibility(j, blocks_of_flags(j.flags, ctx->visibility_wide_blocks, ctx->visibility_clip_blocks, ctx->visibility_blocks), ctx->status, (hipStream_t)stream);
+    const hipError_t e = launch_raster_visibility_by_flags(j, ctx->visibility_blocks, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_visibility");
     return ORBIT_OK;
 }

@@ -148,12 +148,11 @@ int32_t orbit_ctx_create(int32_t device_id, const OrbitCaps *caps_in, OrbitCtx *
     if (!ctx) return fail(nullptr, ORBIT_E_HIP, "out of host memory");
     ctx->device = device_id;
     ctx->num_cus = (uint32_t)prop.multiProcessorCount;
-    ctx->raster_blocks = ctx->num_cus * raster_depth_blocks_per_cu(false);
-    ctx->visibility_blocks = ctx->num_cus * raster_visibility_blocks_per_cu(false);
-    ctx->raster_clip_blocks = ctx->num_cus * raster_depth_blocks_per_cu(true);
-    ctx->visibility_clip_blocks = ctx->num_cus * raster_visibility_blocks_per_cu(true);
-    ctx->raster_wide_blocks = ctx->num_cus * raster_depth_wide_blocks_per_cu();
-    ctx->visibility_wide_blocks = ctx->num_cus * raster_visibility_wide_blocks_per_cu();
+    for (uint32_t v = 0; v < kRasterVariants; v++)
+        with_raster_variant((RasterVariant)v, [&](auto variant) {
+            ctx->raster_blocks[v] = ctx->num_cus * raster_depth_blocks_per_cu<variant.value>();
+            ctx->visibility_blocks[v] = ctx->num_cus * raster_visibility_blocks_per_cu<variant.value>();
+        });
     ctx->caps = caps;
     ctx->rec_shift = rec_shift;
 

@@ -67,10 +67,8 @@ struct OrbitCtx {
     uint32_t *m_tile_masks = nullptr, *m_chunk_sums = nullptr;
     uint32_t *m_tile_counts = nullptr, *m_tile_base = nullptr, *m_total = nullptr;
     uint32_t *s_block_sums = nullptr; // orbit_scene_update: {meshes, lights, shadow casters} per 256 entities
-    uint32_t raster_blocks = 0;      // orbit_raster_depth: workgroups of its kernel resident on the device at once
-    uint32_t visibility_blocks = 0;  // orbit_raster_visibility: the same of its kernel
-    uint32_t raster_clip_blocks = 0, visibility_clip_blocks = 0; // the same of the two ORBIT_RASTER_CLIP_NEAR kernels
-    uint32_t raster_wide_blocks = 0, visibility_wide_blocks = 0; // and of the two ORBIT_RASTER_WIDE_GUARD kernels
+    uint32_t raster_blocks[kRasterVariants] = {};     // orbit_raster_depth: per variant, workgroups of its kernel resident at once
+    uint32_t visibility_blocks[kRasterVariants] = {}; // orbit_raster_visibility: the same of its kernels
     float *b_mesh_slices = nullptr;  // orbit_mesh_bounds: 8 floats per range and slice, kMeshBoundsSlots of them
     uint32_t *x_block_pop = nullptr; // orbit_expand_visible_records: survivors per 1024 records of the list
     uint32_t *c_chunk = nullptr; // compact: its own chunk counts | the ones a counting mark launch left (c_chunk_words each)

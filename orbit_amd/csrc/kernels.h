@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/orbit_abi_ext.h"
 #include "orbit_device.h"
@@ -369,28 +370,42 @@ hipError_t launch_mesh_bounds(const OrbitMeshBoundsRange *ranges, uint32_t range
                               const void *vertices, uint64_t vertex_count, uint32_t vertex_stride,
                               uint32_t position_offset, OrbitMeshInfo *mesh_infos, uint32_t mesh_capacity, float *scratch,
                               int32_t *status, hipStream_t s);
-// raster_depth.hip: orbit_raster_depth — `job` validated by the entry point; one launch clears depth
-// (ORBIT_RASTER_CLEAR) and stats, the next reads the command count on the device and draws (raster_walk.h: one walker
-// and one launch, which raster_depth.hip and raster_visibility.hip give a sink each)
+// raster_depth.hip, raster_visibility.hip: orbit_raster_depth and orbit_raster_visibility (raster_walk.h: one walker and
+// one launch, which the two files give a sink each).  Each call has three kernels, one per RasterVariant, and each
+// kernel a translation unit of its own (raster_depth.hip, raster_depth_clip.hip, raster_depth_wide.hip and the same of
+// raster_visibility), which defines the two explicit specialisations of its variant below.
+enum class RasterVariant : uint32_t { Plain, ClipNear, Wide }; // R1-R9 as they are; + R3c; + R4w (R3c by the flag word)
+constexpr uint32_t kRasterVariants = 3;
+// the one place where a flag word picks its kernel: the launch and the resident grid both follow from its answer
+inline RasterVariant raster_variant(uint32_t flags) {
+    return (flags & ORBIT_RASTER_WIDE_GUARD) ? RasterVariant::Wide : (flags & ORBIT_RASTER_CLIP_NEAR) ? RasterVariant::ClipNear : RasterVariant::Plain;
+}
+// f(std::integral_constant<RasterVariant, v>{}): a variant known at run time as a template argument.  (`default` is
+// Plain: raster_variant and the loop over [0, kRasterVariants) are the only sources of `v`, so no other value arrives;
+// the plain kernel is the one every flag word may fall back on.)
+template <class F>
+inline auto with_raster_variant(RasterVariant v, F f) {
+    switch (v) {
+    case RasterVariant::Wide: return f(std::integral_constant<RasterVariant, RasterVariant::Wide>{});
+    case RasterVariant::ClipNear: return f(std::integral_constant<RasterVariant, RasterVariant::ClipNear>{});
+    default: return f(std::integral_constant<RasterVariant, RasterVariant::Plain>{});
+    }
+}
+// The four templates below are DECLARED ONLY, on purpose: every use names a specialisation that one of the six units
+// defines explicitly, nothing is instantiated here, and the linker joins them.  Do not give a primary a definition:
+// the units that call a specialisation do not see its declaration, so they would instantiate the primary's body
+// instead, silently.
+// `job` validated by the entry point; one launch clears the target (ORBIT_RASTER_CLEAR) and stats, the next reads the
+// command count on the device and draws with V's kernel on at most `resident_blocks` workgroups
+template <RasterVariant V>
 hipError_t launch_raster_depth(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
-// ... its workgroups that one CU holds at once (asked of the runtime once, when a context is created); clip_near: of
-// the kernel that ORBIT_RASTER_CLIP_NEAR launches (R3c), which `resident_blocks` must then be of, too
-uint32_t raster_depth_blocks_per_cu(bool clip_near);
-// raster_depth_clip.hip: what the two above hand ORBIT_RASTER_CLIP_NEAR over to
-hipError_t launch_raster_depth_clip(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
-uint32_t raster_depth_clip_blocks_per_cu();
-// raster_depth_wide.hip: what launch_raster_depth hands ORBIT_RASTER_WIDE_GUARD over to (R4w; with or without CLIP_NEAR)
-hipError_t launch_raster_depth_wide(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
-uint32_t raster_depth_wide_blocks_per_cu();
-// raster_visibility.hip: orbit_raster_visibility — as launch_raster_depth, into the u64 buffer (V1-V4)
+template <RasterVariant V>
 hipError_t launch_raster_visibility(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
-uint32_t raster_visibility_blocks_per_cu(bool clip_near);
-// raster_visibility_clip.hip: the same for ORBIT_RASTER_CLIP_NEAR
-hipError_t launch_raster_visibility_clip(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
-uint32_t raster_visibility_clip_blocks_per_cu();
-// raster_visibility_wide.hip: the same for ORBIT_RASTER_WIDE_GUARD
-hipError_t launch_raster_visibility_wide(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s);
-uint32_t raster_visibility_wide_blocks_per_cu();
+// ... the workgroups of V's kernel that one CU holds at once (asked of the runtime once, when a context is created)
+template <RasterVariant V>
+uint32_t raster_depth_blocks_per_cu();
+template <RasterVariant V>
+uint32_t raster_visibility_blocks_per_cu();
 // ... and orbit_visibility_resolve: one launch clears command_pixels and stats, the next reads every word once
 hipError_t launch_visibility_resolve(const OrbitVisibilityResolve &job, uint32_t num_cus, hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the

@@ -8,9 +8,14 @@
 // much: the buffer only grows, so a stale smaller value costs an atomic, never a pixel.
 #include "raster_walk.h"
 
-#ifndef ORBIT_RASTER_CLIP
-#define ORBIT_RASTER_CLIP 0 // 1: raster_depth_clip.hip compiles this file into the ORBIT_RASTER_CLIP_NEAR kernel and its launch
-#endif                      // 2: raster_depth_wide.hip, into the ORBIT_RASTER_WIDE_GUARD kernel (with or without CLIP_NEAR)
+#ifndef ORBIT_RASTER_VARIANT // raster_depth_clip.hip and raster_depth_wide.hip compile this file with theirs
+#define ORBIT_RASTER_VARIANT Plain
+#endif
+// the variant's kernel, under the name the profiles know it by
+#define ORBIT_RASTER_KERNEL_Plain raster_depth_kernel
+#define ORBIT_RASTER_KERNEL_ClipNear raster_depth_clip_kernel
+#define ORBIT_RASTER_KERNEL_Wide raster_depth_wide_kernel
+#define ORBIT_RASTER_DEPTH_KERNEL ORBIT_RASTER_PASTE(ORBIT_RASTER_KERNEL_, ORBIT_RASTER_VARIANT)
 
 namespace orbit {
 namespace {
@@ -33,47 +38,23 @@ struct DepthSink {
     }
 };
 
-#if !ORBIT_RASTER_CLIP
-__global__ __launch_bounds__(kRasterThreads) void raster_depth_kernel(const RasterParams p, uint32_t *const depth) {
-    raster_commands<false>(p, DepthSink{depth}, 0u);
+constexpr RasterVariant kVariant = RasterVariant::ORBIT_RASTER_VARIANT;
+
+__global__ __launch_bounds__(kRasterThreads) void ORBIT_RASTER_DEPTH_KERNEL(const RasterParams p, uint32_t *const depth) {
+    raster_commands<kVariant>(p, DepthSink{depth}, 0u);
 }
-#define ORBIT_RASTER_DEPTH_KERNEL raster_depth_kernel
-#elif ORBIT_RASTER_CLIP == 1 // ORBIT_RASTER_CLIP_NEAR (R3c), a translation unit of its own (raster_depth_clip.hip)
-__global__ __launch_bounds__(kRasterThreads) void raster_depth_clip_kernel(const RasterParams p, uint32_t *const depth) {
-    raster_commands<true>(p, DepthSink{depth}, 0u);
-}
-#define ORBIT_RASTER_DEPTH_KERNEL raster_depth_clip_kernel
-#else // ORBIT_RASTER_WIDE_GUARD (R4w), a translation unit of its own (raster_depth_wide.hip)
-__global__ __launch_bounds__(kRasterThreads) void raster_depth_wide_kernel(const RasterParams p, uint32_t *const depth) {
-    raster_commands<false, DepthSink, true>(p, DepthSink{depth}, 0u);
-}
-#define ORBIT_RASTER_DEPTH_KERNEL raster_depth_wide_kernel
-#endif
 
 } // namespace
 
-#if !ORBIT_RASTER_CLIP
-uint32_t raster_depth_blocks_per_cu(bool clip_near) {
-    if (clip_near) return raster_depth_clip_blocks_per_cu();
-#elif ORBIT_RASTER_CLIP == 1
-uint32_t raster_depth_clip_blocks_per_cu() {
-#else
-uint32_t raster_depth_wide_blocks_per_cu() {
-#endif
+template <>
+uint32_t raster_depth_blocks_per_cu<kVariant>() {
     int n = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ORBIT_RASTER_DEPTH_KERNEL, (int)kRasterThreads, 0);
     return e == hipSuccess && n > 0 ? (uint32_t)n : 2u;
 }
 
-#if !ORBIT_RASTER_CLIP
-hipError_t launch_raster_depth(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
-    if (job.flags & ORBIT_RASTER_WIDE_GUARD) return launch_raster_depth_wide(job, resident_blocks, status, s);
-    if (job.flags & ORBIT_RASTER_CLIP_NEAR) return launch_raster_depth_clip(job, resident_blocks, status, s);
-#elif ORBIT_RASTER_CLIP == 1
-hipError_t launch_raster_depth_clip(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
-#else
-hipError_t launch_raster_depth_wide(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
-#endif
+template <>
+hipError_t launch_raster_depth<kVariant>(const OrbitRasterDepth &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
     return launch_raster(ORBIT_RASTER_DEPTH_KERNEL, job, (uint32_t *)job.depth, resident_blocks, status, s, (uint32_t *)job.depth);
 }
 

@@ -13,16 +13,20 @@
 // same, one atomicAdd of their number from one lane, until no lane remains.  All outputs are integer sums.
 #include "raster_walk.h"
 
-#ifndef ORBIT_RASTER_CLIP
-#define ORBIT_RASTER_CLIP 0 // 1: raster_visibility_clip.hip compiles this file into the ORBIT_RASTER_CLIP_NEAR kernel and its launch
-#endif                      // 2: raster_visibility_wide.hip, into the ORBIT_RASTER_WIDE_GUARD kernel (with or without CLIP_NEAR)
+#ifndef ORBIT_RASTER_VARIANT // raster_visibility_clip.hip and raster_visibility_wide.hip compile this file with theirs
+#define ORBIT_RASTER_VARIANT Plain
+#define ORBIT_RASTER_WITH_RESOLVE 1 // the resolve is compiled once, in the unit that sets no variant
+#endif
+// the variant's kernel, under the name the profiles know it by
+#define ORBIT_RASTER_KERNEL_Plain raster_visibility_kernel
+#define ORBIT_RASTER_KERNEL_ClipNear raster_visibility_clip_kernel
+#define ORBIT_RASTER_KERNEL_Wide raster_visibility_wide_kernel
+#define ORBIT_RASTER_VISIBILITY_KERNEL ORBIT_RASTER_PASTE(ORBIT_RASTER_KERNEL_, ORBIT_RASTER_VARIANT)
 
 namespace orbit {
 namespace {
 
 using namespace raster;
-
-constexpr uint32_t kResolveThreads = 256, kResolveWaves = kResolveThreads / 64;
 
 // R7 and V2 of one inside sample -> it is a fragment (d > 0)
 struct VisibilitySink {
@@ -39,28 +43,35 @@ struct VisibilitySink {
     }
 };
 
-#if !ORBIT_RASTER_CLIP
-__global__ __launch_bounds__(kRasterThreads) void raster_visibility_kernel(const RasterParams p, const VisibilitySink sink,
-                                                                           const uint32_t command_base) {
-    raster_commands<false>(p, sink, command_base);
-}
-#define ORBIT_RASTER_VISIBILITY_KERNEL raster_visibility_kernel
-#elif ORBIT_RASTER_CLIP == 1 // ORBIT_RASTER_CLIP_NEAR (R3c), a translation unit of its own (raster_visibility_clip.hip): every
-                             // piece carries the original triangle's index
-__global__ __launch_bounds__(kRasterThreads) void raster_visibility_clip_kernel(const RasterParams p, const VisibilitySink sink,
-                                                                                const uint32_t command_base) {
-    raster_commands<true>(p, sink, command_base);
-}
-#define ORBIT_RASTER_VISIBILITY_KERNEL raster_visibility_clip_kernel
-#else // ORBIT_RASTER_WIDE_GUARD (R4w), a translation unit of its own (raster_visibility_wide.hip)
-__global__ __launch_bounds__(kRasterThreads) void raster_visibility_wide_kernel(const RasterParams p, const VisibilitySink sink,
-                                                                                const uint32_t command_base) {
-    raster_commands<false, VisibilitySink, true>(p, sink, command_base);
-}
-#define ORBIT_RASTER_VISIBILITY_KERNEL raster_visibility_wide_kernel
-#endif
+constexpr RasterVariant kVariant = RasterVariant::ORBIT_RASTER_VARIANT;
 
-#if !ORBIT_RASTER_CLIP
+// (with ClipNear and Wide every piece carries the original triangle's index)
+__global__ __launch_bounds__(kRasterThreads) void ORBIT_RASTER_VISIBILITY_KERNEL(const RasterParams p, const VisibilitySink sink,
+                                                                                 const uint32_t command_base) {
+    raster_commands<kVariant>(p, sink, command_base);
+}
+
+} // namespace
+
+template <>
+uint32_t raster_visibility_blocks_per_cu<kVariant>() {
+    int n = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ORBIT_RASTER_VISIBILITY_KERNEL, (int)kRasterThreads, 0);
+    return e == hipSuccess && n > 0 ? (uint32_t)n : 2u;
+}
+
+template <>
+hipError_t launch_raster_visibility<kVariant>(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status,
+                                              hipStream_t s) {
+    return launch_raster(ORBIT_RASTER_VISIBILITY_KERNEL, job, (unsigned long long *)job.visibility, resident_blocks, status, s,
+                         VisibilitySink{(unsigned long long *)job.visibility}, job.command_base);
+}
+
+#ifdef ORBIT_RASTER_WITH_RESOLVE
+namespace {
+
+constexpr uint32_t kResolveThreads = 256, kResolveWaves = kResolveThreads / 64;
+
 // command_pixels[0, commands) = 0 and, if given, the four counters = 0
 __global__ __launch_bounds__(kResolveThreads) void resolve_clear_kernel(uint32_t *command_pixels, uint32_t commands,
                                                                         uint32_t *stats) {
@@ -107,37 +118,8 @@ __global__ __launch_bounds__(kResolveThreads) void visibility_resolve_kernel(con
     if (n_foreign != 0u) atomicAdd(&stats[2], n_foreign);
 }
 
-#endif // !ORBIT_RASTER_CLIP
-
 } // namespace
 
-#if !ORBIT_RASTER_CLIP
-uint32_t raster_visibility_blocks_per_cu(bool clip_near) {
-    if (clip_near) return raster_visibility_clip_blocks_per_cu();
-#elif ORBIT_RASTER_CLIP == 1
-uint32_t raster_visibility_clip_blocks_per_cu() {
-#else
-uint32_t raster_visibility_wide_blocks_per_cu() {
-#endif
-    int n = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ORBIT_RASTER_VISIBILITY_KERNEL, (int)kRasterThreads, 0);
-    return e == hipSuccess && n > 0 ? (uint32_t)n : 2u;
-}
-
-#if !ORBIT_RASTER_CLIP
-hipError_t launch_raster_visibility(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
-    if (job.flags & ORBIT_RASTER_WIDE_GUARD) return launch_raster_visibility_wide(job, resident_blocks, status, s);
-    if (job.flags & ORBIT_RASTER_CLIP_NEAR) return launch_raster_visibility_clip(job, resident_blocks, status, s);
-#elif ORBIT_RASTER_CLIP == 1
-hipError_t launch_raster_visibility_clip(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
-#else
-hipError_t launch_raster_visibility_wide(const OrbitRasterVisibility &job, uint32_t resident_blocks, int32_t *status, hipStream_t s) {
-#endif
-    return launch_raster(ORBIT_RASTER_VISIBILITY_KERNEL, job, (unsigned long long *)job.visibility, resident_blocks, status, s,
-                         VisibilitySink{(unsigned long long *)job.visibility}, job.command_base);
-}
-
-#if !ORBIT_RASTER_CLIP
 hipError_t launch_visibility_resolve(const OrbitVisibilityResolve &job, uint32_t num_cus, hipStream_t s) {
     const uint32_t cap = (num_cus ? num_cus : 64u) * 8u;
     if (job.stats || (job.command_pixels && job.max_commands != 0u)) {
@@ -153,6 +135,6 @@ hipError_t launch_visibility_resolve(const OrbitVisibilityResolve &job, uint32_t
     hipLaunchKernelGGL(visibility_resolve_kernel, dim3(need < cap ? need : cap), dim3(kResolveThreads), 0, s, job, tiles_x, tiles);
     return hipGetLastError();
 }
-#endif // !ORBIT_RASTER_CLIP
+#endif // ORBIT_RASTER_WITH_RESOLVE
 
 } // namespace orbit

@@ -13,7 +13,7 @@
 //            of the front faces of the test scene cover no sample at all); a larger one is taken by the whole wave, one
 //            at a time (ballot, the corners broadcast, every lane repeats the setup, lanes take the 8 x 8 tiles of the
 //            box).  Edge functions are stepped in int64, the same integers as evaluating them per sample.
-// Behind ORBIT_RASTER_WIDE_GUARD (kWide, R4w) a triangle with a vertex beyond R4's band is taken by the whole wave as well,
+// Behind ORBIT_RASTER_WIDE_GUARD (RasterVariant::Wide, R4w) a triangle with a vertex beyond R4's band is taken by the whole wave as well,
 // but not box by box: walk_wide rejects 64 x 64 blocks, then 8 x 8 tiles, and evaluates samples only in the tiles left.
 // A sink has
 //   static constexpr uint32_t kMaxTriangles   a command with more triangles is a range error (V3); ~0u: no limit
@@ -25,6 +25,10 @@
 #include "kernels.h"
 #include "orbit_device.h"
 #include "raster_common.h"
+
+// A##B after both are expanded: a raster unit names its kernel from its ORBIT_RASTER_VARIANT with it
+#define ORBIT_RASTER_PASTE_(a, b) a##b
+#define ORBIT_RASTER_PASTE(a, b) ORBIT_RASTER_PASTE_(a, b)
 
 namespace orbit {
 namespace raster {
@@ -82,7 +86,7 @@ __device__ __forceinline__ Vertex readlane_vertex(const Vertex &v, uint32_t src)
     return out;
 }
 
-// The wave's mvp beyond phase 1: the clip path reads it again in phase 2; without kClipNear there is nothing to keep
+// The wave's mvp beyond phase 1: the pieces form of phase 2 reads it again; the plain form has nothing to keep
 template <bool kKeep>
 struct KeptMvp {
     float m[16];
@@ -165,19 +169,23 @@ __device__ __forceinline__ uint32_t walk_wide(const Sink &sink, uint32_t width, 
 // The body of a raster kernel: a resident grid of wave64s striding over the command list, in the phases named at the
 // top.  `id_base` is added to the command's position in the list before it goes into the sample's id.
 //
-// kClipNear (ORBIT_RASTER_CLIP_NEAR, R3c): a lane whose triangle R3 rejects with a vertex in reads the three positions
-// again through the index words phase 1 checked, recomputes their clip coordinates from the wave's mvp and builds its
-// pieces in registers (raster_common.h); each piece then takes the route above.  The wave walk broadcasts a piece's
-// three Vertex records from the owning lane, as its vertices are not in LDS.  Without kClipNear the body is the code
-// as it was before the flag existed.
-//
-// kWide (ORBIT_RASTER_WIDE_GUARD, R4w): phase 1 keeps a guard-failing vertex's xf, yf in its LDS record; phase 2 is the
-// kClipNear form with ORBIT_RASTER_CLIP_NEAR read from the flag word (a wave-uniform branch, so the flag pair costs two
-// kernels, not four); a piece with every vertex narrow takes the routes above unchanged, one with a vertex out of band
-// is guard_skipped, and a wide one is taken by the whole wave (walk_wide), its three Vertex records broadcast from the
-// owning lane and its setup wave-uniform.  Without kWide nothing of this is compiled.
-template <bool kClipNear, class Sink, bool kWide = false>
+// V (kernels.h) picks one of two forms of phase 2, and what phase 1 keeps for it:
+//   Plain     a lane sets up its triangle from LDS and counts the outcome directly; the wave walk reads the corners
+//             from LDS again.  The code as it was before either flag existed: it holds fewer registers than the pieces
+//             form, which is why it stays a form of its own.
+//   ClipNear  (ORBIT_RASTER_CLIP_NEAR, R3c) the pieces form: a lane whose triangle R3 rejects with a vertex in reads the
+//             three positions again through the index words phase 1 checked, recomputes their clip coordinates from the
+//             wave's mvp and builds its pieces in registers (raster_common.h); each piece then takes the routes above,
+//             and the triangle is counted once, under the best outcome of its pieces.  The wave walk broadcasts a piece's
+//             three Vertex records from the owning lane, as its vertices are not in LDS.
+//   Wide      (ORBIT_RASTER_WIDE_GUARD, R4w; with or without CLIP_NEAR) phase 1 keeps a guard-failing vertex's xf, yf in
+//             its LDS record; phase 2 is the pieces form with ORBIT_RASTER_CLIP_NEAR read from the flag word and three
+//             additions under `if constexpr`: a piece with every vertex narrow takes the routes above unchanged, one with
+//             a vertex out of band is guard_skipped, and a wide one (is_wide_triangle) is taken by the whole wave
+//             (walk_wide), its three Vertex records broadcast from the owning lane and its setup wave-uniform.
+template <RasterVariant V, class Sink>
 __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sink &sink, uint32_t id_base) {
+    constexpr bool kWide = V == RasterVariant::Wide;
     __shared__ int4 lds_verts[kRasterWaves][kMaxVertices];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -203,7 +211,7 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
         bool bad = first_word < index_base || vcount > 255u || (uint64_t)first_word > p.meshlet_data_words ||
                    ((uint64_t)first_index + 3ull * nt + 3ull) / 4ull > p.meshlet_data_words || entity >= p.entity_count ||
                    nt > Sink::kMaxTriangles;
-        KeptMvp<kClipNear || kWide> kept; // (set when !bad)
+        KeptMvp<V != RasterVariant::Plain> kept; // (set when !bad)
         if (!bad) {
             float mvp[16];
             {
@@ -242,77 +250,7 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
         if (lane == 0u) n_triangles += nt;
         const uint32_t command_id = (id_base + i) << 8;
         wave_lds_sync();
-        if constexpr (kWide) {
-            const bool clip_near = (p.flags & ORBIT_RASTER_CLIP_NEAR) != 0u; // (wave-uniform)
-            for (uint32_t base = 0; base < nt; base += 64u) {
-                const uint32_t t = base + lane;
-                Pieces pc;
-                pc.count = 0u;
-                for (int k = 0; k < 4; k++) pc.u[k].X = pc.u[k].Y = 0, pc.u[k].d = 0.f, pc.u[k].flags = 0u;
-                if (t < nt) {
-                    const uint8_t *c = data_bytes + (size_t)first_index + 3u * (size_t)t;
-                    pc.u[0] = lds_vertex(verts, c[0]), pc.u[1] = lds_vertex(verts, c[1]), pc.u[2] = lds_vertex(verts, c[2]);
-                    pc.u[3] = pc.u[2];
-                    const uint32_t any_out = (pc.u[0].flags | pc.u[1].flags | pc.u[2].flags) & kClipFail;
-                    const uint32_t all_out = pc.u[0].flags & pc.u[1].flags & pc.u[2].flags & kClipFail;
-                    if (any_out == 0u) {
-                        pc.count = 1u;
-                    } else if (clip_near && all_out == 0u) { // R3c: a vertex in, a vertex out
-                        Clip cc[3];
-                        for (int k = 0; k < 3; k++) {
-                            const uint64_t g = vertex_base + p.meshlet_data[index_base + c[k]]; // in range: phase 1
-                            const float *src = (const float *)(p.vertices + g * p.vertex_stride + p.position_offset);
-                            cc[k] = clip_position(kept.m, src[0], src[1], src[2]);
-                        }
-                        clip_near_pieces(cc[0], cc[1], cc[2], w_f, h_f, pc, true);
-                    }
-                    if (pc.count == 0u) n_outcome[kClipSkipped]++;
-                }
-                uint32_t best = kNoCoverage; // of this lane's pieces; counted once below
-                const uint32_t rounds = __ballot(pc.count > 1u) != 0ull ? 2u : 1u;
-#pragma nounroll
-                for (uint32_t q = 0; q < rounds; q++) {
-                    Vertex v0, v1, v2;
-                    piece_vertices(pc, q, v0, v1, v2);
-                    Setup s;
-                    bool draw = false, wide = false;
-                    if (q < pc.count) {
-                        wide = is_wide_triangle(v0, v1, v2);
-                        if (!wide) { // all narrow, or a vertex out of band: guard_skipped
-                            const uint32_t outcome = setup_triangle(v0, v1, v2, p.width, p.height, cull_none, s);
-                            draw = outcome == kDraw;
-                            if (!draw) best = better_outcome(best, outcome);
-                        }
-                    }
-                    const bool small = draw && (s.x_hi - s.x_lo + 1) * (s.y_hi - s.y_lo + 1) <= kLaneBox;
-                    if (small && walk(sink, p.width, s, 0, 0, 1, command_id | t, n_fragments) != 0u) best = kDraw;
-                    uint64_t large = __ballot(draw && !small);
-                    while (large != 0ull) {
-                        const uint32_t src = (uint32_t)__builtin_ctzll(large);
-                        large &= large - 1ull;
-                        const Vertex b0 = readlane_vertex(v0, src), b1 = readlane_vertex(v1, src), b2 = readlane_vertex(v2, src);
-                        Setup ws;
-                        (void)setup_triangle(b0, b1, b2, p.width, p.height, cull_none, ws);
-                        const uint32_t inside = walk(sink, p.width, ws, (int32_t)(lane & 7u), (int32_t)(lane >> 3), 8,
-                                                     command_id | (base + src), n_fragments);
-                        if (__ballot(inside != 0u) != 0ull && lane == src) best = kDraw;
-                    }
-                    uint64_t wides = __ballot(wide);
-                    while (wides != 0ull) {
-                        const uint32_t src = (uint32_t)__builtin_ctzll(wides);
-                        wides &= wides - 1ull;
-                        const Vertex b0 = readlane_vertex(v0, src), b1 = readlane_vertex(v1, src), b2 = readlane_vertex(v2, src);
-                        SetupW ws;
-                        const uint32_t outcome = setup_triangle_wide(b0, b1, b2, p.width, p.height, cull_none, ws); // (wave-uniform)
-                        uint32_t inside = 0;
-                        if (outcome == kDraw) inside = walk_wide(sink, p.width, ws, lane, command_id | (base + src), n_fragments);
-                        const bool covered = __ballot(inside != 0u) != 0ull;
-                        if (lane == src) best = covered ? (uint32_t)kDraw : better_outcome(best, outcome == kDraw ? (uint32_t)kNoCoverage : outcome);
-                    }
-                }
-                if (pc.count != 0u && best != kDraw) n_outcome[best]++;
-            }
-        } else if constexpr (!kClipNear) {
+        if constexpr (V == RasterVariant::Plain) {
             for (uint32_t base = 0; base < nt; base += 64u) {
                 const uint32_t t = base + lane;
                 Setup s;
@@ -343,6 +281,8 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
                 }
             }
         } else {
+            // (Wide: a wave-uniform branch, so the flag pair costs two kernels, not four)
+            const bool clip_near = V == RasterVariant::ClipNear || (p.flags & ORBIT_RASTER_CLIP_NEAR) != 0u;
             for (uint32_t base = 0; base < nt; base += 64u) {
                 const uint32_t t = base + lane;
                 Pieces pc;
@@ -356,14 +296,14 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
                     const uint32_t all_out = pc.u[0].flags & pc.u[1].flags & pc.u[2].flags & kClipFail;
                     if (any_out == 0u) {
                         pc.count = 1u;
-                    } else if (all_out == 0u) { // R3c: a vertex in, a vertex out
+                    } else if (clip_near && all_out == 0u) { // R3c: a vertex in, a vertex out
                         Clip cc[3];
                         for (int k = 0; k < 3; k++) {
                             const uint64_t g = vertex_base + p.meshlet_data[index_base + c[k]]; // in range: phase 1
                             const float *src = (const float *)(p.vertices + g * p.vertex_stride + p.position_offset);
                             cc[k] = clip_position(kept.m, src[0], src[1], src[2]);
                         }
-                        clip_near_pieces(cc[0], cc[1], cc[2], w_f, h_f, pc);
+                        clip_near_pieces(cc[0], cc[1], cc[2], w_f, h_f, pc, kWide);
                     }
                     if (pc.count == 0u) n_outcome[kClipSkipped]++;
                 }
@@ -374,11 +314,14 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
                     Vertex v0, v1, v2;
                     piece_vertices(pc, q, v0, v1, v2);
                     Setup s;
-                    bool draw = false;
+                    bool draw = false, wide = false;
                     if (q < pc.count) {
-                        const uint32_t outcome = setup_triangle(v0, v1, v2, p.width, p.height, cull_none, s);
-                        draw = outcome == kDraw;
-                        if (!draw) best = better_outcome(best, outcome);
+                        if constexpr (kWide) wide = is_wide_triangle(v0, v1, v2);
+                        if (!wide) { // all narrow, or a vertex out of band: guard_skipped
+                            const uint32_t outcome = setup_triangle(v0, v1, v2, p.width, p.height, cull_none, s);
+                            draw = outcome == kDraw;
+                            if (!draw) best = better_outcome(best, outcome);
+                        }
                     }
                     const bool small = draw && (s.x_hi - s.x_lo + 1) * (s.y_hi - s.y_lo + 1) <= kLaneBox;
                     if (small && walk(sink, p.width, s, 0, 0, 1, command_id | t, n_fragments) != 0u) best = kDraw;
@@ -392,6 +335,20 @@ __device__ __forceinline__ void raster_commands(const RasterParams &p, const Sin
                         const uint32_t inside = walk(sink, p.width, ws, (int32_t)(lane & 7u), (int32_t)(lane >> 3), 8,
                                                      command_id | (base + src), n_fragments);
                         if (__ballot(inside != 0u) != 0ull && lane == src) best = kDraw;
+                    }
+                    if constexpr (kWide) {
+                        uint64_t wides = __ballot(wide);
+                        while (wides != 0ull) {
+                            const uint32_t src = (uint32_t)__builtin_ctzll(wides);
+                            wides &= wides - 1ull;
+                            const Vertex b0 = readlane_vertex(v0, src), b1 = readlane_vertex(v1, src), b2 = readlane_vertex(v2, src);
+                            SetupW ws;
+                            const uint32_t outcome = setup_triangle_wide(b0, b1, b2, p.width, p.height, cull_none, ws); // (wave-uniform)
+                            uint32_t inside = 0;
+                            if (outcome == kDraw) inside = walk_wide(sink, p.width, ws, lane, command_id | (base + src), n_fragments);
+                            const bool covered = __ballot(inside != 0u) != 0ull;
+                            if (lane == src) best = covered ? (uint32_t)kDraw : better_outcome(best, outcome == kDraw ? (uint32_t)kNoCoverage : outcome);
+                        }
                     }
                 }
                 if (pc.count != 0u && best != kDraw) n_outcome[best]++;

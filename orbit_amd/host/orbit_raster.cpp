@@ -88,6 +88,15 @@ void raster_into(const HostJob &j, const Sink &sink, bool has_target, uint32_t i
             pc.count = 1u;
             if (clip_near && ((pc.u[0].flags | pc.u[1].flags | pc.u[2].flags) & kClipFail))
                 clip_near_pieces(clips[c[0]], clips[c[1]], clips[c[2]], w_f, h_f, pc, wide);
+            // R7 (a Setup) or R7w (a SetupW) of one inside sample: a fragment if d > 0
+            const auto emit = [&](const auto &setup, int32_t x, int32_t y) {
+                const float d = depth_at(setup, 256 * x + 128, 256 * y + 128);
+                if (!(d > 0.0f)) return;
+                st.fragments++;
+                uint32_t bits;
+                std::memcpy(&bits, &d, 4);
+                sink.write((size_t)y * j.width + (uint32_t)x, bits, (id_base + i) << 8 | t);
+            };
             uint32_t best = kNoCoverage; // counted once, under the best outcome of the pieces
             for (uint32_t q = 0; q < pc.count; q++) {
                 Vertex v0, v1, v2;
@@ -108,12 +117,7 @@ void raster_into(const HostJob &j, const Sink &sink, bool has_target, uint32_t i
                                 for (int32_t x = tx; x <= x1; x++) {
                                     if (!inside_wide(ws, x, y)) continue;
                                     inside++;
-                                    const float d = depth_at(ws, 256 * x + 128, 256 * y + 128);
-                                    if (!(d > 0.0f)) continue;
-                                    st.fragments++;
-                                    uint32_t bits;
-                                    std::memcpy(&bits, &d, 4);
-                                    sink.write((size_t)y * j.width + (uint32_t)x, bits, (id_base + i) << 8 | t);
+                                    emit(ws, x, y);
                                 }
                         }
                     if (inside != 0) best = kDraw;
@@ -131,12 +135,7 @@ void raster_into(const HostJob &j, const Sink &sink, bool has_target, uint32_t i
                         const int32_t px = 256 * x + 128, py = 256 * y + 128;
                         if (edge_at(s, 0, px, py) < 0 || edge_at(s, 1, px, py) < 0 || edge_at(s, 2, px, py) < 0) continue;
                         inside++;
-                        const float d = depth_at(s, px, py);
-                        if (!(d > 0.0f)) continue;
-                        st.fragments++;
-                        uint32_t bits;
-                        std::memcpy(&bits, &d, 4);
-                        sink.write((size_t)y * j.width + (uint32_t)x, bits, (id_base + i) << 8 | t);
+                        emit(s, x, y);
                     }
                 if (inside != 0) best = kDraw;
             }
