@@ -47,8 +47,6 @@ const Rccl &rccl() {
 
 constexpr uint32_t kMaxGatherWorld = 64; // counts scratch: one 256-B carve
 
-__global__ void write_u32_kernel(uint32_t *dst, uint32_t v) { *dst = v; }
-
 // Rank-ordered all-gather of {u32 count @0 | header_bytes | items of `stride` bytes} buffers.
 int32_t gather_lists(OrbitCtx *ctx, void *nccl_comm, uint32_t rank, uint32_t world, const void *local_draw_buffer,
                      void *out_draw_buffer, uint32_t out_capacity, void *stream, size_t header_bytes, size_t stride) {
@@ -85,9 +83,8 @@ int32_t gather_lists(OrbitCtx *ctx, void *nccl_comm, uint32_t rank, uint32_t wor
     // 2. header = total; 3. every list straight into out + prefix[rank]
     uint8_t *out = (uint8_t *)out_draw_buffer;
     const uint8_t *mine = (const uint8_t *)local_draw_buffer + header_bytes;
-    hipLaunchKernelGGL(write_u32_kernel, dim3(1), dim3(1), 0, s, (uint32_t *)out, (uint32_t)prefix[world]);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, "launch write_u32");
+    e = launch_write_word((uint32_t *)out, (uint32_t)prefix[world], s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch write_word");
     if (counts[rank] > 0) {
         e = hipMemcpyAsync(out + header_bytes + stride * prefix[rank], mine, stride * counts[rank],
                            hipMemcpyDeviceToDevice, s);

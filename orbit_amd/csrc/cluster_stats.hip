@@ -1,7 +1,7 @@
 // cluster_stats.hip — orbit_cluster_stats: the uncapped light counts of the cluster chain (include/orbit_abi_ext.h).
 //
 // The chain's own arithmetic (cluster_common.h), no output of it: one WAVE owns one screen tile and walks its samples as
-// cluster_mark_kernel does (mark_sample, depth_slice, the same bounds words), keeping per z slice (lane = slice) the
+// cluster_mark_kernel does (mark_sample, mark_values, mark_slice_bounds), keeping per z slice (lane = slice) the
 // number of in-grid samples and the depth bounds in registers.  Lane s then builds cluster s's box with the chain's
 // cluster_aabb from those bounds.  A workgroup is a 4 x 4 square of tiles; its lights are transformed as
 // light_prepare_body does, a chunk at a time (one light per thread), filtered against the union of the workgroup's
@@ -10,7 +10,6 @@
 // NaN does not filter.  Non-point lights are in every cluster and are counted without a test (light_culling.comp:116).
 // Counts go to LDS as 64-bit sums, then one 64-bit atomic per non-zero counter and workgroup: order-independent.
 #include "cluster_common.h"
-#include "scan.h"
 
 namespace orbit {
 
@@ -37,7 +36,7 @@ __device__ __forceinline__ uint32_t light_class(uint32_t count) {
 
 __global__ __launch_bounds__(kStatsThreads) void cluster_stats_kernel(const ClusterStatsParams p) {
     __shared__ float4 s_cand[kStatsThreads];      // view-space point lights behind the union filter
-    __shared__ float s_wbox[kStatsWaves][8];      // per wave: the union of its tile's boxes (6) and its any-NaN flag
+    __shared__ float s_wbox[kStatsWaves][8];      // per wave: a row as union_row_store leaves it (its tile's boxes), and in word 7 whether the tile has a cluster
     __shared__ uint32_t s_ncand[2], s_nonpoint[2]; // per chunk (by parity): candidates, non-point lights
     __shared__ unsigned long long s_cnt[kWords];
     const OrbitMarkActivePush &pc = p.pc;
@@ -60,40 +59,22 @@ __global__ __launch_bounds__(kStatsThreads) void cluster_stats_kernel(const Clus
             size_t index;
             const bool valid = mark_sample(pc, cx, cy, tile, base + lane, index);
             const float d = valid ? p.depth[index] : 0.0f;
-            uint32_t slice = 0xFFFFFFFFu, bmin = 0, bmax = 0;
-            if (valid) {
-                const float linear_z = pc.z_near / d;                       // mark_active.comp:28
-                slice = depth_slice(linear_z, pc.z_scale, pc.z_bias);
-                const float inv = 1.0f - d;                                 // :33
-                bmin = inv != inv ? 0x7fc00000u : __float_as_uint(inv);
-                bmax = __float_as_uint(d);                                  // :34
-            }
-            const bool in_grid = valid && slice < cz;                       // :31
+            const MarkValues v = mark_values(pc, valid, d);
+            const bool in_grid = valid && v.slice < cz;                     // mark_active.comp:31
             outside += (uint32_t)__popcll(__ballot(valid && !in_grid));
-            uint32_t todo = wave_reduce_or(in_grid ? 1u << (slice & 31u) : 0u);
-            while (todo) {
-                const uint32_t s = (uint32_t)__builtin_ctz(todo);
-                todo &= todo - 1u;
-                const bool mine = in_grid && slice == s;
+            const uint32_t todo = wave_reduce_or(in_grid ? v.bit : 0u);
+            mark_slice_bounds(todo, v, lane, acc_min, acc_max, [&](uint32_t s, bool mine) {
                 const uint32_t n = (uint32_t)__popcll(__ballot(mine));
-                const uint32_t m1 = wave_reduce_max(mine ? bmin : 0u);
-                const uint32_t m2 = wave_reduce_max(mine ? bmax : 0u);
-                if (lane == s) {
-                    n_samples += n;
-                    acc_min = max(acc_min, m1);
-                    acc_max = max(acc_max, m2);
-                }
-            }
+                n_samples += lane == s ? n : 0u;
+            });
         }
     }
     const bool active = n_samples != 0u; // (lane < cz only)
     const uint64_t active_mask = __ballot(active);
 
     // ---- lane s: cluster s's box (light_culling.comp:62-90), the wave's union of them, the workgroup's union
-    const float inf = __uint_as_float(0x7f800000u);
     Aabb3 box;
-#pragma unroll
-    for (int i = 0; i < 3; i++) box.mn[i] = inf, box.mx[i] = -inf; // absent cluster: the empty box, neutral in the union
+    box_empty(box.mn, box.mx);
     if (active) {
         OrbitClusterDepthBounds db;
         db.min_depth = acc_min;
@@ -101,43 +82,26 @@ __global__ __launch_bounds__(kStatsThreads) void cluster_stats_kernel(const Clus
         box = cluster_aabb(p.info, tile + lane * tiles, db);
     }
     {
-        bool nan = false;
-        float lo[3], hi[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            lo[i] = box.mn[i], hi[i] = box.mx[i];
-            nan = nan || lo[i] != lo[i] || hi[i] != hi[i];
-        }
-        const bool wave_nan = __ballot(nan) != 0ull;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const float ol = __shfl_xor(lo[i], d, 64), oh = __shfl_xor(hi[i], d, 64);
-                lo[i] = ol < lo[i] ? ol : lo[i];
-                hi[i] = oh > hi[i] ? oh : hi[i];
-            }
-        }
+        Aabb3 u = box;
+        const bool wave_nan = lanes_union<64>(u.mn, u.mx);
         if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) s_wbox[wave][i] = lo[i], s_wbox[wave][3 + i] = hi[i];
-            s_wbox[wave][6] = wave_nan ? 1.0f : 0.0f;
+            union_row_store(s_wbox[wave], u.mn, u.mx, wave_nan);
             s_wbox[wave][7] = active_mask != 0ull ? 1.0f : 0.0f;
         }
     }
     __syncthreads();
-    Aabb3 un;
-    bool un_nan = false, any_active = false;
-#pragma unroll
-    for (int i = 0; i < 3; i++) un.mn[i] = inf, un.mx[i] = -inf;
+    // (not union_rows: its sixteen rows a few at a time cost the regime scene 1 us of this call's 36 — DESIGN.md 4.17.  The
+    // rows' NaN flags are the lanes': a row holds a NaN only if its flag is set.)
+    BoxUnion un = union_empty();
+    bool any_active = false;
     for (uint32_t w = 0; w < kStatsWaves; w++) {
 #pragma unroll
         for (int i = 0; i < 3; i++) {
             const float lo = s_wbox[w][i], hi = s_wbox[w][3 + i];
-            un.mn[i] = lo < un.mn[i] ? lo : un.mn[i];
-            un.mx[i] = hi > un.mx[i] ? hi : un.mx[i];
+            un.box.mn[i] = lo < un.box.mn[i] ? lo : un.box.mn[i];
+            un.box.mx[i] = hi > un.box.mx[i] ? hi : un.box.mx[i];
         }
-        un_nan = un_nan || s_wbox[w][6] != 0.0f;
+        un.any_nan = un.any_nan || s_wbox[w][6] != 0.0f;
         any_active = any_active || s_wbox[w][7] != 0.0f;
     }
 
@@ -153,7 +117,7 @@ __global__ __launch_bounds__(kStatsThreads) void cluster_stats_kernel(const Clus
             const OrbitLightData &l = p.lights[i];
             point = l.light_type == ORBIT_LIGHT_TYPE_POINT;
             v = light_to_view(p.info, l); // light_culling.comp:103, :111
-            cand = point && (un_nan || sphere_hits(un, v));
+            cand = point && light_passes(un, true, v);
         }
         const uint64_t np = __ballot(i < nl && !point), m = __ballot(cand);
         uint32_t at = 0;

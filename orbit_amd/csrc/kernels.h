@@ -467,6 +467,8 @@ hipError_t launch_cluster_assign(const ClusterAssignParams &p, uint32_t num_cus,
 // chunk bases the emit launches keep in LDS (1 Mi tiles = 16 Mi dispatch records)
 constexpr uint32_t kEmitChunkTable = 1024;
 
+// One word stored in stream order (a header or a total that the host knows and a kernel behind it reads)
+hipError_t launch_write_word(uint32_t *dst, uint32_t v, hipStream_t s);
 // Exclusive scan of `n` words by one 1024-thread block; *total = sum.
 hipError_t launch_scan_exclusive(const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total, hipStream_t s);
 // Two-level variant for long inputs: out_local[i] is the exclusive prefix inside

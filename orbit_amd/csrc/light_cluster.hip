@@ -26,10 +26,28 @@
 //   mark launch also takes the compaction's counts): DESIGN.md 4.4.
 #include "cluster_common.h"
 #include "handoff.h"
+#include <type_traits>
 
 namespace orbit {
 
 namespace {
+
+// The two buffers the chain shares with its caller (include/orbit_abi.h), as words.  The active list: a header of four —
+// an indirect dispatch's x, y, z and the number of active clusters — and the clusters' linear indices; the compaction
+// writes it, the assignment reads it.  The light-index list: light_count and the indices.
+template <class Byte>
+__host__ __device__ __forceinline__ auto as_words(Byte *bytes) {
+    return reinterpret_cast<std::conditional_t<std::is_const_v<Byte>, const uint32_t, uint32_t> *>(bytes);
+}
+constexpr uint32_t kActiveCount = 3;
+template <class Byte> __host__ __device__ __forceinline__ auto active_header(Byte *unique) { return as_words(unique); }
+template <class Byte> __host__ __device__ __forceinline__ auto active_indices(Byte *unique) { return as_words(unique + ORBIT_COMPACT_HEADER); }
+__host__ __device__ __forceinline__ uint32_t *light_count(uint8_t *list) { return as_words(list); }
+__host__ __device__ __forceinline__ uint32_t *light_indices(uint8_t *list) { return as_words(list + ORBIT_LIGHT_INDEX_HEADER); }
+// the clusters the assignment works on: the header's count, within what the context was created for
+__device__ __forceinline__ uint32_t active_count(const ClusterAssignParams &p) {
+    return min(active_header(p.unique)[kActiveCount], p.max_clusters);
+}
 
 // ---------------------------------------------------------------- mark_active
 // mark_active.comp:27-57.  Lane L (< cz) accumulates the bounds of slice L.  A wave takes kMarkTiles consecutive tiles
@@ -95,33 +113,12 @@ __global__ __launch_bounds__(kMarkWaves * 64) void cluster_mark_kernel(const Clu
                 valid = sample(tile, base + (uint32_t)lane, index);
                 d = valid ? p.depth[index] : 0.0f;
             }
-            uint32_t slice = 0xFFFFFFFFu, bmin = 0, bmax = 0, bit = 0;
-            if (valid) {
-                const float linear_z = pc.z_near / d;                       // :28
-                // cluster_common.glsl:18-20 as compiled (mark_active.comp.spv): one fused operation — through the
-                // hardware log2 where that provably gives the canonical slice (orbit_device.h depth_slice)
-                slice = depth_slice(linear_z, pc.z_scale, pc.z_bias);
-                bit = shl1(slice);                                          // :30
-                const float inv = 1.0f - d;                                 // :33
-                // the sign / payload of a NaN produced by arithmetic is implementation-defined: canonical quiet NaN
-                bmin = inv != inv ? 0x7fc00000u : __float_as_uint(inv);
-                bmax = __float_as_uint(d);                                  // :34
-            }
-            const uint32_t chunk_mask = wave_reduce_or(bit);
+            const MarkValues v = mark_values(pc, valid, d);
+            const uint32_t chunk_mask = wave_reduce_or(v.bit);
             tile_mask |= chunk_mask;
             uint32_t todo = chunk_mask;
             if (cz < 32u) todo &= (1u << cz) - 1u; // :31 slice < cluster_count.z
-            while (todo) {
-                const uint32_t s = (uint32_t)__builtin_ctz(todo);
-                todo &= todo - 1u;
-                const bool mine = valid && slice == s;
-                const uint32_t m1 = wave_reduce_max(mine ? bmin : 0u);
-                const uint32_t m2 = wave_reduce_max(mine ? bmax : 0u);
-                if ((uint32_t)lane == s) {
-                    acc_min = max(acc_min, m1);
-                    acc_max = max(acc_max, m2);
-                }
-            }
+            mark_slice_bounds(todo, v, (uint32_t)lane, acc_min, acc_max, [](uint32_t, bool) {});
         }
         if ((uint32_t)lane < cz) s_bounds[lane][wave * kMarkTiles + t] = make_uint2(acc_min, acc_max);
         if (lane == 0) s_masks[wave * kMarkTiles + t] = tile_mask;
@@ -182,7 +179,7 @@ __global__ __launch_bounds__(1024) void cluster_compact_kernel(const ClusterComp
     if (!EMIT) {
         if (threadIdx.x == 0) p.chunk_counts[slot_index] = block_total;
     } else {
-        uint32_t *idx = reinterpret_cast<uint32_t *>(p.unique + ORBIT_COMPACT_HEADER);
+        uint32_t *idx = active_indices(p.unique);
         const bool first = blockIdx.x == 0 && blockIdx.y == 0;
         const uint32_t slots = gridDim.x * gridDim.y, upto = first ? slots : slot_index;
         uint32_t part = 0;
@@ -199,11 +196,11 @@ __global__ __launch_bounds__(1024) void cluster_compact_kernel(const ClusterComp
         if (active && pos < p.index_capacity) idx[pos] = i + z * tiles; // cluster_common.glsl:1-4
         if (first && threadIdx.x == 0) {
             const uint32_t n = min(total, p.index_capacity);
-            uint32_t *hdr = reinterpret_cast<uint32_t *>(p.unique);
+            uint32_t *hdr = active_header(p.unique);
             hdr[0] = (n + 255u) / 256u; // active_cluster_compaction.comp:38-41
             hdr[1] = 1u;
             hdr[2] = 1u;
-            hdr[3] = n;
+            hdr[kActiveCount] = n;
             if (total > p.index_capacity) latch_status(p.status, ORBIT_E_CAPACITY);
         }
     }
@@ -267,23 +264,24 @@ constexpr uint32_t kNotPoint = 1u << 31; // candidate index flag: not a point li
 //   test   : lane = candidate.  A wave holds the AABBs of its 4 clusters in SGPRs, tests 64 candidates per step
 //            and turns the hit ballots into counts (WRITE = false, light_culling.comp:128-135) or into ascending
 //            index writes at the scanned offset (WRITE = true, :138-147).
-// A union contains every member box, and aabb_sphere_test is monotone in the box (each clamp distance, each square
-// and each partial sum can only shrink when the box grows, also in floating point), so no light that hits a member
-// box is ever filtered out; a union over boxes that contain a NaN does not filter at all.  Segment order == light
-// order, so the per-cluster lists come out ascending.  The reference runs one thread per cluster over all lights,
-// re-reading each 64-B light twice and redoing world_to_view x position per (cluster, light).
-struct BoxUnion {
-    Aabb3 box;
-    bool any_nan;
-};
+// Every filter tests against a union of boxes and so loses no light that hits a member box (BoxUnion, cluster_common.h).
+// Segment order == light order, so the per-cluster lists come out ascending.  The reference runs one thread per cluster
+// over all lights, re-reading each 64-B light twice and redoing world_to_view x position per (cluster, light).
 
-__device__ __forceinline__ void union_add(BoxUnion &u, const float lo[3], const float hi[3]) {
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        u.any_nan = u.any_nan || lo[i] != lo[i] || hi[i] != hi[i];
-        u.box.mn[i] = lo[i] < u.box.mn[i] ? lo[i] : u.box.mn[i];
-        u.box.mx[i] = hi[i] > u.box.mx[i] ? hi[i] : u.box.mx[i];
-    }
+// One filter round of a wave, the same at all three levels: lane = candidate {have, point, l}; the survivors (light_passes,
+// cluster_common.h) are appended behind the `at` entries the wave's list holds, in lane order = light order — append(pos)
+// stores the lane's candidate as entry pos.  Returns the list's new length.  (`tested`: ORBIT_TRIAGE builds count the
+// sphere-box tests executed.)
+template <class Append>
+__device__ __forceinline__ uint32_t filter_append(const BoxUnion &un, bool have, bool point, const float4 &l, uint32_t at,
+                                                  [[maybe_unused]] uint32_t &tested, Append append) {
+    const bool pass = have && light_passes(un, point, l);
+    const uint64_t m = __ballot(pass);
+#ifdef ORBIT_TRIAGE
+    tested += (uint32_t)__popcll(__ballot(have && point && !un.any_nan));
+#endif
+    if (pass) append(at + lane_prefix(m));
+    return at + (uint32_t)__popcll(m);
 }
 
 constexpr uint32_t kCoarseSplit = 4;                    // blocks that share the lights of one group
@@ -297,8 +295,7 @@ __global__ __launch_bounds__(256) void cluster_aabb_kernel(const ClusterAssignPa
         light_prepare_body(p, blockIdx.x);
         return;
     }
-    const uint32_t *hdr = reinterpret_cast<const uint32_t *>(p.unique);
-    const uint32_t n = min(hdr[3], p.max_clusters);
+    const uint32_t n = active_count(p);
     if (blockIdx.x == prepare_blocks) { // the launch's housekeeping block
         // what the count launch accumulates into: the number of its heavy blocks (and, per group below, the chunks' sums);
         // the chunk counts a counting mark launch left (the compaction has read them)
@@ -349,10 +346,10 @@ __global__ __launch_bounds__(256) void cluster_aabb_kernel(const ClusterAssignPa
     const uint32_t first = grp * kGroupClusters;
     static_assert(kScanChunk % kGroupClusters == 0, "a chunk of the offsets' sums is whole groups");
     if (threadIdx.x == 0 && first % kScanChunk == 0u) p.block_sums[(size_t)(first / kScanChunk) * kChunkSumStride] = 0u;
-    const uint32_t *unique_idx = reinterpret_cast<const uint32_t *>(p.unique + ORBIT_COMPACT_HEADER);
+    const uint32_t *unique_idx = active_indices(p.unique);
     const uint32_t u = first + threadIdx.x;
-    const float inf = __uint_as_float(0x7f800000u);
-    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf}; // absent cluster: the empty box, neutral in the union
+    float lo[3], hi[3];
+    box_empty(lo, hi);
     if (u < n) {
         const Aabb3 box = cluster_aabb(p, unique_idx[u]);
 #pragma unroll
@@ -362,41 +359,14 @@ __global__ __launch_bounds__(256) void cluster_aabb_kernel(const ClusterAssignPa
             p.aabb[6 * (size_t)u + 3 + i] = box.mx[i];
         }
     }
-    // union over the block: butterfly over the lanes, then over the four waves.  With a NaN anywhere the filter is
-    // bypassed (flag), so what the selects make of a NaN operand does not matter.
-    bool nan = false;
-#pragma unroll
-    for (int i = 0; i < 3; i++) nan = nan || lo[i] != lo[i] || hi[i] != hi[i];
-    const bool wave_nan = __ballot(nan) != 0ull;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const float ol = __shfl_xor(lo[i], d, 64), oh = __shfl_xor(hi[i], d, 64);
-            lo[i] = ol < lo[i] ? ol : lo[i];
-            hi[i] = oh > hi[i] ? oh : hi[i];
-        }
-    }
+    // union over the block: over the lanes, then over the four waves
+    const bool wave_nan = lanes_union<64>(lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) s_box[wave][i] = lo[i], s_box[wave][3 + i] = hi[i];
-        s_box[wave][6] = wave_nan ? 1.0f : 0.0f;
-    }
+    if (lane == 0) union_row_store(s_box[wave], lo, hi, wave_nan);
     __syncthreads();
     if (threadIdx.x == 0) {
-        BoxUnion un;
-        un.any_nan = false;
-#pragma unroll
-        for (int i = 0; i < 3; i++) un.box.mn[i] = inf, un.box.mx[i] = -inf;
-        for (int w = 0; w < 4; w++) {
-            union_add(un, &s_box[w][0], &s_box[w][3]);
-            un.any_nan = un.any_nan || s_box[w][6] != 0.0f;
-        }
-        float *g = p.group_box + 8 * (size_t)grp;
-#pragma unroll
-        for (int i = 0; i < 3; i++) g[i] = un.box.mn[i], g[3 + i] = un.box.mx[i];
-        g[6] = un.any_nan ? 1.0f : 0.0f;
+        const BoxUnion un = union_rows<4>(s_box);
+        union_row_store(p.group_box + 8 * (size_t)grp, un.box.mn, un.box.mx, un.any_nan);
     }
     __syncthreads(); // s_box is rewritten by the next group
     }
@@ -406,8 +376,7 @@ __global__ __launch_bounds__(256) void cluster_aabb_kernel(const ClusterAssignPa
 // [s * seg, (s + 1) * seg) against the group's union box into segment s of the group's list, in light order.
 __global__ __launch_bounds__(256) void cluster_coarse_kernel(const ClusterAssignParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t *hdr = reinterpret_cast<const uint32_t *>(p.unique);
-    const uint32_t n = min(hdr[3], p.max_clusters);
+    const uint32_t n = active_count(p);
     for (uint32_t vb = blockIdx.x; (vb / kCoarseSplit) * kGroupClusters < n; vb += gridDim.x) { // as in cluster_aabb_kernel
     const uint32_t group = vb / kCoarseSplit;
     const float *g = p.group_box + 8 * (size_t)group;
@@ -436,17 +405,10 @@ __global__ __launch_bounds__(256) void cluster_coarse_kernel(const ClusterAssign
         for (uint32_t r = 0; r < 4; r++) {
             const uint32_t li = b0 + r * 64u + (uint32_t)lane;
             const bool point = (pt >> r) & 1u;
-            const bool pass = li < end && (!point || un.any_nan || sphere_hits(un.box, l[r]));
-            const uint64_t m = __ballot(pass);
-            if (pass) {
-                const uint32_t pos = cnt + lane_prefix(m);
+            cnt = filter_append(un, li < end, point, l[r], cnt, tested, [&](uint32_t pos) {
                 out[pos] = li | (point ? 0u : kNotPoint);
                 out_l[pos] = l[r];
-            }
-            cnt += (uint32_t)__popcll(m);
-#ifdef ORBIT_TRIAGE
-            tested += (uint32_t)__popcll(__ballot(li < end && point && !un.any_nan));
-#endif
+            });
         }
     }
     ORBIT_COUNT_TESTS(0, tested);
@@ -462,13 +424,30 @@ __global__ __launch_bounds__(256) void cluster_coarse_kernel(const ClusterAssign
 // `place_blocks` take 256 clusters each (thread = cluster), compute the offsets and copy the lists of the clusters
 // whose hits the count launch kept (all but a few); the others stride over the heavy blocks and test those clusters
 // again (WRITE = true below).
+// A thread's share of the offset of cluster `upto`, STRIDE threads together: the sums of the chunks before `chunk`, upto's
+// own, and the counts of that chunk's clusters in front of upto (ROUNDS x STRIDE of them reach that far).  The counts
+// are loaded together: a loop of load-and-add is ROUNDS round trips in a row.
+template <uint32_t STRIDE, uint32_t ROUNDS>
+__device__ __forceinline__ uint32_t offset_share(const ClusterAssignParams &p, uint32_t chunk, uint32_t upto, uint32_t t) {
+    uint32_t part = 0;
+    for (uint32_t k = t; k < chunk; k += STRIDE) part += p.block_sums[(size_t)k * kChunkSumStride];
+    uint32_t cv[ROUNDS];
+#pragma unroll
+    for (uint32_t j = 0; j < ROUNDS; j++) {
+        const uint32_t v = chunk * kScanChunk + j * STRIDE + t;
+        cv[j] = v < upto ? p.counts[v] : 0u;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < ROUNDS; j++) part += cv[j];
+    return part;
+}
+
 __device__ __forceinline__ void cluster_place_body(const ClusterAssignParams &p, uint32_t place_blocks) {
     __shared__ uint32_t s_scan[4 + 1];
     __shared__ uint32_t s_part[4];
-    const uint32_t *hdr = reinterpret_cast<const uint32_t *>(p.unique);
-    const uint32_t *unique_idx = reinterpret_cast<const uint32_t *>(p.unique + ORBIT_COMPACT_HEADER);
-    uint32_t *out = reinterpret_cast<uint32_t *>(p.light_index_buffer + ORBIT_LIGHT_INDEX_HEADER);
-    const uint32_t n = min(hdr[3], p.max_clusters);
+    const uint32_t *unique_idx = active_indices(p.unique);
+    uint32_t *out = light_indices(p.light_index_buffer);
+    const uint32_t n = active_count(p);
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
     static_assert(kScanChunk % 256u == 0, "a piece of 256 clusters lies in one chunk");
     for (uint32_t piece = blockIdx.x; piece * 256u < max(n, 1u); piece += place_blocks) { // (n = 0: block 0 writes the header)
@@ -480,18 +459,8 @@ __device__ __forceinline__ void cluster_place_body(const ClusterAssignParams &p,
 #pragma unroll
         for (uint32_t j = 0; j < kPlaceDirect / 4; j++) // the first 64 B whatever the count says: no load waits for another
             h[j] = reinterpret_cast<const uint4 *>(p.hit_cache + (size_t)min(u, p.max_clusters) * kHitCache)[j];
-        const uint32_t chunk = piece * 256u / kScanChunk;
-        uint32_t part = 0;
-        for (uint32_t k = t; k < chunk; k += 256u) part += p.block_sums[(size_t)k * kChunkSumStride];
-        uint32_t cv[kScanChunk / 256u - 1u]; // the counts of the chunk's clusters in front of the piece, loaded together
-#pragma unroll
-        for (uint32_t j = 0; j < kScanChunk / 256u - 1u; j++) {
-            const uint32_t v = chunk * kScanChunk + j * 256u + t;
-            cv[j] = v < piece * 256u ? p.counts[v] : 0u;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kScanChunk / 256u - 1u; j++) part += cv[j];
-        part = wave_reduce_add(part);
+        // (the piece is one of its chunk's kScanChunk / 256: at most one less lie in front of it)
+        const uint32_t part = wave_reduce_add(offset_share<256u, kScanChunk / 256u - 1u>(p, piece * 256u / kScanChunk, piece * 256u, t));
         if (lane == 0) s_part[wave] = part;
         uint32_t piece_total;
         const uint32_t ex = block_exclusive_scan<4>(cnt, s_scan, &piece_total); // (its barriers order s_part as well)
@@ -521,11 +490,23 @@ __device__ __forceinline__ void cluster_place_body(const ClusterAssignParams &p,
         }
         if (t == 0 && piece * 256u + 256u >= n) { // the last piece: light_count = the sum of all counts (atomicAdd total, :136)
             const uint32_t total = before + piece_total;
-            *reinterpret_cast<uint32_t *>(p.light_index_buffer) = total;
+            *light_count(p.light_index_buffer) = total;
             if (total > p.light_index_capacity) latch_status(p.status, ORBIT_E_CAPACITY);
         }
         __syncthreads(); // s_part is rewritten by the next piece
     }
+}
+
+// What the count launch publishes of a block of kClustersPerBlock clusters (one lane's): its capped counts' sum into the sum
+// of its chunk — what every offset behind it is made of — and, if one of its clusters found more than kHitCache lights,
+// the block into the heavy list.  ONE atomic per block, and every chunk's word on a line of its own: atomics on one 128-B
+// line queue in one L2 channel whatever their words (17 000 of them on the 34 adjacent words of config 4: 85 us).
+__device__ __forceinline__ void publish_block(const ClusterAssignParams &p, uint32_t block_first, uint32_t block_total, bool heavy) {
+    if (block_total != 0u)
+        (void)__hip_atomic_fetch_add(p.block_sums + (size_t)(block_first / kScanChunk) * kChunkSumStride, block_total,
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (heavy)
+        p.block_base[__hip_atomic_fetch_add(p.total, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = block_first / kClustersPerBlock;
 }
 
 // ---- the count launch's item for ONE wave (see cluster_assign_kernel): eight clusters, lane c < 8 holds cluster c
@@ -556,32 +537,19 @@ __device__ __forceinline__ void wave_item_loads(const ClusterAssignParams &p, Wa
 __device__ __forceinline__ void wave_item(const ClusterAssignParams &p, const WaveItem &w, uint32_t block_first, uint32_t n,
                                           uint32_t seg_counts, float4 *s_cand, uint32_t *s_cand_idx, float *s_box, int lane) {
     const bool owns = lane < (int)kWaveClusters && block_first + (uint32_t)lane < n;
-    const float inf = __uint_as_float(0x7f800000u);
-    // the eight boxes: absent cluster = the empty box, neutral in the union; union by a butterfly over lanes 0..7
+    // the eight boxes: every cluster's where the test loop reads it with uniform addresses (LDS broadcasts; 48 scalar
+    // registers held across the loop spilled), and their union over lanes 0..7
     float lo[3], hi[3];
-    bool nan = false;
+    box_empty(lo, hi);
 #pragma unroll
-    for (int i = 0; i < 3; i++) {
-        lo[i] = owns ? w.lo[i] : inf, hi[i] = owns ? w.hi[i] : -inf;
-        nan = nan || lo[i] != lo[i] || hi[i] != hi[i];
-    }
-    BoxUnion un;
-    un.any_nan = (__ballot(nan) & 0xFFull) != 0ull; // (then the filter is bypassed: what the selects make of a NaN does not matter)
-    // every cluster's box where the test loop reads it with uniform addresses (LDS broadcasts; 48 scalar registers
-    // held across the loop spilled), and the union by a butterfly over lanes 0..7
+    for (int i = 0; i < 3; i++)
+        if (owns) lo[i] = w.lo[i], hi[i] = w.hi[i];
     if (lane < (int)kWaveClusters) {
 #pragma unroll
         for (int i = 0; i < 3; i++) s_box[lane * 8 + i] = lo[i], s_box[lane * 8 + 4 + i] = hi[i];
     }
-#pragma unroll
-    for (int d = (int)kWaveClusters / 2; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const float ol = __shfl_xor(lo[i], d, 64), oh = __shfl_xor(hi[i], d, 64);
-            lo[i] = ol < lo[i] ? ol : lo[i];
-            hi[i] = oh > hi[i] ? oh : hi[i];
-        }
-    }
+    BoxUnion un;
+    un.any_nan = lanes_union<(int)kWaveClusters>(lo, hi);
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         un.box.mn[i] = __uint_as_float(__builtin_amdgcn_readfirstlane((int)__float_as_uint(lo[i])));
@@ -595,17 +563,10 @@ __device__ __forceinline__ void wave_item(const ClusterAssignParams &p, const Wa
         const uint32_t cnt = (uint32_t)__shfl((int)seg_counts, (int)(r * 8u + ((uint32_t)lane >> 3)), 64);
         const bool have = ((uint32_t)lane & 7u) < cnt;
         const bool point = (w.tag[r] & kNotPoint) == 0u;
-        const bool pass = have && (!point || un.any_nan || sphere_hits(un.box, w.l[r]));
-        const uint64_t m = __ballot(pass);
-#ifdef ORBIT_TRIAGE
-        n_filter += (uint32_t)__popcll(__ballot(have && point && !un.any_nan));
-#endif
-        if (pass) {
-            const uint32_t pos = total + lane_prefix(m);
+        total = filter_append(un, have, point, w.l[r], total, n_filter, [&](uint32_t pos) {
             s_cand[pos] = w.l[r];
             s_cand_idx[pos] = w.tag[r];
-        }
-        total += (uint32_t)__popcll(m);
+        });
     }
     wave_lds_fence();
     // test: lane = candidate, against the eight boxes in turn (a rolled loop: unrolled, the compiler hoists all 48 box
@@ -643,13 +604,7 @@ __device__ __forceinline__ void wave_item(const ClusterAssignParams &p, const Wa
     if (owns) p.counts[block_first + (uint32_t)lane] = capped;
     const uint32_t block_total = wave_reduce_add(capped);
     const bool heavy = __ballot(capped > kHitCache) != 0ull;
-    if (lane == 0) { // as the four-wave path does at its end
-        if (block_total != 0u)
-            (void)__hip_atomic_fetch_add(p.block_sums + (size_t)(block_first / kScanChunk) * kChunkSumStride, block_total,
-                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (heavy)
-            p.block_base[__hip_atomic_fetch_add(p.total, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = block_first / kClustersPerBlock;
-    }
+    if (lane == 0) publish_block(p, block_first, block_total, heavy);
 }
 
 #ifndef ORBIT_ASSIGN_WAVES // five waves per SIMD: five blocks per CU resident (96 registers; the count launch is its blocks' latencies)
@@ -688,9 +643,8 @@ void cluster_assign_kernel(const ClusterAssignParams p, uint32_t place_blocks) {
 #else
 #define ORBIT_PHASE_STAMP() ((void)0)
 #endif
-    const uint32_t *hdr = reinterpret_cast<const uint32_t *>(p.unique);
-    const uint32_t *unique_idx = reinterpret_cast<const uint32_t *>(p.unique + ORBIT_COMPACT_HEADER);
-    uint32_t *out = reinterpret_cast<uint32_t *>(p.light_index_buffer + ORBIT_LIGHT_INDEX_HEADER);
+    const uint32_t *unique_idx = active_indices(p.unique);
+    uint32_t *out = light_indices(p.light_index_buffer);
     // Little arithmetic (config 4 executes 0.4 M tests here) in a great many short waves: what the launch costs is the
     // instructions its waves issue and the dependent round trips of a block.  The header word n is loaded
     // first but consumed only after the first item's loads that need no other load's result are in flight (indices are
@@ -698,7 +652,7 @@ void cluster_assign_kernel(const ClusterAssignParams p, uint32_t place_blocks) {
     // (wave_item); in the four-wave form the first 16 entries of every segment are fetched before the segment counts are
     // known, which serves groups whose segments hold no more; up to 64 per segment take one fetched step, longer lists
     // the stepped path.
-    const uint32_t n_raw = hdr[3];
+    const uint32_t n_raw = active_header(p.unique)[kActiveCount];
     uint32_t n = 0;
     bool first_item = true;
     constexpr uint32_t kSeg = kLightTile / kAssignWaves; // LDS candidates per wave and step
@@ -776,16 +730,7 @@ void cluster_assign_kernel(const ClusterAssignParams p, uint32_t place_blocks) {
         // chunk), the counts of the chunk's clusters before the wave's first one, the wave's own clusters before the lane's
         static_assert(kScanChunk % kClustersPerBlock == 0, "a block's clusters share a scan chunk");
         const uint32_t chunk = min(block_first, p.max_clusters) / kScanChunk;
-        uint32_t part = 0;
-        for (uint32_t k = (uint32_t)lane; k < chunk; k += 64u) part += p.block_sums[(size_t)k * kChunkSumStride];
-        uint32_t cv[kScanChunk / 64u]; // (loaded together: a loop of load-and-add is sixteen round trips in a row)
-#pragma unroll
-        for (uint32_t j = 0; j < kScanChunk / 64u; j++) {
-            const uint32_t v = chunk * kScanChunk + j * 64u + (uint32_t)lane;
-            cv[j] = v < min(u0, p.max_clusters) ? p.counts[v] : 0u;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kScanChunk / 64u; j++) part += cv[j];
+        const uint32_t part = offset_share<64u, kScanChunk / 64u>(p, chunk, min(u0, p.max_clusters), (uint32_t)lane);
         const uint32_t mine = lane < kClustersPerWave ? my_limit : 0u;
         my_offset = wave_reduce_add(part) + (wave_inclusive_scan(mine) - mine);
     }
@@ -815,14 +760,8 @@ void cluster_assign_kernel(const ClusterAssignParams p, uint32_t place_blocks) {
         if (lane == 0) s_fast = lng ? 0u : mid ? 1u : 2u; // 2: every segment within the speculative fetch
     }
     ORBIT_PHASE_STAMP();
-    // absent cluster: the empty box, neutral in the union
-    {
-        const float inf = __uint_as_float(0x7f800000u);
-#pragma unroll
-        for (int i = 0; i < 3; i++) box.mn[i] = owns ? box.mn[i] : inf, box.mx[i] = owns ? box.mx[i] : -inf;
-    }
-    // the wave's boxes into scalar registers; their union over the wave (lanes 0 .. kClustersPerWave - 1 hold them), then over the block.
-    // With a NaN anywhere the filter is bypassed (flag), so what the selects make of a NaN operand does not matter.
+    if (!owns) box_empty(box.mn, box.mx);
+    // the wave's boxes into scalar registers; their union over the wave (lanes 0 .. kClustersPerWave - 1 hold them), then over the block
     float mn[kClustersPerWave][3], mx[kClustersPerWave][3];
     uint32_t offset[kClustersPerWave], limit[kClustersPerWave], count[kClustersPerWave];
     bool valid[kClustersPerWave];
@@ -839,43 +778,13 @@ void cluster_assign_kernel(const ClusterAssignParams p, uint32_t place_blocks) {
         valid[c] = u0 + c < n;
     }
     {
-        bool nan = false;
-        float lo[3], hi[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            lo[i] = box.mn[i], hi[i] = box.mx[i];
-            nan = nan || lo[i] != lo[i] || hi[i] != hi[i];
-        }
-        const bool wave_nan = (__ballot(nan) & ((1ull << kClustersPerWave) - 1ull)) != 0ull;
-#pragma unroll
-        for (int d = kClustersPerWave / 2; d >= 1; d >>= 1) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const float ol = __shfl_xor(lo[i], d, 64), oh = __shfl_xor(hi[i], d, 64);
-                lo[i] = ol < lo[i] ? ol : lo[i];
-                hi[i] = oh > hi[i] ? oh : hi[i];
-            }
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) s_wbox[wave][i] = lo[i], s_wbox[wave][3 + i] = hi[i];
-            s_wbox[wave][6] = wave_nan ? 1.0f : 0.0f;
-        }
+        Aabb3 u = box;
+        const bool wave_nan = lanes_union<kClustersPerWave>(u.mn, u.mx);
+        if (lane == 0) union_row_store(s_wbox[wave], u.mn, u.mx, wave_nan);
     }
     __syncthreads();
     ORBIT_PHASE_STAMP();
-    BoxUnion un;
-    un.any_nan = false;
-    {
-        const float inf = __uint_as_float(0x7f800000u);
-#pragma unroll
-        for (int i = 0; i < 3; i++) un.box.mn[i] = inf, un.box.mx[i] = -inf;
-    }
-#pragma unroll
-    for (int w = 0; w < kAssignWaves; w++) {
-        union_add(un, &s_wbox[w][0], &s_wbox[w][3]);
-        un.any_nan = un.any_nan || s_wbox[w][6] != 0.0f;
-    }
+    const BoxUnion un = union_rows<kAssignWaves>(s_wbox);
     const uint32_t ctotal = s_cpre[kCoarseSegs];
     const bool fast = !WRITE && s_fast != 0u, spec = !WRITE && s_fast == 2u; // block-uniform
 
@@ -893,17 +802,11 @@ void cluster_assign_kernel(const ClusterAssignParams p, uint32_t place_blocks) {
         for (uint32_t r = 0; r < kLoads; r++) {
             if (r >= filter_rounds) break;
             const bool point = (tag[r] & kNotPoint) == 0u;
-            const bool pass = have[r] && (!point || un.any_nan || sphere_hits(un.box, l[r]));
-            const uint64_t m = __ballot(pass);
-#ifdef ORBIT_TRIAGE
-            n_filter += (uint32_t)__popcll(__ballot(have[r] && point && !un.any_nan));
-#endif
-            if (pass) {
-                const uint32_t pos = wave * kSeg + seg_n + lane_prefix(m);
-                s_cand[pos] = l[r];
-                s_cand_idx[pos] = tag[r];
-            }
-            seg_n += (uint32_t)__popcll(m);
+            seg_n = filter_append(un, have[r], point, l[r], seg_n, n_filter, [&](uint32_t pos) {
+                const uint32_t at = wave * kSeg + pos; // (said once: said per store, it costs the count launch a spilled register)
+                s_cand[at] = l[r];
+                s_cand_idx[at] = tag[r];
+            });
         }
         if (lane == 0) s_wave_cnt[wave] = seg_n;
     };
@@ -1030,23 +933,17 @@ void cluster_assign_kernel(const ClusterAssignParams p, uint32_t place_blocks) {
                 p.offset_image[2 * (size_t)my_ci + 1] = lim;
             }
         }
-        if (!WRITE) { // the chunk's sum (what every offset behind it is made of) and the list of heavy blocks
+        if (!WRITE) { // (for publish_block)
             if (lane < kClustersPerWave) s_wtot[wave * kClustersPerWave + lane] = capped;
         }
     }
     if (!WRITE) {
         __syncthreads(); // (also: s_cpre / s_wbox are rewritten by the next block of clusters)
         if (threadIdx.x == 0) {
-            // ONE atomic per block, and every chunk's word on a line of its own: atomics on one 128-B line queue in one
-            // L2 channel whatever their words (17 000 of them on the 34 adjacent words of config 4: 85 us)
             uint32_t block_total = 0, most = 0;
 #pragma unroll
             for (int c = 0; c < kClustersPerBlock; c++) block_total += s_wtot[c], most = max(most, s_wtot[c]);
-            if (block_total != 0u)
-                (void)__hip_atomic_fetch_add(p.block_sums + (size_t)(block_first / kScanChunk) * kChunkSumStride, block_total,
-                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (most > kHitCache)
-                p.block_base[__hip_atomic_fetch_add(p.total, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = block_first / kClustersPerBlock;
+            publish_block(p, block_first, block_total, most > kHitCache);
         }
     }
     if (WRITE) __syncthreads(); // s_cpre / s_wbox are rewritten by the next block of clusters
@@ -1062,9 +959,6 @@ void cluster_assign_kernel(const ClusterAssignParams p, uint32_t place_blocks) {
     }
 #endif
 }
-
-// header for an empty active list: light_count = 0 (cluster.rs:575-581)
-__global__ void write_word(uint32_t *p, uint32_t v) { *p = v; }
 
 // orbit_debug_log2_guard (tests): depth_slice against depth_slice_canonical for EVERY float bit pattern in [lo, hi] —
 // out[0] = mismatches, out[1] = samples the canonical path decided, out[2] = bits of the largest
@@ -1110,8 +1004,7 @@ hipError_t launch_cluster_compact(const ClusterCompactParams &p, hipStream_t s) 
     const uint32_t nchunks = (tiles + 1023) / 1024;
     const uint32_t cz = p.cc[2];
     if (nchunks == 0 || cz == 0) {
-        hipLaunchKernelGGL(write_word, dim3(1), dim3(1), 0, s, reinterpret_cast<uint32_t *>(p.unique) + 3, 0u);
-        return hipGetLastError();
+        return launch_write_word(active_header(p.unique) + kActiveCount, 0u, s); // an empty active list
     }
     if (!p.counted) {
         hipLaunchKernelGGL(cluster_compact_kernel<false>, dim3(nchunks, cz), dim3(1024), 0, s, p);
@@ -1126,8 +1019,7 @@ hipError_t launch_cluster_assign(const ClusterAssignParams &p, uint32_t num_cus,
     const uint32_t nl = p.info.global_light_count;
     const uint32_t prepare_blocks = (nl + 255u) / 256u;
     if (p.max_clusters == 0) {
-        hipLaunchKernelGGL(write_word, dim3(1), dim3(1), 0, s, reinterpret_cast<uint32_t *>(p.light_index_buffer), 0u);
-        return hipGetLastError();
+        return launch_write_word(light_count(p.light_index_buffer), 0u, s); // light_count = 0 (cluster.rs:575-581)
     }
     // the number of active clusters is only known on the device: grids are bounded by the chip, not by the capacity,
     // and the kernels stride over the work that exists

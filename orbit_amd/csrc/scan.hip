@@ -77,7 +77,15 @@ hipError_t launch_scan_chunks_views(const ScanViews &sv, uint32_t count, uint32_
 }
 
 namespace {
+
+__global__ void write_word(uint32_t *dst, uint32_t v) { *dst = v; }
+
 } // namespace
+
+hipError_t launch_write_word(uint32_t *dst, uint32_t v, hipStream_t s) {
+    hipLaunchKernelGGL(write_word, dim3(1), dim3(1), 0, s, dst, v);
+    return hipGetLastError();
+}
 
 hipError_t launch_scan_chunks(const uint32_t *in, uint32_t *out_local, const uint32_t *n_src, uint32_t div,
                               uint32_t n_max, uint32_t *chunk_sums, hipStream_t s, uint32_t *clear,

@@ -189,6 +189,73 @@ def test_one_wave_and_four_wave_items_alternate_in_one_workgroup(torch_mod, engi
         _check(torch, engine, s, b, f"repetition {rep}")
 
 
+def test_one_wave_item_with_a_nan_box_in_a_short_last_block(torch_mod, engine, oracle):
+    """The count launch's one-wave item at two edges at once: a last block of fewer than eight clusters (its absent
+    clusters are empty boxes in the union) and a cluster box with NaN components in it (the block's union filter must
+    not apply: every candidate goes on to the single boxes).  40 x 24 pixels of depth 0.9 put all 15 tiles' clusters into
+    slice 0, so the active list is tiles 0..14 — a block of eight and one of seven; a NaN sample in tile 1 and one in
+    tile 14 make those two boxes NaN.  Eight lights in the first coarse segment: one wave's work whatever passes.
+    Point lights of radius 0 at chosen boxes' centres, one that reaches its neighbours, one directional light."""
+    from test_cluster_regimes_gpu import group_paths
+
+    import np_restatement as npr
+
+    torch = torch_mod
+    W, H, n_lights = 40, 24, 8
+    push, depth, info, lights = cluster_inputs(oracle, 31, W, H, n_lights, 8, 32)
+    depth[:] = np.float32(0.9)
+    depth[3, 12] = depth[20, 37] = np.nan
+    cc = [int(v) for v in push["cluster_count"]]
+    total = cap = cc[0] * cc[1] * cc[2]
+    om, ob = oracle.cluster_mark(push, depth)
+    ou, _ = oracle.cluster_compact(cc, om, cap)
+    n_active = int(ou[12:16].view(np.uint32)[0])
+    act = ou[16:16 + 4 * n_active].view(np.uint32)
+    mn, mx = npr.cluster_aabb(info, ob, act)
+    has_nan = np.isnan(mn).any(axis=1) | np.isnan(mx).any(axis=1)
+    assert n_active == 15 and np.flatnonzero(has_nan).tolist() == [1, 14]  # a full block and a block of seven, a NaN box in each
+    centre = ((mn + mx) * np.float32(0.5)).astype(np.float32)
+    view_inv = np.linalg.inv(np.asarray(info["world_to_view_matrix"], np.float64).reshape(4, 4).T)
+    lights["light_type"][:] = L.LIGHT_TYPE_POINT
+    for k, u in enumerate((0, 5, 5, 9, 12, 13)):
+        lights["position"][k, :3] = (view_inv @ np.append(centre[u].astype(np.float64), 1.0))[:3].astype(np.float32)
+        lights["outer_radius"][k] = 0.0
+    lights["position"][6, :3] = lights["position"][1, :3]
+    lights["outer_radius"][6] = np.float32(np.abs(mx[5] - mn[5]).max() * 1.2)
+    lights["light_type"][7] = L.LIGHT_TYPE_DIRECTIONAL
+    lcap = n_active * 256 + 16
+    ol, oimg, dropped = oracle.cluster_assign(info, ou, ob, lights, lcap, total)
+    counts = oimg[act][:, 1]
+    assert dropped == 0 and counts[1] == counts[14] == n_lights and 1 <= counts[has_nan == 0].min() < counts[has_nan == 0].max() < n_lights
+    assert group_paths(info, ou, ob, lights, 6000)[0] == ["wave"]  # (6000: the engine fixture's max_lights)
+    s = dict(push=push, depth=depth, info=info, lights=lights, cc=cc, total=total, cap=cap, lcap=lcap, n_active=n_active,
+             n_lights=n_lights, ref=(om, ob, ou, ol, oimg))
+    b = _buffers(torch, s)
+    for what in ("first call", "second call"):  # (the second takes the group order the first left)
+        _poison(b)
+        _call(engine, s, b)
+        _check(torch, engine, s, b, what)
+
+
+def test_a_grid_without_clusters_gets_its_two_counts(torch_mod, engine, oracle):
+    """No z slices, so no cluster: the compaction stores the active list's count and the assignment light_count
+    (cluster.rs:575-581) — 0 both, one word each stored from the host's side — and neither writes behind its header."""
+    torch = torch_mod
+    s = _scene(oracle, 0)
+    b = _buffers(torch, s)
+    cc = (s["cc"][0], s["cc"][1], 0)
+    info = s["info"].copy()
+    info["cluster_count"] = cc
+    engine.cluster_compact(cc, b["gm"], b["gu"], s["cap"])
+    engine.cluster_assign(info, b["gu"], b["gb"], b["lights"], b["gl"], s["lcap"], b["gimg"])
+    torch.cuda.synchronize()
+    engine.status()
+    gu, gl = host(b["gu"]), host(b["gl"])
+    assert int(gu[12:16].view(np.uint32)[0]) == 0 and bool((gu[16:] == 0xEE).all())
+    assert int(gl[:4].view(np.uint32)[0]) == 0 and bool((gl[4:] == 0xEE).all())
+    assert not host(b["gimg"]).any()
+
+
 def test_hardware_log2_slice_equals_the_canonical_slice_for_every_float(torch_mod, engine, oracle):
     """cluster_mark takes a sample's z slice from v_log_f32 wherever that cannot differ from the canonical software log2
     (orbit_amd/csrc/orbit_device.h depth_slice: outside a guard band around the integers of the fused result, normal finite
