@@ -286,6 +286,11 @@ extern "C" {
     pub fn orbit_frame_late(ctx: *mut OrbitCtx, frame: *const OrbitFrameLate, stream: *mut c_void) -> i32;
     pub fn orbit_ctx_meshlet_stream_culls(ctx: *const OrbitCtx) -> u64;
     pub fn orbit_ctx_meshlet_class_culls(ctx: *const OrbitCtx) -> u64;
+    /// Pass-0 culls decided per block of 32 meshlets from the stream's block bounds (on by default; same outputs).
+    pub fn orbit_ctx_block_culls(ctx: *const OrbitCtx) -> u64;
+    pub fn orbit_ctx_set_block_cull(ctx: *mut OrbitCtx, enable: u32) -> i32;
+    pub fn orbit_meshlet_stream_block_bounds(ctx: *mut OrbitCtx, ms: *mut OrbitMeshletStream, first_block: u64, count: u64,
+                                             out: *mut c_void, stream: *mut c_void) -> i32;
     // exchange without a host in the step: IPC-mapped peer buffers + a device-signalled rank-ordered scatter (orbit_exchange_list)
     pub fn orbit_p2p_alloc(ctx: *mut OrbitCtx, bytes: u64, out_ptr: *mut *mut c_void, out_handle: *mut [u8; 64]) -> i32;
     pub fn orbit_p2p_free(ctx: *mut OrbitCtx, ptr: *mut c_void) -> i32;

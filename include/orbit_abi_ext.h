@@ -104,7 +104,7 @@ uint64_t orbit_ctx_fused_culls(const OrbitCtx *ctx);
 /* them (bounding sphere, cone, material index) — 20 and a quarter once the  */
 /* material's alpha_mode is known — and only the ~10 % that survive need the */
 /* rest (vertex_offset, data_offset, counts) for their command.  A stream    */
-/* object keeps derived arrays for a range of the buffer (36.65 B of HBM per */
+/* object keeps derived arrays for a range of the buffer (37.65 B of HBM per */
 /* meshlet on top of the buffer itself):                                     */
 /*   spheres 16 B, cones 4 B, material indices 2 B — what every meshlet's    */
 /*     test reads;                                                           */
@@ -135,7 +135,7 @@ uint64_t orbit_ctx_fused_culls(const OrbitCtx *ctx);
 /*                                                                           */
 /*   create   arrays for global meshlet indices [first_meshlet,              */
 /*            first_meshlet + capacity), capacity <= 2^27 (device memory:    */
-/*            36.65 B x capacity, zero-filled)                               */
+/*            37.65 B x capacity, zero-filled)                               */
 /*   update   re-derives [first, first + count) from `meshlet_buffer` (same  */
 /*            global indexing as bufs->meshlet_buffer), enqueued on `stream`;*/
 /*            call it wherever the renderer writes meshlets (add_mesh) —     */
@@ -210,6 +210,20 @@ uint64_t orbit_ctx_meshlet_stream_culls(const OrbitCtx *ctx);
  * derivation unless it is being captured); after an update that derives classes, once that launch has finished
  * (polled, never waited for: culls enqueued before that read the material indices). */
 uint64_t orbit_ctx_meshlet_class_culls(const OrbitCtx *ctx);
+/* ... of which decided per block of 32 meshlets: every orbit_meshlet_stream_update also derives, for each 32-aligned
+ * block of global meshlet indices it touches, a bound of the block's spheres (centre, radius of the centres, largest
+ * radius; 32 B per block), and orbit_meshlet_cull of occlusion pass 0, perspective projection, canonical arithmetic,
+ * from a stream with alpha classes decides a meshlet from its 4-byte cone word and its block's bound wherever that
+ * verdict is certain, and evaluates it as before where it is not: the outputs are the same, bit for bit.  On by
+ * default; orbit_ctx_set_block_cull(ctx, 0) — or ORBIT_BLOCK_CULL=0 in the environment when the context is created —
+ * keeps the per-meshlet evaluation.  orbit_meshlet_stream_validate also checks every sphere of the buffer against
+ * its block's bound (ORBIT_E_STALE). */
+uint64_t orbit_ctx_block_culls(const OrbitCtx *ctx);
+int32_t orbit_ctx_set_block_cull(OrbitCtx *ctx, uint32_t enable);
+/* Tests: the bounds of blocks [first_block, first_block + count) (block = global meshlet index / 32) into the HOST
+ * array `out`, 32 B each: {float centre[3], centre_radius, max_radius; uint32_t valid, pad[2]}.  Waits for `stream`. */
+int32_t orbit_meshlet_stream_block_bounds(OrbitCtx *ctx, OrbitMeshletStream *ms, uint64_t first_block, uint64_t count,
+                                          void *out, void *stream);
 
 /* One pyramid of a batch.  `depth_row_pitch` = texels per row of the depth buffer (0 = screen_width: tightly
  * packed); exactly one of `pyramid` (packed chain) and `levels` (HOST array of the mip_levels the pyramid has for

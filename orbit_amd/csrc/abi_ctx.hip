@@ -175,10 +175,14 @@ int32_t orbit_ctx_create(int32_t device_id, const OrbitCaps *caps_in, OrbitCtx *
         return hip_fail(nullptr, e, "hipMemset(scratch arena)");
     }
     (void)layout_arena(ctx, (uintptr_t)ctx->arena, md32);
-#ifdef ORBIT_TRIAGE // perf-triage builds (tools/mkvariant_any.sh); the product library reads no environment variable
+#ifdef ORBIT_TRIAGE // perf-triage builds (tools/mkvariant_any.sh); the product library reads no other environment variable
     const char *dbg = getenv("ORBIT_SP_DEBUG");
     ctx->debug_flags = dbg ? (uint32_t)atoi(dbg) : 0u;
 #endif
+    // ORBIT_BLOCK_CULL=0: pass 0 keeps the per-meshlet evaluation (orbit_ctx_set_block_cull) — so that one library can
+    // be timed both ways by a program that knows nothing of the switch
+    const char *bc = getenv("ORBIT_BLOCK_CULL");
+    ctx->block_cull = !(bc && bc[0] == '0' && bc[1] == '\0');
     snprintf(ctx->err, sizeof(ctx->err), "no error");
     // scan scratch of views 1.. of orbit_cull_views, when the caller announced them
     const OrbitCaps child_caps = view_child_caps(caps);

@@ -227,7 +227,8 @@ int32_t profile_pair(OrbitCtx *ctx, hipEvent_t &ev0, hipEvent_t &ev1) {
 int32_t validate_stream(OrbitCtx *ctx, const MeshletCullParams &p, hipStream_t s) {
     if (!p.ms.sphere || !ctx->caps.validate_streams) return ORBIT_OK;
     const hipError_t e = launch_meshlet_stream_validate(p.meshlets, p.ms, p.ms.cls0 ? p.materials : nullptr,
-                                                        ctx->meshlet_stream->material_count, ctx->status, s);
+                                                        ctx->meshlet_stream->material_count, ctx->status, s,
+                                                        stream_block_bounds(ctx->meshlet_stream));
     return e == hipSuccess ? ORBIT_OK : hip_fail(ctx, e, "launch meshlet_stream_validate");
 }
 
@@ -266,9 +267,14 @@ int32_t meshlet_cull_impl(OrbitCtx *ctx, const OrbitGpuCullInfo *ci, const Orbit
     hipError_t e = hipSuccess;
     if (ctx->rec_shift > 5u) e = launch_split_records(split_params_for(ctx, ctx, b), s);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch split_records");
-    e = launch_meshlet_cull(p, ctx->num_cus, s, ev0, ev1);
+    // Pass 0 of a perspective view in canonical arithmetic, from streams with alpha classes, into commands: decided per
+    // block of 32 wherever the block's bound makes the verdict certain (meshlet_eval_blocks.hip) — same outputs
+    const bool blocks = ctx->block_cull && out.kind == MeshletCullOut::kCommands && p.ms.sphere != nullptr &&
+                        p.ms.cls0 != nullptr && ci->occlusion_pass == 0u && ci->projection_type == 0u && p.arith == 0u;
+    e = launch_meshlet_cull(p, ctx->num_cus, s, ev0, ev1, blocks ? stream_block_bounds(ctx->meshlet_stream) : nullptr);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch meshlet_cull");
     count_stream_cull(ctx, p);
+    if (blocks) ctx->block_culls++;
     return ORBIT_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <new>
 #include <vector>
 
+#include "block_pretest.h"
 #include "kernels.h"
 
 using namespace orbit;
@@ -28,6 +29,8 @@ struct OrbitMeshletStream {
     uint16_t *cnt = nullptr;
     uint32_t *link = nullptr, *cls0 = nullptr, *cls1 = nullptr; // word 0 = meshlets (first & ~31) .. +31
     uint2 *base32 = nullptr;                                     // entry 0 = meshlet (first & ~31)
+    BlockBound *blk = nullptr; // entry 0 = meshlets (first & ~31) .. +31: the block's bound (block_pretest.h), re-derived
+                               // by every update for the blocks it touches; zero (not valid) where none was derived
     // A stream may be bound to several contexts, each with its own lock: its own state has its own.  The device-side
     // order of an update against the culls that read it is the caller's, like the order of the meshlet upload itself.
     std::mutex mu;
@@ -104,6 +107,8 @@ struct OrbitCtx {
     OrbitMeshletStream *meshlet_stream = nullptr; // orbit_ctx_bind_meshlet_stream
     uint64_t stream_culls = 0;                          // meshlet culls launched from it
     uint64_t class_culls = 0;                           // ... of which with its alpha classes
+    uint64_t block_culls = 0;                           // ... of which decided per block (meshlet_eval_blocks.hip)
+    bool block_cull = true;                             // orbit_ctx_set_block_cull / ORBIT_BLOCK_CULL=0
     char err[512] = {0};
 };
 
@@ -182,6 +187,9 @@ inline MeshletStreamView stream_view_for(OrbitMeshletStream *ms, const void *mes
     if (!classes) v.cls0 = v.cls1 = nullptr;
     return v;
 }
+
+// The stream's block bounds based at block 0, for a launch whose parameter block reads this stream (p.ms of stream_view_for)
+inline const BlockBound *stream_block_bounds(const OrbitMeshletStream *ms) { return ms->blk - (ms->first >> 5); }
 
 // ------------------------------------------------------------------ culls (abi_cull.hip)
 // One orbit_cull_views call, validated and laid out, not yet enqueued (orbit_frame_late validates all its groups before

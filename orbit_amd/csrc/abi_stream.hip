@@ -65,6 +65,7 @@ int32_t orbit_meshlet_stream_create(OrbitCtx *ctx, uint64_t first_meshlet, uint6
                   {(void **)&ms->cnt, capacity * sizeof(uint16_t) + 256u, 0},
                   {(void **)&ms->link, bit_words * sizeof(uint32_t), 0},
                   {(void **)&ms->base32, bit_words * sizeof(uint2), 0},
+                  {(void **)&ms->blk, bit_words * sizeof(BlockBound), 0}, // not valid until derived
                   {(void **)&ms->cls0, bit_words * sizeof(uint32_t), 0xFF},  // class 3: look the material up
                   {(void **)&ms->cls1, bit_words * sizeof(uint32_t), 0xFF}};
     // Zero-filled: a meshlet inside the derived range that no update has reached (a gap between two uploads) is a
@@ -80,7 +81,7 @@ int32_t orbit_meshlet_stream_create(OrbitCtx *ctx, uint64_t first_meshlet, uint6
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ms->other_event, hipEventDisableTiming);
     if (e != hipSuccess) {
         orbit_meshlet_stream_destroy(ms);
-        return hip_fail(ctx, e, "meshlet_stream_create: hipMalloc (36.65 B per meshlet)");
+        return hip_fail(ctx, e, "meshlet_stream_create: hipMalloc (37.65 B per meshlet)");
     }
     *out_stream = ms;
     return ORBIT_OK;
@@ -109,6 +110,15 @@ int32_t orbit_meshlet_stream_update(OrbitCtx *ctx, OrbitMeshletStream *ms, const
                                                (const OrbitMaterialData *)ms->materials, ms->material_count, ms->d_other,
                                                (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch meshlet_stream_build");
+    // the bounds of every block the update touched, from the sphere array as it now stands (all of each block that
+    // the arrays hold, not only the updated part)
+    if (count != 0) {
+        const MeshletStreamView all = stream_arrays(ms, ms->first, ms->first + ms->capacity);
+        e = launch_block_bounds_build(all.sphere, const_cast<BlockBound *>(stream_block_bounds(ms)), first >> 5,
+                                      ((first + count - 1u) >> 5) - (first >> 5) + 1u, ms->first, ms->first + ms->capacity,
+                                      (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "launch block_bounds_build");
+    }
     if (ms->materials != nullptr && count != 0) { // the range's classes were derived: did a class 3 appear?
         e = read_back_class_flag(ms, (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "meshlet_stream_update: class flag read-back");
@@ -232,8 +242,24 @@ int32_t orbit_meshlet_stream_validate(OrbitCtx *ctx, OrbitMeshletStream *ms, con
     }
     const hipError_t e = launch_meshlet_stream_validate((const OrbitMeshlet *)meshlet_buffer, v,
                                                         classes ? (const OrbitMaterialData *)material_buffer : nullptr,
-                                                        ms->material_count, ctx->status, (hipStream_t)stream);
+                                                        ms->material_count, ctx->status, (hipStream_t)stream,
+                                                        stream_block_bounds(ms));
     if (e != hipSuccess) return hip_fail(ctx, e, "launch meshlet_stream_validate");
+    return ORBIT_OK;
+}
+
+int32_t orbit_meshlet_stream_block_bounds(OrbitCtx *ctx, OrbitMeshletStream *ms, uint64_t first_block, uint64_t count,
+                                          void *out, void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (const int32_t rc = check_stream(ctx, ms, "meshlet_stream_block_bounds", true, out)) return rc;
+    const uint64_t b0 = ms->first >> 5, b1 = (ms->first + ms->capacity + 31u) >> 5;
+    if (first_block < b0 || count > b1 - b0 || first_block - b0 > b1 - b0 - count)
+        return fail(ctx, ORBIT_E_CAPACITY, "meshlet_stream_block_bounds: blocks [%llu, +%llu) outside the stream's [%llu, %llu)",
+                    (unsigned long long)first_block, (unsigned long long)count, (unsigned long long)b0, (unsigned long long)b1);
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpy(out, ms->blk + (first_block - b0), count * sizeof(BlockBound), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(ctx, e, "meshlet_stream_block_bounds: read-back");
     return ORBIT_OK;
 }
 
@@ -249,6 +275,7 @@ int32_t orbit_meshlet_stream_destroy(OrbitMeshletStream *ms) {
     (void)hipFree(ms->cnt);
     (void)hipFree(ms->link);
     (void)hipFree(ms->base32);
+    (void)hipFree(ms->blk);
     (void)hipFree(ms->cls0);
     (void)hipFree(ms->cls1);
     (void)hipFree(ms->d_other);
@@ -273,5 +300,13 @@ uint64_t orbit_ctx_fused_culls(const OrbitCtx *ctx) { return ctx ? ctx->fused_cu
 uint64_t orbit_ctx_meshlet_stream_culls(const OrbitCtx *ctx) { return ctx ? ctx->stream_culls : 0; }
 uint64_t orbit_ctx_meshlet_class_culls(const OrbitCtx *ctx) { return ctx ? ctx->class_culls : 0; }
 uint64_t orbit_ctx_shard_culls(const OrbitCtx *ctx) { return ctx ? ctx->shard_culls : 0; }
+uint64_t orbit_ctx_block_culls(const OrbitCtx *ctx) { return ctx ? ctx->block_culls : 0; }
+
+int32_t orbit_ctx_set_block_cull(OrbitCtx *ctx, uint32_t enable) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->block_cull = enable != 0u;
+    return ORBIT_OK;
+}
 
 } // extern "C"

@@ -10,6 +10,8 @@
 
 namespace orbit {
 
+struct BlockBound; // block_pretest.h
+
 // Meshlet-cull wave tile: 16 dispatch records (= 8 rows of 2 records on the
 // 64 lanes of a wave, one meshlet per lane per row) = 512 meshlets.
 constexpr uint32_t kTileRecords = 16;
@@ -322,8 +324,11 @@ hipError_t launch_cull_fused_views_contracted(const FusedCullViews &all, const u
 hipError_t launch_entity_cull_views(const EntityCullViews &all, uint32_t n, uint32_t max_entity_draw_count,
                                     uint32_t num_cus, hipStream_t s);
 // ev0/ev1 (optional): recorded on `s` immediately before / after the dominant kernel of the op
+// blk (optional): the stream's block bounds, based at block 0 — the evaluation decides per block of 32 where it can
+// (meshlet_eval_blocks.hip).  The caller passes them only for the launch that kernel serves: pass 0, perspective,
+// canonical arithmetic, streams with alpha classes, commands out.
 hipError_t launch_meshlet_cull(const MeshletCullParams &p, uint32_t num_cus, hipStream_t s,
-                               hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+                               hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const BlockBound *blk = nullptr);
 // orbit_cull_views: the meshlet stage of the n views all.v[0..n)
 struct MeshletCullViews {
     MeshletCullParams v[ORBIT_MAX_CULL_VIEWS];
@@ -336,6 +341,9 @@ struct ViewGroup {
 // The launches launch_meshlet_cull / launch_meshlet_cull_views are made of (meshlet_eval.hip, meshlet_emit.hip,
 // meshlet_lists.hip); grids are sized inside.
 hipError_t launch_meshlet_eval(const MeshletCullParams &p, uint32_t num_cus, hipStream_t s);
+// the per-block pass-0 evaluation (meshlet_eval_blocks.hip) in launch_meshlet_eval's place, on its grid for pass 0 from streams
+hipError_t launch_meshlet_eval_blocks(const MeshletCullParams &p, const BlockBound *blk, dim3 grid, hipStream_t s);
+uint32_t meshlet_eval_blocks_grid(uint32_t max_tiles, uint32_t num_cus);
 hipError_t launch_meshlet_eval_views(const MeshletCullViews &all, const ViewGroup &g, uint32_t m, uint32_t pass,
                                      bool ortho, int src, uint32_t max_tiles, uint32_t num_cus, hipStream_t s);
 hipError_t launch_meshlet_emit(const MeshletCullParams &p, bool stream, uint32_t num_cus, hipStream_t s);
@@ -354,9 +362,14 @@ hipError_t launch_meshlet_stream_build(const OrbitMeshlet *meshlets, uint64_t fi
                                        uint32_t material_count, uint32_t *other, hipStream_t s);
 // ORBIT_E_STALE into *status if a meshlet of the stream's range differs from its derived copy (or, with `materials`,
 // an alpha class from its material's alpha_mode): orbit_meshlet_stream_validate
+// ... or (with `blk`, based at block 0) a meshlet's sphere lies outside its block's bound
 hipError_t launch_meshlet_stream_validate(const OrbitMeshlet *meshlets, const MeshletStreamView &ms,
                                           const OrbitMaterialData *materials, uint32_t material_count, int32_t *status,
-                                          hipStream_t s);
+                                          hipStream_t s, const BlockBound *blk = nullptr);
+// The bounds of blocks [block_first, block_first + block_count) (32-aligned blocks of global meshlet indices; `sphere`
+// and `blk` based at index 0) from the stream's own sphere array, over each block's part of [s_first, s_end)
+hipError_t launch_block_bounds_build(const uint4 *sphere, BlockBound *blk, uint64_t block_first, uint64_t block_count,
+                                     uint64_t s_first, uint64_t s_end, hipStream_t s);
 // scene_update.hip: orbit_scene_update_entities (instance_indices == nullptr: the dense form)
 hipError_t launch_scene_update_entities(const OrbitEntityTransform *transforms, const uint32_t *instance_indices,
                                         uint32_t count, OrbitEntityData *entity_data, uint32_t entity_capacity,

@@ -539,6 +539,17 @@ __device__ __forceinline__ void tile_finish_occ(const MeshletCullParams &p, Wave
     }
 }
 
+// The emit launch behind this evaluation scans the tiles' counts itself and publishes each chunk's sum as a non-zero
+// word of chunk_sums (meshlet_emit.hip emit_scan_duty): the first workgroup of every evaluation zeroes them
+// (`threads`: the evaluation's workgroup size).
+__device__ __forceinline__ void clear_chunk_sums(const MeshletCullParams &p, uint32_t threads) {
+    if (blockIdx.x != 0) return;
+    const uint32_t max_tiles = (p.dispatch_capacity + kTileRecords - 1) / kTileRecords;
+    const uint32_t max_chunks = (max_tiles + kScanChunk - 1) / kScanChunk;
+    for (uint32_t c = threadIdx.x; c < max_chunks; c += threads) p.chunk_sums[c] = 0u;
+    if (threadIdx.x < kEmitTicketPools) p.tickets[(kTicketPools + threadIdx.x) * kTicketStride] = 0u; // its group tickets
+}
+
 // Tile setup, split so that each step's loads can be issued well before they are consumed (see the
 // pipelines of the kernels): record load, model-column load, (view x model) product + LDS slab write.
 __device__ __forceinline__ uint4 setup_load_rec(const MeshletCullParams &p, uint32_t tile, bool tile_valid,

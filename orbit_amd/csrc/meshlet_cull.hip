@@ -43,13 +43,22 @@ hipError_t launch_meshlet_scan_emit(const MeshletCullParams &p, uint32_t num_cus
 }
 
 hipError_t launch_meshlet_cull(const MeshletCullParams &p, uint32_t num_cus, hipStream_t s, hipEvent_t ev0,
-                               hipEvent_t ev1) {
+                               hipEvent_t ev1, const BlockBound *blk) {
     const uint32_t max_tiles = (p.dispatch_capacity + kTileRecords - 1) / kTileRecords;
     // nothing is enqueued for a capacity the emit launch cannot address (orbit_ctx_create rejects such caps already)
     if ((max_tiles + kScanChunk - 1) / kScanChunk > kEmitChunkTable) return hipErrorInvalidValue;
     hipError_t e;
     if (ev0 && (e = hipEventRecord(ev0, s)) != hipSuccess) return e;
-    if ((e = launch_meshlet_eval(p, num_cus, s)) != hipSuccess) return e;
+    if (blk != nullptr) {
+        // the per-block evaluation serves exactly one launch; anything else with bounds is a caller's error
+        if (p.ci.occlusion_pass != 0u || p.ci.projection_type != 0u || p.arith != 0u || p.ms.cls0 == nullptr ||
+            p.visible_list != 0u || p.task_records != nullptr)
+            return hipErrorInvalidValue;
+        e = launch_meshlet_eval_blocks(p, blk, dim3(meshlet_eval_blocks_grid(max_tiles, num_cus)), s);
+    } else {
+        e = launch_meshlet_eval(p, num_cus, s);
+    }
+    if (e != hipSuccess) return e;
     if (ev1 && (e = hipEventRecord(ev1, s)) != hipSuccess) return e;
     if (p.task_records) return launch_task_records(p, s);
     if (p.visible_list == 2u) {

@@ -55,16 +55,6 @@ constexpr int kEvWavesPerSimd = 4; // resident waves per SIMD: compiled for (128
 constexpr int ev_waves_per_simd(int pass, bool stream) { return (pass == 0 && stream) ? ORBIT_EV_WPS0 : kEvWavesPerSimd; }
 
 
-// The emit launch behind this evaluation scans the tiles' counts itself and publishes each chunk's sum as a non-zero
-// word of chunk_sums (meshlet_emit.hip emit_scan_duty): the first workgroup of every evaluation zeroes them.
-__device__ __forceinline__ void clear_chunk_sums(const MeshletCullParams &p) {
-    if (blockIdx.x != 0) return;
-    const uint32_t max_tiles = (p.dispatch_capacity + kTileRecords - 1) / kTileRecords;
-    const uint32_t max_chunks = (max_tiles + kScanChunk - 1) / kScanChunk;
-    for (uint32_t c = threadIdx.x; c < max_chunks; c += kEvWaves * 64) p.chunk_sums[c] = 0u;
-    if (threadIdx.x < kEmitTicketPools) p.tickets[(kTicketPools + threadIdx.x) * kTicketStride] = 0u; // its group tickets
-}
-
 // STREAM: meshlets from the derived streams; CLS (with STREAM): predicate bits from the streams' alpha classes
 // LIST: the instantiation can write the record list (visible_list == 2).  Only the several-views kernel has it: it
 // reads its parameter block from the argument segment where it needs it, while the single-view kernels hold theirs
@@ -128,7 +118,7 @@ __device__ __forceinline__ void meshlet_eval_body(const MeshletCullParams &p, co
         rec2 = setup_load_rec(p, wave_g + 2u * stride, wave_g + 2u * stride < cap_tiles, p.dispatch_capacity, lane);
     }
     planes_to_lds(p, planes);
-    clear_chunk_sums(p);
+    clear_chunk_sums(p, kEvWaves * 64);
     if (threadIdx.x < kEvWaves) s_red[threadIdx.x] = 0u;
     if (CLS && threadIdx.x < 6) cls_sel[threadIdx.x] = ((alpha_bits(p.ci, threadIdx.x >> 1) >> (threadIdx.x & 1u)) & 1u) ? ~0u : 0u;
     const AlphaLds *alpha = alpha_table_fill(p, alpha_tab) ? &alpha_tab : nullptr;
@@ -514,7 +504,7 @@ __device__ __forceinline__ void meshlet_pass1_body(const MeshletCullParams &p) {
     __shared__ uint32_t s_red[kEvWaves]; // records_finish
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     planes_to_lds(p, planes);
-    clear_chunk_sums(p);
+    clear_chunk_sums(p, kEvWaves * 64);
     if (threadIdx.x < kEvWaves) s_red[threadIdx.x] = 0u;
     const AlphaLds *alpha = alpha_table_fill(p, alpha_tab) ? &alpha_tab : nullptr;
     __syncthreads();
@@ -644,6 +634,10 @@ void launch_eval_pass(const MeshletCullParams &p, dim3 grid, hipStream_t s) {
 }
 
 } // namespace
+
+#if !ORBIT_CONTRACT
+uint32_t meshlet_eval_blocks_grid(uint32_t max_tiles, uint32_t num_cus) { return eval_grid(0u, true, max_tiles, num_cus); }
+#endif
 
 hipError_t launch_meshlet_eval(const MeshletCullParams &p, uint32_t num_cus, hipStream_t s) {
 #if !ORBIT_CONTRACT

@@ -1,0 +1,308 @@
+// meshlet_eval_blocks.hip — the pass-0 evaluation that decides most meshlets per block of 32 (block_pretest.h): the launch
+// a single-view orbit_meshlet_cull takes for occlusion pass 0, perspective, canonical arithmetic, from derived streams
+// with alpha classes and block bounds.  Everything else keeps meshlet_eval.hip's kernels.
+//
+// Same wave tile, slabs, pipeline and ticket scheme as meshlet_eval_body, same outputs (tile_masks, tile_counts, zeroed
+// chunk sums, status latches).  What differs is a row whose two records are SPARSE (block_record_setup: affine matrix,
+// 32-aligned record inside the stream, valid block bound, block small against its distance from the camera): its lanes
+// load only the 4-byte cone word and run block_pretest_terms — about 25 vector instructions instead of the literal
+// evaluation's 114 and 4 bytes instead of 20.  A lane whose cone verdict is certain and, if kept, whose block is
+// certainly inside every plane is decided there; the others ("candidates") go to a wave-private LDS ring as (row, lane)
+// codes and are evaluated literally, 64 at a time on full lanes, from gathered sphere + cone reads (eval_geometry_mask:
+// the reference's arithmetic, so the result is what the dense row would have given, bit for bit).  Dense rows run
+// rows_eval unchanged.
+#include "block_pretest.h"
+#include "meshlet_common.h"
+
+namespace orbit {
+
+namespace {
+
+constexpr int kBkWaves = 4;
+constexpr int kBkWavesPerSimd = 5; // as the kernel this one stands in for (meshlet_eval.hip ORBIT_EV_WPS0)
+// candidates are flushed in 64s once 64 are queued — checked after rows 1 and 3, where few registers are live — and at
+// the end of the tile, behind the next slab's setup: at most 63 + 4 x 64 are ever queued
+constexpr uint32_t kBkRing = 512, kBkFlush = 64;
+
+struct __attribute__((aligned(16))) BlockTileLds {
+    BlockRecord r[kTileRecords];
+};
+struct CandRing {
+    uint16_t code[kBkRing]; // row * 64 + lane
+};
+struct RingState {
+    uint32_t head = 0, count = 0; // wave-uniform
+    uint32_t total = 0;           // survivors of the tile so far
+};
+
+// bit 2 r of the slab's spare word: both records of row r are sparse (blk_setup)
+__device__ __forceinline__ bool row_is_sparse(const WaveTileLds &L, int r) {
+    const uint32_t w = reinterpret_cast<const uint32_t *>(&L.pad_)[0];
+    return (((uint32_t)__builtin_amdgcn_readfirstlane((int)w) >> (2 * r)) & 1u) != 0u;
+}
+
+// The block bound of record `lane` of a tile (lanes 0..15; `rec` is held by lanes 4 record .. 4 record + 3), and whether
+// the record starts a block and lies inside the stream.  Unconditional loads: everybody else reads the zero page.
+struct BoundRegs {
+    float4 q; // centre, BlockBound::packed (0, not valid, also where the record is not covered: the zero page)
+};
+__device__ __forceinline__ BoundRegs blk_load_bound(const MeshletCullParams &p, const BlockBound *blk, const uint4 &rec, int lane) {
+    const int src_lane = (lane & 15) * 4;
+    const uint32_t y = (uint32_t)__shfl((int)rec.y, src_lane, 64), z = (uint32_t)__shfl((int)rec.z, src_lane, 64);
+    const uint32_t rel = y - p.ms.first;
+    BoundRegs b;
+    const bool covered = lane < (int)kTileRecords && z != 0u && (y & 31u) == 0u && rel < p.ms.count && z <= p.ms.count - rel;
+    const float4 *src = covered ? reinterpret_cast<const float4 *>(blk + (y >> 5)) : reinterpret_cast<const float4 *>(p.zero_page);
+    b.q = src[0];
+    return b;
+}
+
+// Behind setup_write of the same slab (which ends in a wave barrier): lane r < 16 derives record r's BlockRecord.
+__device__ __forceinline__ void blk_setup(const MeshletCullParams &p, WaveTileLds &L, BlockTileLds &B, const PlaneLds &P,
+                                          const BoundRegs &bb, int lane) {
+    uint32_t flags = 0u;
+    if (lane < (int)kTileRecords) {
+        const RecordLds &R = L.r[lane];
+        float m[16];
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const float4 col = R.mcol[c];
+            m[4 * c] = col.x, m[4 * c + 1] = col.y, m[4 * c + 2] = col.z, m[4 * c + 3] = col.w;
+        }
+        const BlockBound b = block_bound_unpack(bb.q.x, bb.q.y, bb.q.z, __float_as_uint(bb.q.w));
+        const uint32_t aw = reinterpret_cast<const uint32_t *>(&L.affine_rows)[lane >> 3];
+        const bool affine = ((aw >> (8 * ((lane >> 1) & 3))) & 1u) != 0u;
+        // (covered: a record that is not reads the zero page, whose bound is not valid)
+        BlockRecord o = block_record_setup(m, affine, R.scale, b, true, reinterpret_cast<const float *>(P.plane),
+                                           min(p.ci.cull_plane_count, (uint32_t)ORBIT_MAX_CULL_PLANES));
+        if (R.rec.z == 0u) o.flags = kBlkSparse; // no record: no lane of it is ever allowed, it holds no row back
+        B.r[lane] = o;
+        flags = o.flags;
+    }
+    uint64_t m = __ballot((flags & kBlkSparse) != 0u);
+    m &= m >> 1; // bit 2 r: both records of row r
+    if (lane == 0) L.pad_ = m & 0x5555ull;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// rows_load<0, R, 1, true, true> with the sphere read only for a dense row (`sparse` is wave-uniform; the load is
+// issued either way, outside the resource for a sparse row, so the wait counts stay exact)
+template <int R>
+__device__ __forceinline__ void blk_row_load(const MeshletCullParams &p, const WaveTileLds &L, bool sparse, int lane,
+                                             RowRegs<1> &t, const StreamRsrc &SR) {
+    const uint32_t half = lane >> 5, ml = lane & 31;
+    const uint4 rec = L.r[2 * R + half].rec;
+    const bool active = ml < rec.z;
+    const uint32_t rel = rec.y + ml - SR.first;
+    const bool in = active & (rel < SR.count);
+    if (active & !in) latch_status(p.status, ORBIT_E_RANGE);
+    const uint32_t i = in ? rel : kNoOffset >> 4;
+    const uint32_t is = sparse ? kNoOffset >> 4 : i;
+    const auto sp = __builtin_amdgcn_raw_buffer_load_b128(SR.sphere, is << 4, 0, ORBIT_EVAL_LOAD_AUX);
+    const uint32_t c = __builtin_amdgcn_raw_buffer_load_b32(SR.cone, i << 2, 0, ORBIT_EVAL_LOAD_AUX);
+    t.a[0] = make_uint4(sp[0], sp[1], sp[2], sp[3]);
+    t.b[0] = make_uint4(c, 0u, 0u, 0u);
+    t.prev[0] = 0u;
+}
+
+// A sparse row: the pre-test decides, the open lanes queue up.
+template <int R>
+__device__ __forceinline__ void blk_row_eval(WaveTileLds &L, const BlockTileLds &B, CandRing &ring, int lane,
+                                             const RowRegs<1> &t, RingState &rs) {
+    const uint32_t half = lane >> 5;
+    const BlockRecord br = B.r[2 * R + half];
+    float s0, band;
+    block_pretest_terms(br, t.b[0].x, s0, band);
+    const uint64_t culled = ballot(block_cone_culls(br, s0, band));
+    const uint64_t kept = ballot(block_cone_keeps(s0, band)) & ballot((br.flags & kBlkInside) != 0u);
+    // lanes that hold a meshlet whose material passes (:207), as in rows_eval
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.r[2 * R].amask.x);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.r[2 * R + 1].amask.x);
+    const uint64_t allow = (uint64_t)hi << 32 | lo;
+    const uint64_t draw = allow & kept & ~culled;
+    const uint64_t cand = allow & ~culled & ~kept;
+    if (lane == 0) L.draw_mask[R] = draw;
+    rs.total += (uint32_t)__popcll(draw);
+    if (lane_of(cand)) ring.code[(rs.head + rs.count + lane_prefix(cand)) & (kBkRing - 1u)] = (uint16_t)(R * 64 + lane);
+    rs.count += (uint32_t)__popcll(cand);
+}
+
+// The literal evaluation of the first n <= 64 queued candidates; lane j takes candidate j.
+__device__ __forceinline__ void blk_flush(const MeshletCullParams &p, WaveTileLds &L, const PlaneLds &P, const CandRing &ring,
+                                          const StreamRsrc &SR, int lane, RingState &rs, uint32_t n) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const bool valid = (uint32_t)lane < n;
+    const uint32_t code = valid ? (uint32_t)ring.code[(rs.head + (uint32_t)lane) & (kBkRing - 1u)] : 0u;
+    const uint32_t rid = (code >> 5) & 15u, ml = code & 31u;
+    const uint4 rec = L.r[rid].rec;
+    const uint32_t rel = rec.y + ml - SR.first;
+    const uint32_t i = (valid && ml < rec.z && rel < SR.count) ? rel : kNoOffset >> 4; // (a sparse record lies inside)
+    const auto sp = __builtin_amdgcn_raw_buffer_load_b128(SR.sphere, i << 4, 0, 0);
+    const uint32_t c = __builtin_amdgcn_raw_buffer_load_b32(SR.cone, i << 2, 0, 0);
+    Sphere s;
+    // every candidate's record is affine (block_record_setup); a lane without one holds zeros
+    const uint64_t geo = eval_geometry_mask<0>(p, L, P, rid, make_uint4(sp[0], sp[1], sp[2], sp[3]), make_uint4(c, 0u, 0u, 0u), s, true);
+    const uint64_t vis = geo & ballot(valid);
+    if (lane_of(vis)) atomicOr(reinterpret_cast<uint32_t *>(L.draw_mask) + rid, 1u << ml);
+    rs.total += (uint32_t)__popcll(vis);
+    rs.head = (rs.head + n) & (kBkRing - 1u);
+    rs.count -= n;
+}
+
+__global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_blocks_kernel(const MeshletCullParams p,
+                                                                                            const BlockBound *blk) {
+    __shared__ WaveTileLds lds[kBkWaves][3];
+    __shared__ BlockTileLds blds[kBkWaves][2]; // of tile i in [i & 1]: written when tile i - 2 is through its rows
+    __shared__ PlaneLds planes;
+    __shared__ CandRing rings[kBkWaves];
+    __shared__ uint32_t cls_sel[8]; // [2 c + k] = all ones if alpha class c has predicate bit k (alpha_bits)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // the ramp, the tile assignment (static share + tickets) and the priorities: meshlet_eval_body, which explains them
+    const uint32_t nrec_raw = *reinterpret_cast<const uint32_t *>(p.dispatch_buffer);
+    const uint32_t stride = gridDim.x * kBkWaves, wave_g = blockIdx.x * kBkWaves + wave;
+    const uint32_t cap_tiles = (p.dispatch_capacity + kTileRecords - 1) / kTileRecords;
+    uint4 r0 = setup_load_rec(p, wave_g, wave_g < cap_tiles, p.dispatch_capacity, lane);
+    uint4 r1 = setup_load_rec(p, wave_g + stride, wave_g + stride < cap_tiles, p.dispatch_capacity, lane);
+    uint4 rec2 = setup_load_rec(p, wave_g + 2u * stride, wave_g + 2u * stride < cap_tiles, p.dispatch_capacity, lane);
+    planes_to_lds(p, planes);
+    clear_chunk_sums(p, kBkWaves * 64);
+    if (threadIdx.x < 6) cls_sel[threadIdx.x] = ((alpha_bits(p.ci, threadIdx.x >> 1) >> (threadIdx.x & 1u)) & 1u) ? ~0u : 0u;
+    __syncthreads();
+    const uint32_t nrec = min(nrec_raw, p.dispatch_capacity);
+    const uint32_t ntiles = (nrec + kTileRecords - 1) / kTileRecords;
+    const uint32_t full_rounds = ntiles / stride;
+    const uint32_t dyn_rounds = min(max(full_rounds / 4u, 1u), 3u);
+    const uint32_t n_static = ntiles <= stride ? 0xFFFFFFFFu : max(full_rounds >= dyn_rounds ? full_rounds - dyn_rounds : 0u, 3u);
+    const uint32_t npools = min((uint32_t)kTicketPools, stride);
+    const uint32_t pool = wave_g % npools;
+    uint32_t *ticket_ctr = p.tickets + pool * kTicketStride;
+    uint32_t claims = 0;
+    auto claim = [&]() -> uint32_t {
+        uint32_t raw = claims;
+        if (claims >= n_static) {
+            raw = 0;
+            if (lane == 0) raw = atomicAdd(ticket_ctr, 1u);
+        }
+        claims++;
+        return raw;
+    };
+    auto ticket_tile = [&](uint32_t raw, uint32_t k) -> uint32_t {
+        const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)raw);
+        if (k < n_static) return t * stride + wave_g;
+        return t >= 0x08000000u ? 0xFFFFFFFFu : n_static * stride + t * npools + pool;
+    };
+    StreamRsrc SR = {};
+    SR.first = p.ms.first;
+    SR.count = p.ms.count;
+    SR.sphere = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(p.ms.sphere + p.ms.first), 0, p.ms.count * 16u, kBufFlags);
+    SR.cone = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(p.ms.cone + p.ms.first), 0, p.ms.count * 4u, kBufFlags);
+    uint32_t w0, w1, w2, tk_raw;
+    {
+        const uint32_t t0 = claim(), t1 = claim(), t2 = claim();
+        tk_raw = claim();
+        w0 = ticket_tile(t0, 0u);
+        w1 = ticket_tile(t1, 1u);
+        w2 = ticket_tile(t2, 2u);
+    }
+    RowRegs<1> qa, qb;
+    {
+        const uint4 none = make_uint4(0u, 0u, 0u, 0u);
+        const uint32_t rl = (uint32_t)lane >> 2;
+        if (!(w0 < ntiles && w0 * kTileRecords + rl < nrec)) r0 = none;
+        if (!(w1 < ntiles && w1 * kTileRecords + rl < nrec)) r1 = none;
+        if (!(w2 < ntiles && w2 * kTileRecords + rl < nrec)) rec2 = none;
+        if ((lane & 3) == 0) lds[wave][0].r[lane >> 2].rec = r0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const float4 m0 = setup_load_mat(p, r0, lane);
+        const float4 m1 = setup_load_mat(p, r1, lane);
+        const uint32_t c0 = setup_load_cls(p, r0, lane), c1 = setup_load_cls(p, r1, lane);
+        const BoundRegs b0 = blk_load_bound(p, blk, r0, lane), b1 = blk_load_bound(p, blk, r1, lane);
+        // tile 0's first rows go out before its slab says which rows are sparse: as dense rows, which is always right
+        // (a sparse row never looks at the sphere it was given)
+        blk_row_load<0>(p, lds[wave][0], false, lane, qa, SR);
+        blk_row_load<1>(p, lds[wave][0], false, lane, qb, SR);
+        setup_write_cls(lds[wave][0], cls_sel, r0, c0, lane);
+        setup_write_cls(lds[wave][1], cls_sel, r1, c1, lane);
+        setup_write(p, lds[wave][0], r0, m0, lane);
+        blk_setup(p, lds[wave][0], blds[wave][0], planes, b0, lane);
+        setup_write(p, lds[wave][1], r1, m1, lane);
+        blk_setup(p, lds[wave][1], blds[wave][1], planes, b1, lane);
+    }
+    uint32_t it = 0;
+    const uint32_t prio_rank = blockIdx.x / max(gridDim.x / (uint32_t)kBkWavesPerSimd, 1u);
+    while (w0 < ntiles) {
+        switch ((it + prio_rank) & 3u) {
+        case 0: __builtin_amdgcn_s_setprio(0); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        default: __builtin_amdgcn_s_setprio(3); break;
+        }
+        const uint32_t w3 = ticket_tile(tk_raw, claims - 1u);
+        tk_raw = claim();
+        WaveTileLds &L = lds[wave][it % 3];
+        WaveTileLds &Ln = lds[wave][(it + 1) % 3];
+        const BlockTileLds &B = blds[wave][it & 1u];
+        CandRing &ring = rings[wave];
+        RingState rs;
+#define BK_ROW(R, Q)                                                                                                   \
+    if (row_is_sparse(L, R)) blk_row_eval<R>(L, B, ring, lane, Q, rs);                                                 \
+    else rs.total = rows_eval<0, 0, R, 1, true>(p, L, planes, nullptr, lane, Q, rs.total, nullptr);
+#define BK_FLUSH() \
+    while (rs.count >= kBkFlush) blk_flush(p, L, planes, ring, SR, lane, rs, kBkFlush);
+        BK_ROW(0, qa)
+        blk_row_load<2>(p, L, row_is_sparse(L, 2), lane, qa, SR);
+        BK_ROW(1, qb)
+        blk_row_load<3>(p, L, row_is_sparse(L, 3), lane, qb, SR);
+        BK_FLUSH()
+        BK_ROW(2, qa)
+        blk_row_load<4>(p, L, row_is_sparse(L, 4), lane, qa, SR);
+        BK_ROW(3, qb)
+        blk_row_load<5>(p, L, row_is_sparse(L, 5), lane, qb, SR);
+        BK_FLUSH()
+        const float4 mat2 = setup_load_mat(p, rec2, lane);
+        const uint32_t cls2 = setup_load_cls(p, rec2, lane);
+        const BoundRegs bnd2 = blk_load_bound(p, blk, rec2, lane);
+        const uint4 rec3 = setup_load_rec(p, w3, w3 < ntiles, nrec, lane);
+        BK_ROW(4, qa)
+        blk_row_load<6>(p, L, row_is_sparse(L, 6), lane, qa, SR);
+        BK_ROW(5, qb)
+        blk_row_load<7>(p, L, row_is_sparse(L, 7), lane, qb, SR);
+        BK_ROW(6, qa)
+        blk_row_load<0>(p, Ln, row_is_sparse(Ln, 0), lane, qa, SR);
+        BK_ROW(7, qb)
+        blk_row_load<1>(p, Ln, row_is_sparse(Ln, 1), lane, qb, SR);
+#undef BK_ROW
+#undef BK_FLUSH
+        setup_write_cls(lds[wave][(it + 2) % 3], cls_sel, rec2, cls2, lane);
+        setup_write(p, lds[wave][(it + 2) % 3], rec2, mat2, lane);
+        blk_setup(p, lds[wave][(it + 2) % 3], blds[wave][it & 1u], planes, bnd2, lane); // (this tile's rows are through)
+        while (rs.count > 0u) blk_flush(p, L, planes, ring, SR, lane, rs, min(rs.count, kBkFlush));
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // the mask writes of this tile
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (lane < 2 * (int)kTileRows)
+            p.tile_masks[(size_t)w0 * (2 * kTileRows) + lane] = reinterpret_cast<const uint32_t *>(L.draw_mask)[lane];
+        if (lane == 0) p.tile_counts[w0] = rs.total;
+        w0 = w1;
+        w1 = w2;
+        w2 = w3;
+        rec2 = rec3;
+        it++;
+    }
+}
+
+} // namespace
+
+// `grid`: meshlet_eval.hip's for this pass and source (launch_meshlet_eval sizes it)
+hipError_t launch_meshlet_eval_blocks(const MeshletCullParams &p, const BlockBound *blk, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL(meshlet_eval_blocks_kernel, grid, dim3(kBkWaves * 64), 0, s, p, blk);
+    return hipGetLastError();
+}
+
+} // namespace orbit

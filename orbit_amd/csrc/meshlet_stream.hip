@@ -1,6 +1,7 @@
 // meshlet_stream.hip — the derived meshlet streams (orbit_meshlet_stream_*; kernels.h MeshletStreamView): the static
 // 32-B Meshlet records (shaders/include/types.glsl:143-152 of the reference repo) re-laid out once, at upload, into
 // what every evaluation reads and what only a survivor's command needs; their alpha classes; the validation launch.
+#include "block_pretest.h"
 #include "kernels.h"
 
 namespace orbit {
@@ -148,7 +149,7 @@ hipError_t launch_meshlet_stream_build(const OrbitMeshlet *meshlets, uint64_t fi
 // orbit_meshlet_stream_validate: thread = meshlet of the stream's range; the Meshlet as the arrays hold it against the
 // Meshlet in the buffer, the alpha class against the material's alpha_mode.
 __global__ __launch_bounds__(256) void meshlet_stream_validate_kernel(const OrbitMeshlet *meshlets, const StreamBuildArrays A,
-                                                                      int32_t *status) {
+                                                                      int32_t *status, const BlockBound *blk) {
     for (uint64_t m = A.s_first + (uint64_t)blockIdx.x * 256u + threadIdx.x; m < A.s_end; m += (uint64_t)gridDim.x * 256u) {
         const uint4 *src = reinterpret_cast<const uint4 *>(meshlets + m);
         const uint4 a = src[0], b = src[1], sa = A.sphere[m];
@@ -168,18 +169,71 @@ __global__ __launch_bounds__(256) void meshlet_stream_validate_kernel(const Orbi
             const bool link = b.y == pb.y && b.z == pb.z + meshlet_data_words((pb.w >> 16) & 0xFFu, pb.w >> 24);
             same = same && link == (((A.link[m >> 5] >> (m & 31u)) & 1u) != 0u);
         }
+        if (blk != nullptr) { // the buffer's sphere against its block's bound, distances recomputed (in double)
+            const BlockBound B = blk[m >> 5];
+            if (B.valid != 0u) {
+                const double dx = (double)__uint_as_float(a.x) - B.cx, dy = (double)__uint_as_float(a.y) - B.cy;
+                const double dz = (double)__uint_as_float(a.z) - B.cz, r = (double)__uint_as_float(a.w);
+                const bool inside = dx * dx + dy * dy + dz * dz <= (double)B.rc * B.rc && r <= (double)B.r_max && r >= 0.0;
+                same = same && inside; // (false for a NaN)
+            }
+        }
         if (!same) latch_status(status, ORBIT_E_STALE);
     }
 }
 
+// orbit_meshlet_stream_update, behind the build launch: thread = meshlet, half a wave = one block of 32.  A block's bound
+// covers every meshlet of it that the stream's arrays hold ([s_first, s_end): never-derived ones are the zero spheres a
+// cull would read), so an update that begins or ends inside a block leaves that block's bound right.
+__global__ __launch_bounds__(256) void block_bounds_kernel(const uint4 *sphere, BlockBound *blk, uint64_t block_first,
+                                                           uint64_t block_count, uint64_t s_first, uint64_t s_end) {
+    const uint32_t ml = threadIdx.x & 31u, half = (threadIdx.x >> 5) & 1u;
+    const float inf = __builtin_inff();
+    auto reduce = [](float v, bool want_max) {
+#pragma unroll
+        for (int d = 16; d >= 1; d >>= 1) {
+            const float o = __shfl_xor(v, d, 32);
+            v = want_max ? fmaxf(v, o) : fminf(v, o);
+        }
+        return v;
+    };
+    const uint64_t rounds = (block_count + (uint64_t)gridDim.x * 8u - 1u) / ((uint64_t)gridDim.x * 8u);
+    for (uint64_t it = 0; it < rounds; it++) { // (whole waves stay in the loop: the ballot and the shuffles below)
+        const uint64_t k = (it * gridDim.x + blockIdx.x) * 8u + (threadIdx.x >> 5);
+        const uint64_t m = (block_first + k) * 32u + ml;
+        const bool in = k < block_count && m >= s_first && m < s_end;
+        uint4 w = make_uint4(0u, 0u, 0u, 0u);
+        if (in) w = sphere[m];
+        const float x = __uint_as_float(w.x), y = __uint_as_float(w.y), z = __uint_as_float(w.z), r = __uint_as_float(w.w);
+        const bool bad = in && !(__builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z) && __builtin_isfinite(r));
+        const bool finite = (uint32_t)(__ballot(bad) >> (32u * half)) == 0u;
+        const float x0 = reduce(in ? x : inf, false), x1 = reduce(in ? x : -inf, true);
+        const float y0 = reduce(in ? y : inf, false), y1 = reduce(in ? y : -inf, true);
+        const float z0 = reduce(in ? z : inf, false), z1 = reduce(in ? z : -inf, true);
+        const float cx = 0.5f * x0 + 0.5f * x1, cy = 0.5f * y0 + 0.5f * y1, cz = 0.5f * z0 + 0.5f * z1;
+        const float dist = reduce(in ? block_dist(cx, cy, cz, x, y, z) : 0.0f, true);
+        const float r_max = reduce(in ? r : 0.0f, true), r_min = reduce(in ? r : 0.0f, false);
+        if (ml == 0u && k < block_count) blk[block_first + k] = block_bound_finish(cx, cy, cz, dist, r_max, r_min, finite);
+    }
+}
+
+hipError_t launch_block_bounds_build(const uint4 *sphere, BlockBound *blk, uint64_t block_first, uint64_t block_count,
+                                     uint64_t s_first, uint64_t s_end, hipStream_t s) {
+    if (block_count == 0) return hipSuccess;
+    const uint64_t need = (block_count + 7u) / 8u;
+    hipLaunchKernelGGL(block_bounds_kernel, dim3((uint32_t)(need < 8192u ? need : 8192u)), dim3(256), 0, s, sphere, blk,
+                       block_first, block_count, s_first, s_end);
+    return hipGetLastError();
+}
+
 hipError_t launch_meshlet_stream_validate(const OrbitMeshlet *meshlets, const MeshletStreamView &ms,
                                           const OrbitMaterialData *materials, uint32_t material_count, int32_t *status,
-                                          hipStream_t s) {
+                                          hipStream_t s, const BlockBound *blk) {
     if (ms.count == 0) return hipSuccess;
     const uint64_t need = ((uint64_t)ms.count + 255u) / 256u;
     const uint32_t blocks = (uint32_t)(need < 8192u ? need : 8192u);
     hipLaunchKernelGGL(meshlet_stream_validate_kernel, dim3(blocks), dim3(256), 0, s, meshlets,
-                       stream_build_arrays(ms, materials, material_count), status);
+                       stream_build_arrays(ms, materials, material_count), status, blk);
     return hipGetLastError();
 }
 

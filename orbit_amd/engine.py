@@ -683,6 +683,14 @@ class Engine:
         """orbit_ctx_meshlet_class_culls: ... of which evaluated from the stream's alpha classes."""
         return int(self._lib.orbit_ctx_meshlet_class_culls(self._ctx))
 
+    def block_culls(self):
+        """orbit_ctx_block_culls: ... of which decided per block of 32 meshlets (pass 0; include/orbit_abi_ext.h)."""
+        return int(self._lib.orbit_ctx_block_culls(self._ctx))
+
+    def set_block_cull(self, enable):
+        """orbit_ctx_set_block_cull: False keeps the per-meshlet evaluation for pass 0 (same outputs either way)."""
+        _lib.check(self._lib.orbit_ctx_set_block_cull(self._ctx, 1 if enable else 0), self._ctx)
+
     def exchange_list(self, local_list, rank, world, out_buffers, ctrl_buffers, out_capacity, header_bytes, stride,
                       stream=None):
         """orbit_exchange_list: the rank-ordered all-gather of the ranks' lists with counts and completion signalled on

@@ -11,6 +11,7 @@
 #include "orbit_gltf.hpp"
 #include "orbit_raster.hpp"
 #include "orbit_scene.hpp"
+#include "../csrc/block_pretest.h"
 
 using namespace orbit;
 using namespace orbit::passes;
@@ -665,6 +666,25 @@ void orbit_host_transform_from_mat4(const float matrix[16], float position[3], f
     orientation[0] = t.orientation.x, orientation[1] = t.orientation.y, orientation[2] = t.orientation.z;
     orientation[3] = t.orientation.w;
     scale[0] = t.scale.x, scale[1] = t.scale.y, scale[2] = t.scale.z;
+}
+
+void orbit_host_block_bounds(const float *spheres, uint64_t count, void *out) {
+    orbit::BlockBound *o = static_cast<orbit::BlockBound *>(out);
+    for (uint64_t b = 0; b * 32u < count; b++) o[b] = orbit::block_bound_of(spheres + 128u * b, (uint32_t)std::min<uint64_t>(32u, count - 32u * b));
+}
+
+uint32_t orbit_host_block_pretest(const float m[16], int32_t affine, float scale, const void *bound, const float *planes,
+                                  uint32_t n_planes, float ratio, const uint32_t *cones, uint64_t count, uint8_t *verdicts) {
+    orbit::BlockBound in;
+    memcpy(&in, bound, sizeof(in));
+    const orbit::BlockBound b = orbit::block_bound_unpack(in.cx, in.cy, in.cz, in.packed);
+    const orbit::BlockRecord r = orbit::block_record_setup(m, affine != 0, scale, b, true, planes, n_planes, ratio < 0.0f ? ORBIT_BLK_RATIO : ratio);
+    for (uint64_t i = 0; i < count; i++) {
+        uint32_t v = (r.flags & orbit::kBlkSparse) ? orbit::block_pretest(r, cones[i]) : 0u;
+        if (v == 2u && (r.flags & orbit::kBlkInside)) v |= 4u;
+        verdicts[i] = (uint8_t)v;
+    }
+    return r.flags;
 }
 
 } // extern "C"

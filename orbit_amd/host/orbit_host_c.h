@@ -271,6 +271,20 @@ uint64_t orbit_host_simplify_clustered(const float *positions, uint64_t vertex_c
                                        uint64_t capacity, uint64_t *needed);
 /* Transform::from_mat4 (scene.rs:41-48) of a column-major matrix -> position[3], orientation[4] (x, y, z, w), scale[3] */
 void orbit_host_transform_from_mat4(const float matrix[16], float position[3], float orientation[4], float scale[3]);
+/* The per-block pre-test of the pass-0 evaluation (orbit_amd/csrc/block_pretest.h: the same functions the device runs),
+ * for tests of its certification on the host.
+ * orbit_host_block_bounds: the bounds of the ceil(count / 32) blocks of `count` spheres {x, y, z, radius} (block b =
+ * spheres [32 b, 32 b + 32)), as orbit_meshlet_stream_update derives them; out: 32 B per block
+ * (include/orbit_abi_ext.h orbit_meshlet_stream_block_bounds).
+ * orbit_host_block_pretest: one dispatch record — view x model `m` (column-major), `affine` and `scale` as the wave tile's
+ * slab holds them, its block's 32-B bound (read the way the evaluation reads it), n_planes cull planes {nx, ny, nz, w} —
+ * against `count` cone words.  verdicts[i]: 0 = the record is dense or the meshlet's verdict open (the literal evaluation
+ * decides), 1 = certainly culled by the cone, 2 = certainly kept by the cone, 2 | 4 = ... and certainly inside every plane.
+ * ratio: the record is sparse only if its block is further than ratio x its view-space radius (< 0: the evaluation's).
+ * Returns the record's flags (1: sparse, 2: inside). */
+void orbit_host_block_bounds(const float *spheres, uint64_t count, void *out);
+uint32_t orbit_host_block_pretest(const float m[16], int32_t affine, float scale, const void *bound, const float *planes,
+                                  uint32_t n_planes, float ratio, const uint32_t *cones, uint64_t count, uint8_t *verdicts);
 #ifdef __cplusplus
 }
 #endif

@@ -54,8 +54,11 @@ def main():
         out["kernels"][name] = {"read_bytes": rd, "write_bytes": wr, "hbm_bytes": rd + wr,
                                 "raw_fetch_kib": fetch[k], "raw_write_kib": write.get(k, 0.0),
                                 "launches": launches[k], "kernel_name": k[:120]}
-    dom = out["kernels"].get("meshlet_eval_kernel")
-    out["dominant_kernel"] = "meshlet_eval_kernel"
+    # the default line's pass 0 runs the per-block evaluation; a run with ORBIT_BLOCK_CULL=0 or from the Meshlet buffer does not
+    blocks, plain = out["kernels"].get("meshlet_eval_blocks_kernel"), out["kernels"].get("meshlet_eval_kernel")
+    name = "meshlet_eval_blocks_kernel" if blocks and (not plain or blocks["launches"] > plain["launches"]) else "meshlet_eval_kernel"
+    dom = out["kernels"].get(name)
+    out["dominant_kernel"] = name
     out["hbm_bytes_per_launch"] = dom["hbm_bytes"] if dom else None
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with open(os.path.join(root, "gpurun_out", "traffic.json" if source == "buffer" else "traffic_stream.json"), "w") as f:
