@@ -289,6 +289,7 @@ extern "C" {
     /// Pass-0 culls decided per block of 32 meshlets from the stream's block bounds (on by default; same outputs).
     pub fn orbit_ctx_block_culls(ctx: *const OrbitCtx) -> u64;
     pub fn orbit_ctx_set_block_cull(ctx: *mut OrbitCtx, enable: u32) -> i32;
+    pub fn orbit_ctx_set_block_cull_grid(ctx: *mut OrbitCtx, max_workgroups: u32) -> i32;
     pub fn orbit_meshlet_stream_block_bounds(ctx: *mut OrbitCtx, ms: *mut OrbitMeshletStream, first_block: u64, count: u64,
                                              out: *mut c_void, stream: *mut c_void) -> i32;
     // exchange without a host in the step: IPC-mapped peer buffers + a device-signalled rank-ordered scatter (orbit_exchange_list)

@@ -271,7 +271,8 @@ int32_t meshlet_cull_impl(OrbitCtx *ctx, const OrbitGpuCullInfo *ci, const Orbit
     // block of 32 wherever the block's bound makes the verdict certain (meshlet_eval_blocks.hip) — same outputs
     const bool blocks = ctx->block_cull && out.kind == MeshletCullOut::kCommands && p.ms.sphere != nullptr &&
                         p.ms.cls0 != nullptr && ci->occlusion_pass == 0u && ci->projection_type == 0u && p.arith == 0u;
-    e = launch_meshlet_cull(p, ctx->num_cus, s, ev0, ev1, blocks ? stream_block_bounds(ctx->meshlet_stream) : nullptr);
+    e = launch_meshlet_cull(p, ctx->num_cus, s, ev0, ev1, blocks ? stream_block_bounds(ctx->meshlet_stream) : nullptr,
+                            ctx->block_cull_grid);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch meshlet_cull");
     count_stream_cull(ctx, p);
     if (blocks) ctx->block_culls++;

@@ -327,8 +327,10 @@ hipError_t launch_entity_cull_views(const EntityCullViews &all, uint32_t n, uint
 // blk (optional): the stream's block bounds, based at block 0 — the evaluation decides per block of 32 where it can
 // (meshlet_eval_blocks.hip).  The caller passes them only for the launch that kernel serves: pass 0, perspective,
 // canonical arithmetic, streams with alpha classes, commands out.
+// blk_grid_cap: that kernel's grid is at most this many workgroups (0 = as sized; orbit_ctx_set_block_cull_grid)
 hipError_t launch_meshlet_cull(const MeshletCullParams &p, uint32_t num_cus, hipStream_t s,
-                               hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const BlockBound *blk = nullptr);
+                               hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const BlockBound *blk = nullptr,
+                               uint32_t blk_grid_cap = 0);
 // orbit_cull_views: the meshlet stage of the n views all.v[0..n)
 struct MeshletCullViews {
     MeshletCullParams v[ORBIT_MAX_CULL_VIEWS];

@@ -43,7 +43,7 @@ hipError_t launch_meshlet_scan_emit(const MeshletCullParams &p, uint32_t num_cus
 }
 
 hipError_t launch_meshlet_cull(const MeshletCullParams &p, uint32_t num_cus, hipStream_t s, hipEvent_t ev0,
-                               hipEvent_t ev1, const BlockBound *blk) {
+                               hipEvent_t ev1, const BlockBound *blk, uint32_t blk_grid_cap) {
     const uint32_t max_tiles = (p.dispatch_capacity + kTileRecords - 1) / kTileRecords;
     // nothing is enqueued for a capacity the emit launch cannot address (orbit_ctx_create rejects such caps already)
     if ((max_tiles + kScanChunk - 1) / kScanChunk > kEmitChunkTable) return hipErrorInvalidValue;
@@ -54,7 +54,11 @@ hipError_t launch_meshlet_cull(const MeshletCullParams &p, uint32_t num_cus, hip
         if (p.ci.occlusion_pass != 0u || p.ci.projection_type != 0u || p.arith != 0u || p.ms.cls0 == nullptr ||
             p.visible_list != 0u || p.task_records != nullptr)
             return hipErrorInvalidValue;
-        e = launch_meshlet_eval_blocks(p, blk, dim3(meshlet_eval_blocks_grid(max_tiles, num_cus)), s);
+        // (the results do not depend on the grid, only the assignment of tiles to waves does: a test caps it to reach
+        // the tile-to-tile hand-overs with a few hundred records)
+        uint32_t grid = meshlet_eval_blocks_grid(max_tiles, num_cus);
+        if (blk_grid_cap != 0u) grid = min(grid, blk_grid_cap);
+        e = launch_meshlet_eval_blocks(p, blk, dim3(grid), s);
     } else {
         e = launch_meshlet_eval(p, num_cus, s);
     }

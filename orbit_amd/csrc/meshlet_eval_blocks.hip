@@ -11,6 +11,10 @@
 // codes and are evaluated literally, 64 at a time on full lanes, from gathered sphere + cone reads (eval_geometry_mask:
 // the reference's arithmetic, so the result is what the dense row would have given, bit for bit).  Dense rows run
 // rows_eval unchanged.
+//
+// A tile whose eight rows are all sparse has its eight cone words loaded together, a whole tile ahead (issued before the
+// tile in front of it runs its rows) and with no sphere load at all; a tile with a dense row keeps the row-by-row
+// pipeline, two rows in flight.  Either kind issues the next tile's first loads in the form that tile needs (PipeRegs).
 #include "block_pretest.h"
 #include "meshlet_common.h"
 
@@ -87,11 +91,26 @@ __device__ __forceinline__ void blk_setup(const MeshletCullParams &p, WaveTileLd
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// rows_load<0, R, 1, true, true> with the sphere read only for a dense row (`sparse` is wave-uniform; the load is
-// issued either way, outside the resource for a sparse row, so the wait counts stay exact)
+// The registers the pipeline carries from tile to tile, in one of two forms (wave-uniform, `whole` in the kernel):
+// rows: v[0..3] the sphere and v[4] the cone word of row 0 of the tile, v[5..9] the same of row 1 (rows 2.. follow row by
+//       row, two in flight, as in meshlet_eval_body);
+// whole: v[r] the cone word of row r of an ALL-SPARSE tile — a cone word is one register where a dense row is five, so
+//       the eight rows of such a tile fit where two dense rows would, and all eight loads are in flight at once.
+struct PipeRegs {
+    uint32_t v[10];
+};
+
+// every row of the tile is sparse (blk_setup; a tile past the wave's last holds no record and is one, too)
+__device__ __forceinline__ bool tile_is_sparse(const WaveTileLds &L) {
+    const uint32_t w = reinterpret_cast<const uint32_t *>(&L.pad_)[0];
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)w) == 0x5555u;
+}
+
+// rows_load<0, R, 1, true, true> into v[0..4], with the sphere read only for a dense row (`sparse` is wave-uniform; the
+// load is issued either way, outside the resource for a sparse row, so the wait counts stay exact)
 template <int R>
 __device__ __forceinline__ void blk_row_load(const MeshletCullParams &p, const WaveTileLds &L, bool sparse, int lane,
-                                             RowRegs<1> &t, const StreamRsrc &SR) {
+                                             uint32_t *v, const StreamRsrc &SR) {
     const uint32_t half = lane >> 5, ml = lane & 31;
     const uint4 rec = L.r[2 * R + half].rec;
     const bool active = ml < rec.z;
@@ -101,20 +120,48 @@ __device__ __forceinline__ void blk_row_load(const MeshletCullParams &p, const W
     const uint32_t i = in ? rel : kNoOffset >> 4;
     const uint32_t is = sparse ? kNoOffset >> 4 : i;
     const auto sp = __builtin_amdgcn_raw_buffer_load_b128(SR.sphere, is << 4, 0, ORBIT_EVAL_LOAD_AUX);
-    const uint32_t c = __builtin_amdgcn_raw_buffer_load_b32(SR.cone, i << 2, 0, ORBIT_EVAL_LOAD_AUX);
-    t.a[0] = make_uint4(sp[0], sp[1], sp[2], sp[3]);
-    t.b[0] = make_uint4(c, 0u, 0u, 0u);
-    t.prev[0] = 0u;
+    v[4] = __builtin_amdgcn_raw_buffer_load_b32(SR.cone, i << 2, 0, ORBIT_EVAL_LOAD_AUX);
+    v[0] = sp[0], v[1] = sp[1], v[2] = sp[2], v[3] = sp[3];
 }
 
-// A sparse row: the pre-test decides, the open lanes queue up.
+// The eight cone words of an all-sparse tile into v[0..7]: eight loads back to back, no sphere load at all.  Range-checked
+// lane by lane as blk_row_load does it (the status is latched once, behind the loads: first error wins either way).
+__device__ __forceinline__ void blk_tile_load(const MeshletCullParams &p, const WaveTileLds &L, int lane, uint32_t *v,
+                                              const StreamRsrc &SR) {
+    const uint32_t half = lane >> 5, ml = lane & 31;
+    bool bad = false;
+#pragma unroll
+    for (int r = 0; r < (int)kTileRows; r++) {
+        const uint4 rec = L.r[2 * r + half].rec;
+        const bool active = ml < rec.z;
+        const uint32_t rel = rec.y + ml - SR.first;
+        const bool in = active & (rel < SR.count);
+        bad |= active & !in;
+        const uint32_t i = in ? rel : kNoOffset >> 4;
+        v[r] = __builtin_amdgcn_raw_buffer_load_b32(SR.cone, i << 2, 0, ORBIT_EVAL_LOAD_AUX);
+    }
+    if (bad) latch_status(p.status, ORBIT_E_RANGE);
+}
+
+// A dense row from v[0..4]: rows_eval unchanged.
+template <int R>
+__device__ __forceinline__ uint32_t blk_row_dense(const MeshletCullParams &p, WaveTileLds &L, const PlaneLds &P, int lane,
+                                                  const uint32_t *v, uint32_t total) {
+    RowRegs<1> t;
+    t.a[0] = make_uint4(v[0], v[1], v[2], v[3]);
+    t.b[0] = make_uint4(v[4], 0u, 0u, 0u);
+    t.prev[0] = 0u;
+    return rows_eval<0, 0, R, 1, true>(p, L, P, nullptr, lane, t, total, nullptr);
+}
+
+// A sparse row from its cone words: the pre-test decides, the open lanes queue up.
 template <int R>
 __device__ __forceinline__ void blk_row_eval(WaveTileLds &L, const BlockTileLds &B, CandRing &ring, int lane,
-                                             const RowRegs<1> &t, RingState &rs) {
+                                             uint32_t cone, RingState &rs) {
     const uint32_t half = lane >> 5;
     const BlockRecord br = B.r[2 * R + half];
     float s0, band;
-    block_pretest_terms(br, t.b[0].x, s0, band);
+    block_pretest_terms(br, cone, s0, band);
     const uint64_t culled = ballot(block_cone_culls(br, s0, band));
     const uint64_t kept = ballot(block_cone_keeps(s0, band)) & ballot((br.flags & kBlkInside) != 0u);
     // lanes that hold a meshlet whose material passes (:207), as in rows_eval
@@ -160,10 +207,11 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
     __shared__ PlaneLds planes;
     __shared__ CandRing rings[kBkWaves];
     __shared__ uint32_t cls_sel[8]; // [2 c + k] = all ones if alpha class c has predicate bit k (alpha_bits)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // the ramp, the tile assignment (static share + tickets) and the priorities: meshlet_eval_body, which explains them
     const uint32_t nrec_raw = *reinterpret_cast<const uint32_t *>(p.dispatch_buffer);
-    const uint32_t stride = gridDim.x * kBkWaves, wave_g = blockIdx.x * kBkWaves + wave;
+    // (wave-uniform, and told so: the ticket pool and its counter's address then live in scalar registers)
+    const uint32_t stride = gridDim.x * kBkWaves, wave_g = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kBkWaves + wave));
     const uint32_t cap_tiles = (p.dispatch_capacity + kTileRecords - 1) / kTileRecords;
     uint4 r0 = setup_load_rec(p, wave_g, wave_g < cap_tiles, p.dispatch_capacity, lane);
     uint4 r1 = setup_load_rec(p, wave_g + stride, wave_g + stride < cap_tiles, p.dispatch_capacity, lane);
@@ -208,7 +256,9 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
         w1 = ticket_tile(t1, 1u);
         w2 = ticket_tile(t2, 2u);
     }
-    RowRegs<1> qa, qb;
+    PipeRegs q;  // tile w0's first loads, in the form `whole` names
+    bool whole;  // wave-uniform
+    uint32_t *const qa = q.v, *const qb = q.v + 5;
     {
         const uint4 none = make_uint4(0u, 0u, 0u, 0u);
         const uint32_t rl = (uint32_t)lane >> 2;
@@ -223,14 +273,20 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
         const float4 m1 = setup_load_mat(p, r1, lane);
         const uint32_t c0 = setup_load_cls(p, r0, lane), c1 = setup_load_cls(p, r1, lane);
         const BoundRegs b0 = blk_load_bound(p, blk, r0, lane), b1 = blk_load_bound(p, blk, r1, lane);
-        // tile 0's first rows go out before its slab says which rows are sparse: as dense rows, which is always right
-        // (a sparse row never looks at the sphere it was given)
-        blk_row_load<0>(p, lds[wave][0], false, lane, qa, SR);
-        blk_row_load<1>(p, lds[wave][0], false, lane, qb, SR);
         setup_write_cls(lds[wave][0], cls_sel, r0, c0, lane);
         setup_write_cls(lds[wave][1], cls_sel, r1, c1, lane);
         setup_write(p, lds[wave][0], r0, m0, lane);
         blk_setup(p, lds[wave][0], blds[wave][0], planes, b0, lane);
+        // tile 0's first loads go out once its slab says which of its rows are sparse, behind the second slab's loads
+        // and ahead of its setup: no sphere is read for a row that never looks at it
+        whole = tile_is_sparse(lds[wave][0]);
+        if (whole) {
+            blk_tile_load(p, lds[wave][0], lane, q.v, SR);
+            q.v[8] = q.v[9] = 0u;
+        } else {
+            blk_row_load<0>(p, lds[wave][0], row_is_sparse(lds[wave][0], 0), lane, qa, SR);
+            blk_row_load<1>(p, lds[wave][0], row_is_sparse(lds[wave][0], 1), lane, qb, SR);
+        }
         setup_write(p, lds[wave][1], r1, m1, lane);
         blk_setup(p, lds[wave][1], blds[wave][1], planes, b1, lane);
     }
@@ -250,35 +306,78 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
         const BlockTileLds &B = blds[wave][it & 1u];
         CandRing &ring = rings[wave];
         RingState rs;
-#define BK_ROW(R, Q)                                                                                                   \
-    if (row_is_sparse(L, R)) blk_row_eval<R>(L, B, ring, lane, Q, rs);                                                 \
-    else rs.total = rows_eval<0, 0, R, 1, true>(p, L, planes, nullptr, lane, Q, rs.total, nullptr);
+        // the next tile's slab is complete (blk_setup runs two tiles ahead): its loads go out in the form it needs
+        const bool nxt_whole = tile_is_sparse(Ln);
+        float4 mat2;
+        uint32_t cls2;
+        BoundRegs bnd2;
+        uint4 rec3;
 #define BK_FLUSH() \
     while (rs.count >= kBkFlush) blk_flush(p, L, planes, ring, SR, lane, rs, kBkFlush);
-        BK_ROW(0, qa)
-        blk_row_load<2>(p, L, row_is_sparse(L, 2), lane, qa, SR);
-        BK_ROW(1, qb)
-        blk_row_load<3>(p, L, row_is_sparse(L, 3), lane, qb, SR);
-        BK_FLUSH()
-        BK_ROW(2, qa)
-        blk_row_load<4>(p, L, row_is_sparse(L, 4), lane, qa, SR);
-        BK_ROW(3, qb)
-        blk_row_load<5>(p, L, row_is_sparse(L, 5), lane, qb, SR);
-        BK_FLUSH()
-        const float4 mat2 = setup_load_mat(p, rec2, lane);
-        const uint32_t cls2 = setup_load_cls(p, rec2, lane);
-        const BoundRegs bnd2 = blk_load_bound(p, blk, rec2, lane);
-        const uint4 rec3 = setup_load_rec(p, w3, w3 < ntiles, nrec, lane);
-        BK_ROW(4, qa)
-        blk_row_load<6>(p, L, row_is_sparse(L, 6), lane, qa, SR);
-        BK_ROW(5, qb)
-        blk_row_load<7>(p, L, row_is_sparse(L, 7), lane, qb, SR);
-        BK_ROW(6, qa)
-        blk_row_load<0>(p, Ln, row_is_sparse(Ln, 0), lane, qa, SR);
-        BK_ROW(7, qb)
-        blk_row_load<1>(p, Ln, row_is_sparse(Ln, 1), lane, qb, SR);
+        if (whole) {
+            // An all-sparse tile: its eight cone words are in q.  Everything the wave will wait for next goes out
+            // first — the next tile's loads and the setup loads of the tile after it — then the eight rows run from
+            // registers with no load between them.
+            PipeRegs tn;
+            if (nxt_whole) {
+                blk_tile_load(p, Ln, lane, tn.v, SR);
+                tn.v[8] = tn.v[9] = 0u;
+            } else {
+                blk_row_load<0>(p, Ln, row_is_sparse(Ln, 0), lane, tn.v, SR);
+                blk_row_load<1>(p, Ln, row_is_sparse(Ln, 1), lane, tn.v + 5, SR);
+            }
+            mat2 = setup_load_mat(p, rec2, lane);
+            cls2 = setup_load_cls(p, rec2, lane);
+            bnd2 = blk_load_bound(p, blk, rec2, lane);
+            rec3 = setup_load_rec(p, w3, w3 < ntiles, nrec, lane);
+            blk_row_eval<0>(L, B, ring, lane, q.v[0], rs);
+            blk_row_eval<1>(L, B, ring, lane, q.v[1], rs);
+            BK_FLUSH()
+            blk_row_eval<2>(L, B, ring, lane, q.v[2], rs);
+            blk_row_eval<3>(L, B, ring, lane, q.v[3], rs);
+            BK_FLUSH()
+            blk_row_eval<4>(L, B, ring, lane, q.v[4], rs);
+            blk_row_eval<5>(L, B, ring, lane, q.v[5], rs);
+            blk_row_eval<6>(L, B, ring, lane, q.v[6], rs);
+            blk_row_eval<7>(L, B, ring, lane, q.v[7], rs);
+            q = tn;
+        } else {
+            // A tile with a dense row: row by row, two in flight, as before.  The next tile's loads go out where the
+            // row registers fall free: rows 0 and 1 behind rows 6 and 7, a whole tile of cone words behind row 7.
+#define BK_ROW(R, Q)                                                                                                   \
+    if (row_is_sparse(L, R)) blk_row_eval<R>(L, B, ring, lane, (Q)[4], rs);                                            \
+    else rs.total = blk_row_dense<R>(p, L, planes, lane, Q, rs.total);
+            BK_ROW(0, qa)
+            blk_row_load<2>(p, L, row_is_sparse(L, 2), lane, qa, SR);
+            BK_ROW(1, qb)
+            blk_row_load<3>(p, L, row_is_sparse(L, 3), lane, qb, SR);
+            BK_FLUSH()
+            BK_ROW(2, qa)
+            blk_row_load<4>(p, L, row_is_sparse(L, 4), lane, qa, SR);
+            BK_ROW(3, qb)
+            blk_row_load<5>(p, L, row_is_sparse(L, 5), lane, qb, SR);
+            BK_FLUSH()
+            mat2 = setup_load_mat(p, rec2, lane);
+            cls2 = setup_load_cls(p, rec2, lane);
+            bnd2 = blk_load_bound(p, blk, rec2, lane);
+            rec3 = setup_load_rec(p, w3, w3 < ntiles, nrec, lane);
+            BK_ROW(4, qa)
+            blk_row_load<6>(p, L, row_is_sparse(L, 6), lane, qa, SR);
+            BK_ROW(5, qb)
+            blk_row_load<7>(p, L, row_is_sparse(L, 7), lane, qb, SR);
+            BK_ROW(6, qa)
+            if (!nxt_whole) blk_row_load<0>(p, Ln, row_is_sparse(Ln, 0), lane, qa, SR);
+            BK_ROW(7, qb)
+            if (nxt_whole) {
+                blk_tile_load(p, Ln, lane, q.v, SR);
+                q.v[8] = q.v[9] = 0u;
+            } else {
+                blk_row_load<1>(p, Ln, row_is_sparse(Ln, 1), lane, qb, SR);
+            }
 #undef BK_ROW
+        }
 #undef BK_FLUSH
+        whole = nxt_whole;
         setup_write_cls(lds[wave][(it + 2) % 3], cls_sel, rec2, cls2, lane);
         setup_write(p, lds[wave][(it + 2) % 3], rec2, mat2, lane);
         blk_setup(p, lds[wave][(it + 2) % 3], blds[wave][it & 1u], planes, bnd2, lane); // (this tile's rows are through)

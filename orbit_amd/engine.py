@@ -691,6 +691,10 @@ class Engine:
         """orbit_ctx_set_block_cull: False keeps the per-meshlet evaluation for pass 0 (same outputs either way)."""
         _lib.check(self._lib.orbit_ctx_set_block_cull(self._ctx, 1 if enable else 0), self._ctx)
 
+    def set_block_cull_grid(self, max_workgroups):
+        """orbit_ctx_set_block_cull_grid: at most that many workgroups for the per-block evaluation (0 = as sized; tests)."""
+        _lib.check(self._lib.orbit_ctx_set_block_cull_grid(self._ctx, int(max_workgroups)), self._ctx)
+
     def exchange_list(self, local_list, rank, world, out_buffers, ctrl_buffers, out_capacity, header_bytes, stride,
                       stream=None):
         """orbit_exchange_list: the rank-ordered all-gather of the ranks' lists with counts and completion signalled on
