@@ -12,6 +12,12 @@ use std::ffi::{c_char, c_void};
 pub struct OrbitCtx { _private: [u8; 0] }
 #[repr(C)]
 pub struct OrbitMeshletStream { _private: [u8; 0] }
+/// orbit_meshlet_stream_read_arrays' HOST arrays (tests): every one must be given
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitMeshletStreamArrays {
+    pub sphere: *mut c_void, pub cone: *mut c_void, pub mat: *mut c_void, pub cmd: *mut c_void, pub cnt: *mut c_void,
+    pub link: *mut c_void, pub cls0: *mut c_void, pub cls1: *mut c_void, pub base32: *mut c_void,
+}
 
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct OrbitCaps {
@@ -292,6 +298,9 @@ extern "C" {
     pub fn orbit_ctx_set_block_cull_grid(ctx: *mut OrbitCtx, max_workgroups: u32) -> i32;
     pub fn orbit_meshlet_stream_block_bounds(ctx: *mut OrbitCtx, ms: *mut OrbitMeshletStream, first_block: u64, count: u64,
                                              out: *mut c_void, stream: *mut c_void) -> i32;
+    /// Tests: the stream's derived arrays of meshlets [first, first + count) into host arrays.
+    pub fn orbit_meshlet_stream_read_arrays(ctx: *mut OrbitCtx, ms: *mut OrbitMeshletStream, first: u64, count: u64,
+                                            out: *const OrbitMeshletStreamArrays, stream: *mut c_void) -> i32;
     // exchange without a host in the step: IPC-mapped peer buffers + a device-signalled rank-ordered scatter (orbit_exchange_list)
     pub fn orbit_p2p_alloc(ctx: *mut OrbitCtx, bytes: u64, out_ptr: *mut *mut c_void, out_handle: *mut [u8; 64]) -> i32;
     pub fn orbit_p2p_free(ctx: *mut OrbitCtx, ptr: *mut c_void) -> i32;

@@ -228,6 +228,17 @@ int32_t orbit_ctx_set_block_cull_grid(OrbitCtx *ctx, uint32_t max_workgroups);
  * array `out`, 32 B each: {float centre[3], centre_radius, max_radius; uint32_t valid, pad[2]}.  Waits for `stream`. */
 int32_t orbit_meshlet_stream_block_bounds(OrbitCtx *ctx, OrbitMeshletStream *ms, uint64_t first_block, uint64_t count,
                                           void *out, void *stream);
+/* Tests: the derived arrays of meshlets [first, first + count) (inside the stream's range, else ORBIT_E_CAPACITY) into
+ * HOST arrays, every one of which must be given: per meshlet `sphere` 16 B, `cone` 4 B, `mat` 2 B, `cmd` 12 B and `cnt`
+ * 2 B; and the words of `link`, `cls0`, `cls1` (4 B) and the entries of `base32` (8 B) that hold those meshlets — words
+ * first / 32 .. (first + count - 1) / 32 of global meshlet indices, as the bounds above are addressed.  Bits of such a
+ * word that belong to meshlets outside the stream's range mean nothing.  Waits for `stream`; launches nothing. */
+typedef struct OrbitMeshletStreamArrays {
+    void *sphere, *cone, *mat, *cmd, *cnt, *link, *cls0, *cls1, *base32;
+} OrbitMeshletStreamArrays;
+ORBIT_STATIC_ASSERT(sizeof(OrbitMeshletStreamArrays) == 72, "stream arrays block is nine pointers");
+int32_t orbit_meshlet_stream_read_arrays(OrbitCtx *ctx, OrbitMeshletStream *ms, uint64_t first, uint64_t count,
+                                         const OrbitMeshletStreamArrays *out, void *stream);
 
 /* One pyramid of a batch.  `depth_row_pitch` = texels per row of the depth buffer (0 = screen_width: tightly
  * packed); exactly one of `pyramid` (packed chain) and `levels` (HOST array of the mip_levels the pyramid has for

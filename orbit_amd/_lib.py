@@ -72,6 +72,10 @@ class DepthPyramidDesc(C.Structure):
                 ("mip_width", C.c_uint32 * MAX_PYRAMID_MIPS), ("mip_height", C.c_uint32 * MAX_PYRAMID_MIPS)]
 
 
+class MeshletStreamArrays(C.Structure):  # OrbitMeshletStreamArrays: host arrays of orbit_meshlet_stream_read_arrays
+    _fields_ = [(name, C.c_void_p) for name in ("sphere", "cone", "mat", "cmd", "cnt", "link", "cls0", "cls1", "base32")]
+
+
 class SceneUpdate(C.Structure):  # OrbitSceneUpdate
     _fields_ = [("entities", C.c_void_p), ("transforms", C.c_void_p), ("entity_data", C.c_void_p),
                 ("entity_draw_buffer", C.c_void_p), ("light_data", C.c_void_p), ("shadow_orientations", C.c_void_p),
@@ -192,6 +196,8 @@ SYMBOLS = {
     "orbit_ctx_set_block_cull_grid": (C.c_int32, [C.c_void_p, C.c_uint32]),
     "orbit_meshlet_stream_block_bounds": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                                       C.c_void_p]),
+    "orbit_meshlet_stream_read_arrays": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                                     C.POINTER(MeshletStreamArrays), C.c_void_p]),
     "orbit_cull_shard": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(EntityCullBufs), C.c_uint32, C.c_uint32,
                                      C.POINTER(MeshletCullBufs), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "orbit_ctx_shard_culls": (C.c_uint64, [C.c_void_p]),

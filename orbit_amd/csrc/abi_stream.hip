@@ -108,7 +108,7 @@ int32_t orbit_meshlet_stream_update(OrbitCtx *ctx, OrbitMeshletStream *ms, const
     if ((uint64_t)v.first + v.count < first + count) v.count = (uint32_t)(first + count - v.first);
     hipError_t e = launch_meshlet_stream_build((const OrbitMeshlet *)meshlet_buffer, first, count, v,
                                                (const OrbitMaterialData *)ms->materials, ms->material_count, ms->d_other,
-                                               (hipStream_t)stream);
+                                               ms->first, ms->first + ms->capacity, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch meshlet_stream_build");
     // the bounds of every block the update touched, from the sphere array as it now stands (all of each block that
     // the arrays hold, not only the updated part)
@@ -260,6 +260,41 @@ int32_t orbit_meshlet_stream_block_bounds(OrbitCtx *ctx, OrbitMeshletStream *ms,
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     if (e == hipSuccess) e = hipMemcpy(out, ms->blk + (first_block - b0), count * sizeof(BlockBound), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(ctx, e, "meshlet_stream_block_bounds: read-back");
+    return ORBIT_OK;
+}
+
+int32_t orbit_meshlet_stream_read_arrays(OrbitCtx *ctx, OrbitMeshletStream *ms, uint64_t first, uint64_t count,
+                                         const OrbitMeshletStreamArrays *out, void *stream) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (const int32_t rc = check_stream(ctx, ms, "meshlet_stream_read_arrays", true, out)) return rc;
+    if (!out->sphere || !out->cone || !out->mat || !out->cmd || !out->cnt || !out->link || !out->cls0 || !out->cls1 ||
+        !out->base32)
+        return fail(ctx, ORBIT_E_MISSING, "meshlet_stream_read_arrays: NULL array");
+    if (first < ms->first || count > ms->capacity || first - ms->first > ms->capacity - count)
+        return fail(ctx, ORBIT_E_CAPACITY, "meshlet_stream_read_arrays: [%llu, +%llu) outside the stream's [%llu, +%llu)",
+                    (unsigned long long)first, (unsigned long long)count, (unsigned long long)ms->first,
+                    (unsigned long long)ms->capacity);
+    // the words that hold [first, first + count), as the allocation counts them: word 0 = meshlets (ms->first & ~31) .. +31
+    const size_t at = (size_t)(first - ms->first), w0 = (size_t)((first >> 5) - (ms->first >> 5));
+    const size_t words = count != 0 ? (size_t)(((first + count - 1u) >> 5) - (first >> 5)) + 1u : 0u;
+    const struct {
+        void *dst;
+        const void *src;
+        size_t bytes;
+    } copies[] = {{out->sphere, ms->sphere + at, count * sizeof(uint4)},
+                  {out->cone, ms->cone + at, count * sizeof(uint32_t)},
+                  {out->mat, ms->mat + at, count * sizeof(uint16_t)},
+                  {out->cmd, ms->cmd + 3u * at, count * 12u},
+                  {out->cnt, ms->cnt + at, count * sizeof(uint16_t)},
+                  {out->link, ms->link + w0, words * sizeof(uint32_t)},
+                  {out->cls0, ms->cls0 + w0, words * sizeof(uint32_t)},
+                  {out->cls1, ms->cls1 + w0, words * sizeof(uint32_t)},
+                  {out->base32, ms->base32 + w0, words * sizeof(uint2)}};
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    for (const auto &c : copies)
+        if (e == hipSuccess && c.bytes != 0) e = hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(ctx, e, "meshlet_stream_read_arrays: read-back");
     return ORBIT_OK;
 }
 

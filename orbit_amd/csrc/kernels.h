@@ -358,10 +358,12 @@ uint32_t max_dispatch_capacity();
 // meshlets[first, first + count) -> the three streams (a plain re-layout, one pass)
 // `ms`: the stream's arrays (writable through the const view) and its range; link bits are re-derived for
 // [first, first + count] — the meshlet after the range chains from the range's last one.  `materials` (optional):
-// the buffer the range's alpha classes are derived from (none: class 3, "look the material up").
+// the buffer the range's alpha classes are derived from (none: class 3, "look the material up").  [c_first, c_end):
+// the meshlets the arrays hold; the class bits of those outside [first, first + count) keep their value.
 hipError_t launch_meshlet_stream_build(const OrbitMeshlet *meshlets, uint64_t first, uint64_t count,
                                        const MeshletStreamView &ms, const OrbitMaterialData *materials,
-                                       uint32_t material_count, uint32_t *other, hipStream_t s);
+                                       uint32_t material_count, uint32_t *other, uint64_t c_first, uint64_t c_end,
+                                       hipStream_t s);
 // ORBIT_E_STALE into *status if a meshlet of the stream's range differs from its derived copy (or, with `materials`,
 // an alpha class from its material's alpha_mode): orbit_meshlet_stream_validate
 // ... or (with `blk`, based at block 0) a meshlet's sphere lies outside its block's bound

@@ -453,12 +453,15 @@ __device__ __forceinline__ void meshlet_emit_chain_body(const MeshletCullParams 
     B.first_word = p.ms.first >> 5;
     // + 2 bytes: the 4-B load of a lane whose first meshlet is the stream's last one (the arrays are padded)
     B.cnt = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(p.ms.cnt + p.ms.first), 0, p.ms.count * 2u + 2u, kBufFlags);
+    // words that hold the stream's meshlets, from its last meshlet's word (first + count + 31 would wrap in 32 bits for
+    // a stream that ends within 31 meshlets of 2^32; count == 0: the stream is not read at all, chain_has)
+    const uint32_t stream_words = p.ms.count != 0u ? ((p.ms.first + (p.ms.count - 1u)) >> 5) - B.first_word + 1u : 0u;
     B.link = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(p.ms.link + B.first_word), 0,
-                                               (((p.ms.first + p.ms.count + 31u) >> 5) - B.first_word + 2u) * 4u, kBufFlags);
+                                               (stream_words + 2u) * 4u, kBufFlags);
     B.cmd = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(p.ms.cmd + (size_t)p.ms.first * 3u), 0,
                                               p.ms.count * 12u, kBufFlags);
     B.base32 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint2 *>(p.ms.base32 + B.first_word), 0,
-                                                 (((p.ms.first + p.ms.count + 31u) >> 5) - B.first_word) * 8u, kBufFlags);
+                                                 stream_words * 8u, kBufFlags);
     uint32_t *out = reinterpret_cast<uint32_t *>(p.draw_buffer + ORBIT_DRAW_HEADER);
     const uint32_t stride = gridDim.x * 4;
     const uint32_t sub = (uint32_t)lane >> 4, i16 = (uint32_t)lane & 15u;

@@ -22,7 +22,8 @@ struct StreamBuildArrays {
     uint16_t *cnt;
     uint32_t *link, *cls0, *cls1;
     uint2 *base32;
-    uint64_t s_first, s_end; // the stream's range
+    uint64_t s_first, s_end; // the stream's range: what was derived from the current source (the capacity for the launches
+                             // that work on all of it)
     const OrbitMaterialData *materials; // alpha classes come from here (nullptr: class 3 everywhere)
     uint32_t material_count;
     uint32_t *other; // set to 1 when a meshlet of class 3 is derived while `materials` is set (abi.hip: such a stream
@@ -37,8 +38,10 @@ __device__ __forceinline__ uint32_t alpha_class(const StreamBuildArrays &A, uint
     return mode < 3u ? mode : 3u;
 }
 
+// [c_first, c_end): the stream's capacity — the meshlets the arrays hold, whatever they were derived from.
 __global__ __launch_bounds__(256) void meshlet_stream_build_kernel(const OrbitMeshlet *meshlets, uint64_t first,
-                                                                   uint64_t count, const StreamBuildArrays A) {
+                                                                   uint64_t count, uint64_t c_first, uint64_t c_end,
+                                                                   const StreamBuildArrays A) {
     const int lane = threadIdx.x & 63;
     const uint64_t lo = first & ~63ull, end = first + count;
     for (uint64_t base = lo + ((uint64_t)blockIdx.x * 256u + (threadIdx.x & ~63u)); base <= end;
@@ -79,9 +82,11 @@ __global__ __launch_bounds__(256) void meshlet_stream_build_kernel(const OrbitMe
                 bit = vtx == pv && data == pd + meshlet_data_words((p7 >> 16) & 0xFFu, p7 >> 24);
             }
         }
-        // the class planes: meshlets outside the updated range keep their bits
+        // the class planes: meshlets outside the updated range keep their bits — every meshlet the arrays hold, not
+        // only those derived from this source: set_materials derived them all, and a later update that reaches one of
+        // their neighbours must leave them as they are
         bool p0 = (cls & 1u) != 0u, p1 = (cls & 2u) != 0u;
-        if (!in && in_stream) {
+        if (!in && m >= c_first && m < c_end) {
             p0 = ((A.cls0[m >> 5] >> (m & 31u)) & 1u) != 0;
             p1 = ((A.cls1[m >> 5] >> (m & 31u)) & 1u) != 0;
         }
@@ -137,11 +142,12 @@ static StreamBuildArrays stream_build_arrays(const MeshletStreamView &ms, const 
 
 hipError_t launch_meshlet_stream_build(const OrbitMeshlet *meshlets, uint64_t first, uint64_t count,
                                        const MeshletStreamView &ms, const OrbitMaterialData *materials,
-                                       uint32_t material_count, uint32_t *other, hipStream_t s) {
+                                       uint32_t material_count, uint32_t *other, uint64_t c_first, uint64_t c_end,
+                                       hipStream_t s) {
     if (count == 0) return hipSuccess;
     const uint64_t need = (count + 64u + 255u) / 256u + 1u;
     const uint32_t blocks = (uint32_t)(need < 8192u ? need : 8192u);
-    hipLaunchKernelGGL(meshlet_stream_build_kernel, dim3(blocks), dim3(256), 0, s, meshlets, first, count,
+    hipLaunchKernelGGL(meshlet_stream_build_kernel, dim3(blocks), dim3(256), 0, s, meshlets, first, count, c_first, c_end,
                        stream_build_arrays(ms, materials, material_count, other));
     return hipGetLastError();
 }

@@ -88,15 +88,17 @@ def cluster_stats_dict(stats):
 
 
 class MeshletStream:
-    """Handle of an OrbitMeshletStream (include/orbit_abi.h, "Derived meshlet streams")."""
+    """Handle of an OrbitMeshletStream (include/orbit_abi.h, "Derived meshlet streams"): created over [first, first +
+    count) and updated from `meshlet_buffer` over all of it (initial_update=False: created only, nothing readable yet)."""
 
-    def __init__(self, engine, meshlet_buffer, first, count, stream=None):
+    def __init__(self, engine, meshlet_buffer, first, count, stream=None, initial_update=True):
         self._engine, self._lib = engine, engine._lib
         self._h = C.c_void_p()
         self.first, self.capacity = int(first), int(count)
         _lib.check(self._lib.orbit_meshlet_stream_create(engine._ctx, self.first, self.capacity, C.byref(self._h)),
                    engine._ctx)
-        self.update(meshlet_buffer, first, count, stream)
+        if initial_update:
+            self.update(meshlet_buffer, first, count, stream)
 
     def update(self, meshlet_buffer, first=None, count=None, stream=None):
         first = self.first if first is None else int(first)
@@ -121,6 +123,22 @@ class MeshletStream:
         """orbit_meshlet_stream_validate: ORBIT_E_STALE is latched (Engine.status raises) if the stream differs."""
         _lib.check(self._lib.orbit_meshlet_stream_validate(self._engine._ctx, self._h, _ptr(meshlet_buffer),
                                                            _ptr(material_buffer), _stream(stream)), self._engine._ctx)
+
+    def read_arrays(self, first=None, count=None, stream=None):
+        """orbit_meshlet_stream_read_arrays (tests): the derived arrays of meshlets [first, first + count) — by default
+        the whole stream — as a dict of numpy arrays: sphere u32[n, 4], cone u32[n], mat u16[n], cmd u32[n, 3], cnt
+        u16[n], and link / cls0 / cls1 u32[words], base32 u32[words, 2] for words first // 32 .. (first + count - 1) // 32
+        of global meshlet indices."""
+        first = self.first if first is None else int(first)
+        count = self.capacity if count is None else int(count)
+        words = ((first + count - 1) >> 5) - (first >> 5) + 1 if count else 0
+        out = dict(sphere=np.zeros((count, 4), np.uint32), cone=np.zeros(count, np.uint32), mat=np.zeros(count, np.uint16),
+                   cmd=np.zeros((count, 3), np.uint32), cnt=np.zeros(count, np.uint16), link=np.zeros(words, np.uint32),
+                   cls0=np.zeros(words, np.uint32), cls1=np.zeros(words, np.uint32), base32=np.zeros((words, 2), np.uint32))
+        block = _lib.MeshletStreamArrays(**{k: v.ctypes.data for k, v in out.items()})
+        _lib.check(self._lib.orbit_meshlet_stream_read_arrays(self._engine._ctx, self._h, first, count, C.byref(block),
+                                                              _stream(stream)), self._engine._ctx)
+        return out
 
     def close(self):
         """orbit_meshlet_stream_destroy.  The library refuses while a context still has the stream bound; the engine

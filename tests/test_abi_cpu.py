@@ -116,6 +116,8 @@ def test_meshlet_stream_entry_points_reject_null_without_a_device():
     h = C.c_void_p()
     assert lib.orbit_meshlet_stream_create(None, 0, 16, C.byref(h)) == _lib.E_INVALID and not h.value
     assert lib.orbit_meshlet_stream_update(None, None, None, 0, 0, None) == _lib.E_INVALID
+    assert lib.orbit_meshlet_stream_read_arrays(None, None, 0, 0, None, None) == _lib.E_INVALID
+    assert C.sizeof(_lib.MeshletStreamArrays) == 72
     assert lib.orbit_ctx_bind_meshlet_stream(None, None) == _lib.E_INVALID
     assert lib.orbit_meshlet_stream_destroy(None) == _lib.OK
     assert lib.orbit_ctx_meshlet_stream_culls(None) == 0

@@ -24,10 +24,11 @@ def capped(engine):  # noqa: F811
     engine.set_block_cull_grid(0)
 
 
-def record_sparse_flags(scene, cam, recs, stream_count=None):
+def record_sparse_flags(scene, cam, recs, stream_count=None, stream_first=0):
     """The sparse flag blk_setup derives for each dispatched record, from the host pre-test (orbit_host_block_pretest): a
-    record that does not start a block or is not inside the stream reads no bound and is dense; the others are what the
-    pre-test says of their view x model matrix, their block's bound and the planes."""
+    record that does not start a block or is not inside the stream [stream_first, stream_first + stream_count) reads no
+    bound and is dense; the others are what the pre-test says of their view x model matrix, their block's bound and the
+    planes."""
     from test_block_pretest_cpu import F, _host, bounds_of, slab_scale
 
     h = _host()
@@ -43,11 +44,12 @@ def record_sparse_flags(scene, cam, recs, stream_count=None):
     cones = (m["cone_axis"].view(np.uint8).astype(np.uint32) << np.array([0, 8, 16], dtype=np.uint32)).sum(1).astype(np.uint32) \
         | m["cone_cutoff"].view(np.uint8).astype(np.uint32) << 24
     planes = np.ascontiguousarray(cam.planes, dtype=F).reshape(-1, 4)
-    n_ms = len(m) if stream_count is None else stream_count
+    n_ms = len(m) - stream_first if stream_count is None else stream_count
     flags = np.zeros(len(recs), dtype=bool)
     out = np.zeros(32, dtype=np.uint8)
     for i, (ent, off, cnt, _) in enumerate(recs.tolist()):
-        if cnt == 0 or off % 32 != 0 or off >= n_ms or cnt > n_ms - off:
+        rel = off - stream_first
+        if cnt == 0 or off % 32 != 0 or rel < 0 or rel >= n_ms or cnt > n_ms - rel:
             continue
         c = cols[ent]
         with np.errstate(invalid="ignore"):

@@ -265,6 +265,21 @@ def test_stream_argument_errors(torch_mod, engine):
     assert b"outside the stream" in lib.orbit_last_error(engine._ctx)
     assert lib.orbit_meshlet_stream_update(engine._ctx, h, p, 140, 10, None) == _lib.OK
     assert lib.orbit_meshlet_stream_update(engine._ctx, h, p, 50, 0, None) == _lib.OK  # empty range: nothing enqueued
+    # read_arrays: the same range rule, every host array given
+    out = {k: np.zeros(100 * 16, np.uint8) for k, _ in _lib.MeshletStreamArrays._fields_}
+    block = _lib.MeshletStreamArrays(**{k: v.ctypes.data for k, v in out.items()})
+    assert lib.orbit_meshlet_stream_read_arrays(None, h, 50, 100, C.byref(block), None) == _lib.E_INVALID
+    assert lib.orbit_meshlet_stream_read_arrays(engine._ctx, None, 50, 100, C.byref(block), None) == _lib.E_MISSING
+    assert lib.orbit_meshlet_stream_read_arrays(engine._ctx, h, 50, 100, None, None) == _lib.E_MISSING
+    assert lib.orbit_meshlet_stream_read_arrays(engine._ctx, h, 49, 10, C.byref(block), None) == _lib.E_CAPACITY
+    assert lib.orbit_meshlet_stream_read_arrays(engine._ctx, h, 50, 101, C.byref(block), None) == _lib.E_CAPACITY
+    assert lib.orbit_meshlet_stream_read_arrays(engine._ctx, h, 140, 11, C.byref(block), None) == _lib.E_CAPACITY
+    assert b"outside the stream" in lib.orbit_last_error(engine._ctx)
+    assert lib.orbit_meshlet_stream_read_arrays(engine._ctx, h, 150, 0, C.byref(block), None) == _lib.OK  # nothing copied
+    assert lib.orbit_meshlet_stream_read_arrays(engine._ctx, h, 50, 100, C.byref(block), None) == _lib.OK
+    assert not out["sphere"].any() and out["cls0"][:16].view(np.uint32)[1] == 0xFFFFFFFF  # a zero buffer; class 3 everywhere
+    block.cnt = None
+    assert lib.orbit_meshlet_stream_read_arrays(engine._ctx, h, 50, 100, C.byref(block), None) == _lib.E_MISSING
     assert lib.orbit_ctx_bind_meshlet_stream(None, h) == _lib.E_INVALID
     assert lib.orbit_ctx_bind_meshlet_stream(engine._ctx, h) == _lib.OK
     assert lib.orbit_ctx_bind_meshlet_stream(engine._ctx, None) == _lib.OK
