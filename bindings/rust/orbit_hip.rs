@@ -155,6 +155,27 @@ pub struct OrbitRasterVisibility {
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct OrbitVisibilityStats { pub covered_pixels: u32, pub visible_commands: u32, pub foreign_pixels: u32, pub _pad: u32 }
 
+pub const ORBIT_COMPACT_TRIANGLES: u32 = 1;
+
+/// The counters of orbit_visibility_compact (32 B, DEVICE, cleared by the call)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitVisibilityCompactStats {
+    pub covered_pixels: u32, pub foreign_pixels: u32, pub visible_commands: u32, pub visible_triangles: u32,
+    pub written_commands: u32, pub dropped_commands: u32, pub data_words_needed: u32, pub range_errors: u32,
+}
+
+/// orbit_visibility_compact's argument block (120 B, HOST): DEVICE pointers; visible_ids and stats may be null,
+/// meshlet_data and visible_data only without ORBIT_COMPACT_TRIANGLES
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitVisibilityCompact {
+    pub visibility: *const u64, pub draw_commands: *const c_void, pub meshlet_data: *const u32,
+    pub triangle_masks: *mut u32, pub visible_commands: *mut c_void, pub visible_ids: *mut u32,
+    pub visible_data: *mut u32, pub stats: *mut OrbitVisibilityCompactStats, pub workspace: *mut c_void,
+    pub meshlet_data_words: u64, pub workspace_bytes: u64,
+    pub width: u32, pub height: u32, pub command_base: u32, pub max_commands: u32,
+    pub visible_capacity: u32, pub visible_data_words: u32, pub flags: u32, pub _pad: u32,
+}
+
 /// orbit_visibility_resolve's argument block (48 B, HOST): DEVICE pointers; each output may be null, not all
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct OrbitVisibilityResolve {
@@ -364,6 +385,10 @@ extern "C" {
     pub fn orbit_raster_visibility(ctx: *mut OrbitCtx, job: *const OrbitRasterVisibility, stream: *mut c_void) -> i32;
     /// One read of the visibility buffer: depth (the high halves), pixels per command, covered / visible / foreign counts.
     pub fn orbit_visibility_resolve(ctx: *mut OrbitCtx, job: *const OrbitVisibilityResolve, stream: *mut c_void) -> i32;
+    /// The bytes of scratch orbit_visibility_compact needs for a list of max_commands.
+    pub fn orbit_visibility_compact_workspace(max_commands: u32) -> u64;
+    /// The exact visible draw list of a visibility buffer, optionally cut down to the visible triangles (C1-C6).
+    pub fn orbit_visibility_compact(ctx: *mut OrbitCtx, job: *const OrbitVisibilityCompact, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

@@ -1138,6 +1138,116 @@ ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilityResolve, width) == 32, "width @32");
 int32_t orbit_raster_visibility(OrbitCtx *ctx, const OrbitRasterVisibility *job, void *stream);
 int32_t orbit_visibility_resolve(OrbitCtx *ctx, const OrbitVisibilityResolve *job, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* The visible draw list.  orbit_visibility_compact turns a visibility      */
+/* buffer and the list that produced it into the exact list of the commands */
+/* that own a pixel, in the list's order, optionally cut down to the        */
+/* triangles that own one.  The output has the layout orbit_meshlet_cull    */
+/* writes and orbit_raster_depth / orbit_raster_visibility read.  ONE       */
+/* definition for the device and the host mirror                            */
+/* (orbit_host_visibility_compact); the two agree on every byte of every    */
+/* output.                                                                  */
+/*  C1 mark: n = min(count, max_commands), the count read ON THE DEVICE and */
+/*     never read back.  A word != 0 with k = ((word >> 8) & 0xFFFFFF) -    */
+/*     command_base (u32, wrapping) and t = word & 255 sets bit t & 31 of   */
+/*     triangle_masks[8 * k + (t >> 5)] iff k < n; any other covered pixel  */
+/*     is foreign.  THIS DIFFERS FROM orbit_visibility_resolve, which owns  */
+/*     k < max_commands without reading the list.  covered_pixels = words   */
+/*     != 0.  The masks of k >= n stay 0 (all 8 * max_commands words are    */
+/*     cleared by the call).                                                */
+/*  C2 visible: command k is visible iff its 256-bit mask is non-zero; m_k  */
+/*     is the mask's popcount.  It is CONSISTENT iff nt = cmd_index_count / */
+/*     3 <= 256 and no mask bit t >= nt is set; with                        */
+/*     ORBIT_COMPACT_TRIANGLES it must also pass R9's checks that concern   */
+/*     meshlet_data: first_word = cmd_first_index / 4 >= cmd_vertex_offset  */
+/*     (u32 bits), vcount = first_word - cmd_vertex_offset <= 255,          */
+/*     first_word <= meshlet_data_words and (cmd_first_index + 3 * nt + 3)  */
+/*     / 4 <= meshlet_data_words (in 64 bits).  A visible, inconsistent     */
+/*     command is skipped whole, counted in range_errors, and latches       */
+/*     ORBIT_E_RANGE; it only arises when the buffer was not made from this */
+/*     list.  visible_commands and visible_triangles count the visible      */
+/*     consistent commands and their set bits.                              */
+/*  C3 order and capacity: the visible consistent commands are numbered j = */
+/*     0, 1, ... in ascending k.  With the flag size_j = vcount + (3 * m +  */
+/*     3) / 4 words, base_j = the sum of the sizes before j (in 64 bits),   */
+/*     data_words_needed = the total (saturating at 2^32 - 1); without it   */
+/*     every size is 0.  Command j is written iff j < visible_capacity and, */
+/*     with the flag, base_j + size_j <= visible_data_words.  base_j +      */
+/*     size_j grows with j, so the written commands are a prefix.           */
+/*     visible_commands[0] (the output's count) = written_commands; the     */
+/*     rest are dropped_commands; any drop latches ORBIT_E_CAPACITY.        */
+/*     data_words_needed and stats.visible_commands tell the caller what to */
+/*     allocate.  visible_ids[j] = command_base + k.  Entries behind the    */
+/*     written ones are not touched.                                        */
+/*  C4 without the flag the written command is the input command's seven    */
+/*     words verbatim (it still reads the original meshlet_data).           */
+/*  C5 with the flag visible_data[base_j, base_j + vcount) is a copy of     */
+/*     meshlet_data[cmd_vertex_offset, + vcount); then come the corner      */
+/*     bytes of the set triangles in ascending t, three bytes each, packed; */
+/*     the pad bytes of the last word are 0.  The command is copied with    */
+/*     cmd_index_count = 3 * m, cmd_vertex_offset = base_j and              */
+/*     cmd_first_index = 4 * (base_j + vcount): R1 decodes the same vcount  */
+/*     from it.  Words of visible_data beyond the written regions are not   */
+/*     touched.                                                             */
+/*  C6 consequences.  Let the buffer come from ONE ORBIT_RASTER_CLEAR call  */
+/*     of the list with this command_base, and nothing be dropped.          */
+/*     Rasterise the output list with the same flags, command_base 0, and   */
+/*     visible_data (flag) or the original meshlet_data (no flag):          */
+/*     (a) the high halves are equal byte for byte; (b) a pixel that held   */
+/*     (command_base + k, t) holds (j, r) with visible_ids[j] =             */
+/*     command_base + k; (c) r is the rank of t among the set bits of mask  */
+/*     k, and r = t without the flag — ties keep their winner, because both */
+/*     orders are preserved; (d) with the flag the output raster's          */
+/*     `triangles` equals visible_triangles and its four skip counters are  */
+/*     0.  Resolving the output buffer gives visible_commands ==            */
+/*     written_commands and no entry of command_pixels is 0.                */
+/* stats (may be NULL) is cleared by the call, as are triangle_masks, the   */
+/* workspace and the output's count.  All outputs are integer sums, ORs and */
+/* prefix sums: independent of scheduling.                                  */
+/*   ORBIT_E_INVALID  job NULL; visibility, draw_commands, triangle_masks,  */
+/*                    visible_commands or workspace NULL; meshlet_data or   */
+/*                    visible_data NULL with ORBIT_COMPACT_TRIANGLES; a     */
+/*                    pointer misaligned (visibility, workspace: 8 B, the   */
+/*                    rest: 4 B); workspace_bytes <                         */
+/*                    orbit_visibility_compact_workspace(max_commands);     */
+/*                    width or height 0 or above ORBIT_RASTER_MAX_DIM;      */
+/*                    command_base + max_commands > ORBIT_VIS_MAX_COMMANDS; */
+/*                    visible_data_words > 2^30 (cmd_first_index is a byte  */
+/*                    offset in 32 bits); unknown flags                     */
+/* max_commands 0, or a count of 0, is ORBIT_OK with an empty list (the     */
+/* pixels are still counted: all covered ones are foreign).  The call       */
+/* allocates nothing, takes all scratch from the caller, never waits on the */
+/* host and is kernel nodes only: a graph captures it on a fresh context's  */
+/* first call.                                                              */
+/* ------------------------------------------------------------------------ */
+#define ORBIT_COMPACT_TRIANGLES 1u /* flags: cut each visible command down to its visible triangles */
+typedef struct OrbitVisibilityCompactStats { /* DEVICE, 32 B, cleared by the call */
+    uint32_t covered_pixels, foreign_pixels, visible_commands, visible_triangles, written_commands, dropped_commands,
+        data_words_needed, range_errors;
+} OrbitVisibilityCompactStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitVisibilityCompactStats) == 32, "VisibilityCompactStats is 32 B");
+typedef struct OrbitVisibilityCompact { /* HOST block, 120 B; every pointer a DEVICE pointer */
+    const uint64_t *visibility;         /* width * height u64, as orbit_raster_visibility left it */
+    const void *draw_commands;          /* {u32 count; OrbitMeshletDrawCommand[max_commands]}: the list that was rasterised with this command_base */
+    const uint32_t *meshlet_data;       /* its meshlet_data; may be NULL without ORBIT_COMPACT_TRIANGLES */
+    uint32_t *triangle_masks;           /* required: 8 * max_commands words, cleared by the call */
+    void *visible_commands;             /* required: {u32 count; OrbitMeshletDrawCommand[visible_capacity]} */
+    uint32_t *visible_ids;              /* NULL, or visible_capacity words */
+    uint32_t *visible_data;             /* required iff ORBIT_COMPACT_TRIANGLES: visible_data_words words */
+    OrbitVisibilityCompactStats *stats; /* NULL, or the counters */
+    void *workspace;                    /* required: orbit_visibility_compact_workspace(max_commands) bytes, 8-B aligned */
+    uint64_t meshlet_data_words, workspace_bytes;
+    uint32_t width, height, command_base, max_commands, visible_capacity, visible_data_words, flags, _pad;
+} OrbitVisibilityCompact;
+ORBIT_STATIC_ASSERT(sizeof(OrbitVisibilityCompact) == 120, "VisibilityCompact is 120 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilityCompact, meshlet_data_words) == 72, "meshlet_data_words @72");
+ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilityCompact, width) == 88, "width @88");
+
+/* the scratch of the call below, in bytes: a function of max_commands alone, never 0 */
+uint64_t orbit_visibility_compact_workspace(uint32_t max_commands);
+/* the exact visible draw list of a visibility buffer; see above */
+int32_t orbit_visibility_compact(OrbitCtx *ctx, const OrbitVisibilityCompact *job, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

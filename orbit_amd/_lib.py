@@ -120,6 +120,19 @@ class VisibilityResolve(C.Structure):  # OrbitVisibilityResolve
                 ("width", C.c_uint32), ("height", C.c_uint32), ("command_base", C.c_uint32), ("max_commands", C.c_uint32)]
 
 
+class VisibilityCompact(C.Structure):  # OrbitVisibilityCompact (120 B)
+    _fields_ = [("visibility", C.c_void_p), ("draw_commands", C.c_void_p), ("meshlet_data", C.c_void_p),
+                ("triangle_masks", C.c_void_p), ("visible_commands", C.c_void_p), ("visible_ids", C.c_void_p),
+                ("visible_data", C.c_void_p), ("stats", C.c_void_p), ("workspace", C.c_void_p),
+                ("meshlet_data_words", C.c_uint64), ("workspace_bytes", C.c_uint64), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("command_base", C.c_uint32), ("max_commands", C.c_uint32),
+                ("visible_capacity", C.c_uint32), ("visible_data_words", C.c_uint32), ("flags", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+COMPACT_TRIANGLES = 1  # ORBIT_COMPACT_TRIANGLES
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -218,6 +231,8 @@ SYMBOLS = {
     "orbit_raster_depth": (C.c_int32, [C.c_void_p, C.POINTER(RasterDepth), C.c_void_p]),
     "orbit_raster_visibility": (C.c_int32, [C.c_void_p, C.POINTER(RasterVisibility), C.c_void_p]),
     "orbit_visibility_resolve": (C.c_int32, [C.c_void_p, C.POINTER(VisibilityResolve), C.c_void_p]),
+    "orbit_visibility_compact_workspace": (C.c_uint64, [C.c_uint32]),
+    "orbit_visibility_compact": (C.c_int32, [C.c_void_p, C.POINTER(VisibilityCompact), C.c_void_p]),
 }
 
 _lib = None

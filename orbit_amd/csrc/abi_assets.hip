@@ -1,7 +1,8 @@
 // abi_assets.hip — the C ABI's calls that read the vertex buffer (include/orbit_abi_ext.h): orbit_meshlet_bounds and
 // orbit_mesh_bounds, the refit of Meshlet and MeshInfo bounds on the device (meshlet_bounds.hip), orbit_raster_depth,
 // the depth prepass of the draw commands in compute (raster_depth.hip), and orbit_raster_visibility with
-// orbit_visibility_resolve, the same pass keeping the winner's identity and its resolve (raster_visibility.hip).
+// orbit_visibility_resolve, the same pass keeping the winner's identity and its resolve (raster_visibility.hip), and
+// orbit_visibility_compact, the visible draw list of such a buffer (visibility_compact.hip).
 #include "abi_internal.h"
 
 namespace {
@@ -147,6 +148,42 @@ int32_t orbit_visibility_resolve(OrbitCtx *ctx, const OrbitVisibilityResolve *jo
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_visibility_resolve(j, ctx->num_cus, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_resolve");
+    return ORBIT_OK;
+}
+
+uint64_t orbit_visibility_compact_workspace(uint32_t max_commands) { return visibility_compact_workspace_bytes(max_commands); }
+
+// Five launches (clear, mark, scan, totals, emit) on the stream; the command count stays on the device and all scratch is
+// the caller's.  No allocation, no host sync: capturable on the first call.  The job is checked before the context is
+// looked at (the checks read neither), so each of them can be reached without a device: a NULL context is the last error.
+int32_t orbit_visibility_compact(OrbitCtx *ctx, const OrbitVisibilityCompact *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "visibility_compact: job is NULL");
+    const OrbitVisibilityCompact &j = *job;
+    if (j.flags & ~ORBIT_COMPACT_TRIANGLES) return fail(ctx, ORBIT_E_INVALID, "visibility_compact: flags %#x", j.flags);
+    const bool cut = (j.flags & ORBIT_COMPACT_TRIANGLES) != 0u;
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "visibility_compact: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS)
+        return fail(ctx, ORBIT_E_INVALID, "visibility_compact: command_base %u + max_commands %u > %u (24 bits of id)",
+                    j.command_base, j.max_commands, ORBIT_VIS_MAX_COMMANDS);
+    if (j.visible_data_words > (1u << 30))
+        return fail(ctx, ORBIT_E_INVALID, "visibility_compact: visible_data_words %u > 2^30 (cmd_first_index is a byte offset)",
+                    j.visible_data_words);
+    if (!j.visibility || !j.draw_commands || !j.triangle_masks || !j.visible_commands || !j.workspace)
+        return fail(ctx, ORBIT_E_INVALID, "visibility_compact: NULL buffer");
+    if (cut && (!j.meshlet_data || !j.visible_data))
+        return fail(ctx, ORBIT_E_INVALID, "visibility_compact: ORBIT_COMPACT_TRIANGLES needs meshlet_data and visible_data");
+    if ((((uintptr_t)j.visibility | (uintptr_t)j.workspace) & 7u) ||
+        (((uintptr_t)j.draw_commands | (uintptr_t)j.meshlet_data | (uintptr_t)j.triangle_masks | (uintptr_t)j.visible_commands |
+          (uintptr_t)j.visible_ids | (uintptr_t)j.visible_data | (uintptr_t)j.stats) & 3u))
+        return fail(ctx, ORBIT_E_INVALID, "visibility_compact: visibility and workspace must be 8-B aligned, every other buffer 4-B aligned");
+    if (j.workspace_bytes < visibility_compact_workspace_bytes(j.max_commands))
+        return fail(ctx, ORBIT_E_INVALID, "visibility_compact: workspace of %llu bytes, %llu needed", (unsigned long long)j.workspace_bytes,
+                    (unsigned long long)visibility_compact_workspace_bytes(j.max_commands));
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "visibility_compact: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_visibility_compact(j, ctx->num_cus, ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_compact");
     return ORBIT_OK;
 }
 

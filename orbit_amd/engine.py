@@ -59,6 +59,11 @@ def depth_pyramid_desc(screen_width, screen_height):
     return d
 
 
+def visibility_compact_workspace(max_commands):
+    """The bytes of scratch Engine.visibility_compact needs for a list of max_commands (orbit_visibility_compact_workspace)."""
+    return int(_lib.load().orbit_visibility_compact_workspace(int(max_commands)))
+
+
 def shard_range(entity_draw_count, rank, world):
     b, e = C.c_uint32(), C.c_uint32()
     _lib.load().orbit_shard_range(entity_draw_count, rank, world, C.byref(b), C.byref(e))
@@ -398,6 +403,35 @@ class Engine:
         j.visibility, j.depth, j.command_pixels, j.stats = _ptr(visibility), _ptr(depth), _ptr(command_pixels), _ptr(stats)
         j.width, j.height, j.command_base, j.max_commands = int(width), int(height), int(command_base), int(max_commands)
         _lib.check(self._lib.orbit_visibility_resolve(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
+    # -- the exact visible draw list of a visibility buffer (orbit_visibility_compact)
+    def visibility_compact(self, visibility, width, height, draw_commands, max_commands, triangle_masks, visible_commands,
+                           visible_capacity, workspace, command_base=0, meshlet_data=None, meshlet_data_words=None,
+                           visible_ids=None, visible_data=None, visible_data_words=0, stats=None, triangles=False,
+                           workspace_bytes=None, stream=None):
+        """From the width x height u64 tensor `visibility` and the {u32 count; 28-B commands} `draw_commands` that were
+        rasterised into it with `command_base` to the list of the commands that own a pixel, in the list's order, in
+        `visible_commands` ({u32 count; visible_capacity commands}: what raster_depth / raster_visibility read).
+        triangle_masks (8 * max_commands u32, cleared by the call): bit t of command k's 256 bits = triangle t owns a
+        pixel.  visible_ids (visible_capacity u32 or None): command_base + k of each written command.  triangles=True
+        (ORBIT_COMPACT_TRIANGLES): each command is cut down to the triangles that own a pixel, its index words and
+        their corner bytes packed into `visible_data` (visible_data_words u32), which the output list then indexes in
+        place of `meshlet_data`.  stats (32 bytes, layouts.VIS_COMPACT_STATS, cleared by the call): visible_commands
+        and data_words_needed tell what to allocate.  workspace: visibility_compact_workspace(max_commands) bytes,
+        8-B aligned.  Byte-equal to orbit_amd.raster.host_visibility_compact.  Enqueued on `stream`; a dropped command
+        is reported by status() (ORBIT_E_CAPACITY), a buffer that was not made from this list by ORBIT_E_RANGE."""
+        nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
+        j = _lib.VisibilityCompact()
+        j.visibility, j.draw_commands, j.meshlet_data = _ptr(visibility), _ptr(draw_commands), _ptr(meshlet_data)
+        j.triangle_masks, j.visible_commands, j.visible_ids = _ptr(triangle_masks), _ptr(visible_commands), _ptr(visible_ids)
+        j.visible_data, j.stats, j.workspace = _ptr(visible_data), _ptr(stats), _ptr(workspace)
+        j.meshlet_data_words = nbytes(meshlet_data) // 4 if meshlet_data_words is None else int(meshlet_data_words)
+        j.workspace_bytes = ((nbytes(workspace) if not isinstance(workspace, int) else visibility_compact_workspace(max_commands))
+                             if workspace_bytes is None else int(workspace_bytes))
+        j.width, j.height, j.command_base, j.max_commands = int(width), int(height), int(command_base), int(max_commands)
+        j.visible_capacity, j.visible_data_words = int(visible_capacity), int(visible_data_words)
+        j.flags = _lib.COMPACT_TRIANGLES if triangles else 0
+        _lib.check(self._lib.orbit_visibility_compact(self._ctx, C.byref(j), _stream(stream)), self._ctx)
 
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,

@@ -597,6 +597,13 @@ int32_t orbit_host_visibility_resolve(const uint64_t *visibility, uint32_t width
     });
 }
 
+int32_t orbit_host_visibility_compact(const OrbitVisibilityCompact *job, int32_t *status) {
+    return guarded([&] {
+        if (!job) throw Panic("visibility_compact: job is NULL");
+        raster::visibility_compact(*job, status);
+    });
+}
+
 // ---------------------------------------------------------------- asset ingestion (orbit_gltf.hpp), host only
 void *orbit_host_gltf_load(const char *path) {
     gltf_loader::LoadedScene *scene = nullptr;

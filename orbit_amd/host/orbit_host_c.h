@@ -243,6 +243,11 @@ int32_t orbit_host_raster_visibility(const void *draw_commands, uint32_t max_com
 int32_t orbit_host_visibility_resolve(const uint64_t *visibility, uint32_t width, uint32_t height, uint32_t command_base,
                                       uint32_t max_commands, float *depth, uint32_t *command_pixels,
                                       OrbitVisibilityStats *stats);
+/* the reference of orbit_visibility_compact (C1-C6): the device call's block with HOST pointers in it; workspace and
+ * workspace_bytes are not read.  Every output holds the device's bytes.  *status (may be NULL): what the device latches,
+ * ORBIT_E_RANGE before ORBIT_E_CAPACITY before ORBIT_OK.  ORBIT_HOST_PANIC for what the device answers with
+ * ORBIT_E_INVALID (alignment and the workspace aside). */
+int32_t orbit_host_visibility_compact(const OrbitVisibilityCompact *job, int32_t *status);
 
 /* ---- asset ingestion (orbit_gltf.hpp): glTF 2.0 (.glb / .gltf) -> materials, meshes with their LOD chains, entities ----
  * load_gltf (gltf_loader.rs:511-676) + GpuAssets::add_mesh (assets/mod.rs:325-476).  NULL + orbit_host_last_error()

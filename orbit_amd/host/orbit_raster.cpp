@@ -191,5 +191,87 @@ void visibility_resolve(const uint64_t *visibility, uint32_t width, uint32_t hei
     if (stats) *stats = st;
 }
 
+void visibility_compact(const OrbitVisibilityCompact &j, int32_t *status) {
+    const bool cut = (j.flags & ORBIT_COMPACT_TRIANGLES) != 0u;
+    if (j.flags & ~ORBIT_COMPACT_TRIANGLES) throw Panic("visibility_compact: unknown flags");
+    if (!j.visibility || !j.draw_commands || !j.triangle_masks || !j.visible_commands) throw Panic("visibility_compact: NULL argument");
+    if (cut && (!j.meshlet_data || !j.visible_data)) throw Panic("visibility_compact: ORBIT_COMPACT_TRIANGLES without meshlet_data or visible_data");
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        throw Panic("visibility_compact: target size");
+    if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS) throw Panic("visibility_compact: command_base + max_commands");
+    if (j.visible_data_words > (1u << 30)) throw Panic("visibility_compact: visible_data_words");
+    const uint32_t *commands = static_cast<const uint32_t *>(j.draw_commands);
+    uint32_t *out = static_cast<uint32_t *>(j.visible_commands);
+    const uint32_t n = commands[0] < j.max_commands ? commands[0] : j.max_commands;
+    OrbitVisibilityCompactStats st{};
+    int32_t latched = ORBIT_OK;
+    // C1
+    std::memset(j.triangle_masks, 0, (size_t)j.max_commands * 32);
+    for (size_t p = 0; p < (size_t)j.width * j.height; p++) {
+        const uint64_t word = j.visibility[p];
+        if (word == 0) continue;
+        st.covered_pixels++;
+        const uint32_t id = (uint32_t)(word >> 8) & 0xFFFFFFu, t = (uint32_t)word & 255u;
+        if (id < j.command_base || id - j.command_base >= n) {
+            st.foreign_pixels++;
+            continue;
+        }
+        j.triangle_masks[8u * (size_t)(id - j.command_base) + (t >> 5)] |= 1u << (t & 31u);
+    }
+    // C2-C5, command after command
+    const uint8_t *data_bytes = reinterpret_cast<const uint8_t *>(j.meshlet_data);
+    uint64_t next_word = 0; // base of the next visible consistent command
+    bool dropping = false;
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t *mask = j.triangle_masks + 8u * (size_t)k, *cmd = commands + 1u + 7u * (size_t)k;
+        const uint32_t nt = cmd[0] / 3u, first_index = cmd[2], index_base = cmd[3], first_word = first_index / 4u;
+        uint32_t m = 0;
+        bool beyond = false;
+        for (uint32_t t = 0; t < 256u; t++)
+            if (mask[t >> 5] >> (t & 31u) & 1u) {
+                m++;
+                if (t >= nt) beyond = true;
+            }
+        if (m == 0) continue;
+        bool consistent = nt <= 256u && !beyond;
+        const uint32_t vcount = first_word - index_base;
+        if (cut && (first_word < index_base || vcount > 255u || (uint64_t)first_word > j.meshlet_data_words ||
+                    ((uint64_t)first_index + 3ull * nt + 3ull) / 4ull > j.meshlet_data_words))
+            consistent = false;
+        if (!consistent) {
+            st.range_errors++;
+            latched = ORBIT_E_RANGE;
+            continue;
+        }
+        const uint32_t jv = st.visible_commands++;
+        st.visible_triangles += m;
+        const uint32_t size = cut ? vcount + (3u * m + 3u) / 4u : 0u;
+        const uint64_t base = next_word;
+        next_word += size;
+        if (dropping || jv >= j.visible_capacity || (cut && base + size > j.visible_data_words)) {
+            dropping = true; // (base + size only grows: nothing behind a dropped command fits)
+            st.dropped_commands++;
+            continue;
+        }
+        st.written_commands++;
+        uint32_t *dst = out + 1u + 7u * (size_t)jv;
+        std::memcpy(dst, cmd, 28);
+        if (j.visible_ids) j.visible_ids[jv] = j.command_base + k;
+        if (!cut) continue;
+        uint32_t *region = j.visible_data + base;
+        dst[0] = 3u * m, dst[2] = 4u * ((uint32_t)base + vcount), dst[3] = (uint32_t)base;
+        std::memcpy(region, j.meshlet_data + index_base, (size_t)vcount * 4);
+        uint8_t *corners = reinterpret_cast<uint8_t *>(region + vcount);
+        std::memset(corners, 0, (size_t)(size - vcount) * 4);
+        for (uint32_t t = 0, r = 0; t < nt; t++)
+            if (mask[t >> 5] >> (t & 31u) & 1u) std::memcpy(corners + 3u * (size_t)r++, data_bytes + (size_t)first_index + 3u * (size_t)t, 3);
+    }
+    out[0] = st.written_commands;
+    st.data_words_needed = next_word > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)next_word;
+    if (st.dropped_commands != 0 && latched == ORBIT_OK) latched = ORBIT_E_CAPACITY;
+    if (j.stats) *j.stats = st;
+    if (status) *status = latched;
+}
+
 } // namespace raster
 } // namespace orbit

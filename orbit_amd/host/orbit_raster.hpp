@@ -40,5 +40,11 @@ void raster_visibility(const HostJob &job, uint64_t *visibility, uint32_t comman
 void visibility_resolve(const uint64_t *visibility, uint32_t width, uint32_t height, uint32_t command_base,
                         uint32_t max_commands, float *depth, uint32_t *command_pixels, OrbitVisibilityStats *stats);
 
+// orbit_visibility_compact (C1-C6, §4.18) on host buffers: the job's pointers are HOST pointers, `workspace` and
+// `workspace_bytes` are not read.  Sequential, the obvious loop.  *status (may be null) = what the device call latches:
+// ORBIT_E_RANGE if a visible command was inconsistent, else ORBIT_E_CAPACITY if one was dropped, else ORBIT_OK (the
+// scan, which finds the first, runs before the emit, which finds the second).  Throws Panic for ORBIT_E_INVALID.
+void visibility_compact(const OrbitVisibilityCompact &job, int32_t *status);
+
 } // namespace raster
 } // namespace orbit

@@ -60,6 +60,10 @@ RASTER_STATS = np.dtype([(n, "<u4") for n in ("commands", "triangles", "clip_ski
                                               "no_coverage", "fragments", "range_errors")])
 # OrbitVisibilityStats: the counters of orbit_visibility_resolve
 VIS_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "visible_commands", "foreign_pixels", "_pad")])
+# OrbitVisibilityCompactStats: the counters of orbit_visibility_compact
+VIS_COMPACT_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "foreign_pixels", "visible_commands",
+                                                   "visible_triangles", "written_commands", "dropped_commands",
+                                                   "data_words_needed", "range_errors")])
 # types.glsl:92-110, src/assets/mod.rs:171-191
 MATERIAL = np.dtype([
     ("base_color", "<f4", (4,)), ("emissive_factor", "<f4", (3,)), ("metallic_factor", "<f4"),

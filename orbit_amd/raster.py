@@ -1,7 +1,8 @@
 """ctypes binding of the host mirror of ``orbit_raster_depth``, ``orbit_raster_visibility`` and
 ``orbit_visibility_resolve`` (``orbit_amd/host/orbit_raster.hpp``): the depth prepass of a MeshletDrawCommandBuffer on
 host arrays, the same pass keeping the winner's identity and its resolve — the references of ``Engine.raster_depth``,
-``Engine.raster_visibility`` and ``Engine.visibility_resolve``.  Python adds nothing; host only."""
+``Engine.raster_visibility`` and ``Engine.visibility_resolve`` — and of ``orbit_visibility_compact``, the visible draw
+list of such a buffer, the reference of ``Engine.visibility_compact``.  Python adds nothing; host only."""
 import ctypes as C
 
 import numpy as np
@@ -95,3 +96,38 @@ def host_visibility_resolve(visibility, command_base=0, max_commands=0, want_com
     _check(lib().orbit_host_visibility_resolve(p(vis), C.c_uint32(width), C.c_uint32(height), C.c_uint32(command_base),
                                                C.c_uint32(max_commands), p(depth), p(pixels), p(stats)))
     return depth, None if pixels is None else pixels[:int(max_commands)], stats[0]
+
+
+def host_visibility_compact(visibility, draw_commands, max_commands, command_base=0, meshlet_data=None, triangles=False,
+                            visible_capacity=None, visible_data_words=None, meshlet_data_words=None, fill=0,
+                            want_ids=True):
+    """orbit_host_visibility_compact on a (height, width) np.uint64 buffer and the {count; commands} words that were
+    rasterised into it -> dict(masks: np.uint32[8 * max_commands], commands: np.uint32[1 + 7 * visible_capacity] (the
+    output list), ids: np.uint32[visible_capacity] or None, data: np.uint32[visible_data_words] or None (only with
+    triangles=True, ORBIT_COMPACT_TRIANGLES), stats: np[layouts.VIS_COMPACT_STATS] scalar row, status: what the device
+    call latches).  The capacities default to max_commands commands and, with triangles, the words of meshlet_data.
+    Every output is filled with `fill` (a u32) first: what the call does not write keeps it."""
+    vis = np.ascontiguousarray(visibility, dtype=np.uint64)
+    height, width = vis.shape
+    buf = np.ascontiguousarray(draw_commands).view(np.uint8).reshape(-1)
+    if buf.nbytes < 4 + 28 * int(max_commands):
+        raise ValueError("max_commands reaches beyond the command array")
+    data = None if meshlet_data is None else np.ascontiguousarray(meshlet_data, dtype=np.uint32).reshape(-1)
+    if triangles and data is None:
+        raise ValueError("triangles=True needs meshlet_data")
+    cap = int(max_commands) if visible_capacity is None else int(visible_capacity)
+    words = (len(data) if triangles else 0) if visible_data_words is None else int(visible_data_words)
+    new = lambda n: np.full(max(int(n), 1), fill, np.uint32)  # noqa: E731
+    masks, out, ids, stats = new(8 * max_commands), new(1 + 7 * cap), new(cap) if want_ids else None, np.zeros(1, L.VIS_COMPACT_STATS)
+    vdata = new(words) if triangles else None
+    p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    j = _lib.VisibilityCompact()
+    j.visibility, j.draw_commands, j.meshlet_data, j.triangle_masks = p(vis), p(buf), p(data), p(masks)
+    j.visible_commands, j.visible_ids, j.visible_data, j.stats = p(out), p(ids), p(vdata), p(stats)
+    j.meshlet_data_words = (0 if data is None else len(data)) if meshlet_data_words is None else int(meshlet_data_words)
+    j.width, j.height, j.command_base, j.max_commands = width, height, int(command_base), int(max_commands)
+    j.visible_capacity, j.visible_data_words, j.flags = cap, words, _lib.COMPACT_TRIANGLES if triangles else 0
+    status = C.c_int32(0)
+    _check(lib().orbit_host_visibility_compact(C.byref(j), C.byref(status)))
+    return dict(masks=masks[:8 * int(max_commands)], commands=out[:1 + 7 * cap], ids=None if ids is None else ids[:cap],
+                data=None if vdata is None else vdata[:words], stats=stats[0], status=status.value)
