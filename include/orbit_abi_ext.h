@@ -224,6 +224,11 @@ int32_t orbit_ctx_set_block_cull(OrbitCtx *ctx, uint32_t enable);
  * tiles one after another, so a small grid gives every wave a sequence of tiles from a small scene).  0, the default,
  * leaves the grid as the library sizes it.  The outputs do not depend on the grid; no other launch is touched. */
 int32_t orbit_ctx_set_block_cull_grid(OrbitCtx *ctx, uint32_t max_workgroups);
+/* Tests: every launch of orbit_raster_depth and orbit_raster_visibility, whichever flags pick the kernel, and the
+ * clearing launch in front of it take at most `max_workgroups` workgroups (of four waves; a wave takes its commands one
+ * after another, so under a cap of c wave k takes commands k, k + 4c, ... of even a short list).  0, the default,
+ * restores the resident grid.  The outputs do not depend on the grid; no other launch is touched. */
+int32_t orbit_ctx_set_raster_grid(OrbitCtx *ctx, uint32_t max_workgroups);
 /* Tests: the bounds of blocks [first_block, first_block + count) (block = global meshlet index / 32) into the HOST
  * array `out`, 32 B each: {float centre[3], centre_radius, max_radius; uint32_t valid, pad[2]}.  Waits for `stream`. */
 int32_t orbit_meshlet_stream_block_bounds(OrbitCtx *ctx, OrbitMeshletStream *ms, uint64_t first_block, uint64_t count,

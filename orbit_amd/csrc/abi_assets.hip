@@ -30,18 +30,23 @@ int32_t check_raster_job(OrbitCtx *ctx, const char *who, uint32_t flags, uint32_
     return ORBIT_OK;
 }
 
+// orbit_ctx_set_raster_grid: the workgroups a raster launch (and its clear) may take, `grid_cap` at most (0 = no cap)
+uint32_t capped_raster_grid(uint32_t resident_blocks, uint32_t grid_cap) {
+    return grid_cap != 0u && (resident_blocks == 0u || grid_cap < resident_blocks) ? grid_cap : resident_blocks;
+}
+
 // The kernel of job.flags on that kernel's own resident grid, both picked by the one variant (resident_blocks: the
 // context's row of the call)
 hipError_t launch_raster_depth_by_flags(const OrbitRasterDepth &job, const uint32_t (&resident_blocks)[kRasterVariants],
-                                        int32_t *status, hipStream_t s) {
+                                        uint32_t grid_cap, int32_t *status, hipStream_t s) {
     return with_raster_variant(raster_variant(job.flags), [&](auto v) {
-        return launch_raster_depth<v.value>(job, resident_blocks[(uint32_t)v.value], status, s);
+        return launch_raster_depth<v.value>(job, capped_raster_grid(resident_blocks[(uint32_t)v.value], grid_cap), status, s);
     });
 }
-hipError_t launch_raster_visibility_by_flags(const OrbitRasterVisibility &job,
-                                             const uint32_t (&resident_blocks)[kRasterVariants], int32_t *status, hipStream_t s) {
+hipError_t launch_raster_visibility_by_flags(const OrbitRasterVisibility &job, const uint32_t (&resident_blocks)[kRasterVariants],
+                                             uint32_t grid_cap, int32_t *status, hipStream_t s) {
     return with_raster_variant(raster_variant(job.flags), [&](auto v) {
-        return launch_raster_visibility<v.value>(job, resident_blocks[(uint32_t)v.value], status, s);
+        return launch_raster_visibility<v.value>(job, capped_raster_grid(resident_blocks[(uint32_t)v.value], grid_cap), status, s);
     });
 }
 
@@ -105,7 +110,7 @@ int32_t orbit_raster_depth(OrbitCtx *ctx, const OrbitRasterDepth *job, void *str
         return rc;
     if (!j.depth || ((uintptr_t)j.depth & 3u)) return fail(ctx, ORBIT_E_INVALID, "raster_depth: depth is NULL or not 4-B aligned");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_raster_depth_by_flags(j, ctx->raster_blocks, ctx->status, (hipStream_t)stream);
+    const hipError_t e = launch_raster_depth_by_flags(j, ctx->raster_blocks, ctx->raster_grid, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_depth");
     return ORBIT_OK;
 }
@@ -125,7 +130,7 @@ int32_t orbit_raster_visibility(OrbitCtx *ctx, const OrbitRasterVisibility *job,
     if (!j.visibility || ((uintptr_t)j.visibility & 7u))
         return fail(ctx, ORBIT_E_INVALID, "raster_visibility: visibility is NULL or not 8-B aligned");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_raster_visibility_by_flags(j, ctx->visibility_blocks, ctx->status, (hipStream_t)stream);
+    const hipError_t e = launch_raster_visibility_by_flags(j, ctx->visibility_blocks, ctx->raster_grid, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch raster_visibility");
     return ORBIT_OK;
 }

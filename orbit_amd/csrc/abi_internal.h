@@ -110,6 +110,7 @@ struct OrbitCtx {
     uint64_t block_culls = 0;                           // ... of which decided per block (meshlet_eval_blocks.hip)
     bool block_cull = true;                             // orbit_ctx_set_block_cull / ORBIT_BLOCK_CULL=0
     uint32_t block_cull_grid = 0;                       // orbit_ctx_set_block_cull_grid: workgroups at most (0 = no cap)
+    uint32_t raster_grid = 0;                           // orbit_ctx_set_raster_grid: the same for every raster launch
     char err[512] = {0};
 };
 

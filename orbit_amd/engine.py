@@ -747,6 +747,11 @@ class Engine:
         """orbit_ctx_set_block_cull_grid: at most that many workgroups for the per-block evaluation (0 = as sized; tests)."""
         _lib.check(self._lib.orbit_ctx_set_block_cull_grid(self._ctx, int(max_workgroups)), self._ctx)
 
+    def set_raster_grid(self, max_workgroups):
+        """orbit_ctx_set_raster_grid: at most that many workgroups for every raster launch and its clear (0 = the resident
+        grid; tests)."""
+        _lib.check(self._lib.orbit_ctx_set_raster_grid(self._ctx, int(max_workgroups)), self._ctx)
+
     def exchange_list(self, local_list, rank, world, out_buffers, ctrl_buffers, out_capacity, header_bytes, stride,
                       stream=None):
         """orbit_exchange_list: the rank-ordered all-gather of the ranks' lists with counts and completion signalled on
