@@ -229,6 +229,12 @@ int32_t orbit_ctx_set_block_cull_grid(OrbitCtx *ctx, uint32_t max_workgroups);
  * after another, so under a cap of c wave k takes commands k, k + 4c, ... of even a short list).  0, the default,
  * restores the resident grid.  The outputs do not depend on the grid; no other launch is touched. */
 int32_t orbit_ctx_set_raster_grid(OrbitCtx *ctx, uint32_t max_workgroups);
+/* Tests: every launch of the one-launch cull behind orbit_cull_views (either arithmetic profile, every tile shape) takes
+ * at most `max_workgroups` workgroups per view (of four waves; work is handed out by tickets, so under a cap of 1 or 2 a
+ * wave runs many tiles in a row and one workgroup runs every entity chunk).  Read when the launch is enqueued: a
+ * prepared call follows it too.  0, the default, restores the sized grid.  The outputs do not depend on the grid; the
+ * shard launch and every other launch are not touched. */
+int32_t orbit_ctx_set_fused_grid(OrbitCtx *ctx, uint32_t max_workgroups);
 /* Tests: the bounds of blocks [first_block, first_block + count) (block = global meshlet index / 32) into the HOST
  * array `out`, 32 B each: {float centre[3], centre_radius, max_radius; uint32_t valid, pad[2]}.  Waits for `stream`. */
 int32_t orbit_meshlet_stream_block_bounds(OrbitCtx *ctx, OrbitMeshletStream *ms, uint64_t first_block, uint64_t count,

@@ -364,7 +364,7 @@ int32_t prepare_cull_views(OrbitCtx *ctx, const OrbitCullView *views, uint32_t c
 int32_t launch_prepared_cull_views(OrbitCtx *ctx, const PreparedCullViews &pc, hipStream_t s) {
     hipError_t e;
     if (pc.fused) {
-        e = launch_cull_fused_views(pc.fv, pc.draws, pc.count, ctx->num_cus, s);
+        e = launch_cull_fused_views(pc.fv, pc.draws, pc.count, ctx->num_cus, s, ctx->fused_grid);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch cull_fused");
         ctx->fused_culls += pc.count;
         return ORBIT_OK;

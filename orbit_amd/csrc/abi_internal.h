@@ -111,6 +111,7 @@ struct OrbitCtx {
     bool block_cull = true;                             // orbit_ctx_set_block_cull / ORBIT_BLOCK_CULL=0
     uint32_t block_cull_grid = 0;                       // orbit_ctx_set_block_cull_grid: workgroups at most (0 = no cap)
     uint32_t raster_grid = 0;                           // orbit_ctx_set_raster_grid: the same for every raster launch
+    uint32_t fused_grid = 0;                            // orbit_ctx_set_fused_grid: the same for the one-launch cull's launches
     char err[512] = {0};
 };
 

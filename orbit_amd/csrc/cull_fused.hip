@@ -416,9 +416,9 @@ uint32_t fused_grid(uint32_t entity_draw_count, uint32_t rows, uint32_t num_cus,
 // orbit_cull_views: the n views of `all` — ONE launch for all of them (two when views of up to and of more than
 // kFusedSmallEntityDraws entity-draws meet in one call: they take different tile sizes)
 hipError_t launch_cull_fused_views(const FusedCullViews &all, const uint32_t *entity_draw_counts, uint32_t n,
-                                   uint32_t num_cus, hipStream_t s) {
+                                   uint32_t num_cus, hipStream_t s, uint32_t grid_cap) {
 #if !ORBIT_CONTRACT
-    if (all.v[0].m.arith != 0u) return launch_cull_fused_views_contracted(all, entity_draw_counts, n, num_cus, s);
+    if (all.v[0].m.arith != 0u) return launch_cull_fused_views_contracted(all, entity_draw_counts, n, num_cus, s, grid_cap);
 #endif
     // three shapes: 0 = the local entity stage (passes 0 / 1, at most kFusedLocalChunks chunks: 2-row tiles), 1 = 2-row
     // tiles, 2 = 8-row tiles
@@ -446,7 +446,8 @@ hipError_t launch_cull_fused_views(const FusedCullViews &all, const uint32_t *en
         }
         if (m == 0) continue;
         const uint32_t rows = shape == 2u ? 8u : 2u;
-        const dim3 grid(fused_grid(most, rows, num_cus, m), m), block(kEntityBlock);
+        const uint32_t sized = fused_grid(most, rows, num_cus, m);
+        const dim3 grid(grid_cap != 0u ? min(sized, grid_cap) : sized, m), block(kEntityBlock); // (the tickets make any grid right)
         if (shape == 0u) hipLaunchKernelGGL(cull_fused_local_views_kernel, grid, block, 0, s, all, g);
         else if (shape == 1u) hipLaunchKernelGGL((cull_fused_views_kernel<2>), grid, block, 0, s, all, g);
         else hipLaunchKernelGGL((cull_fused_views_kernel<8>), grid, block, 0, s, all, g);

@@ -268,8 +268,9 @@ struct FusedCullParams {
 struct FusedCullViews {
     FusedCullParams v[ORBIT_MAX_CULL_VIEWS];
 };
+// grid_cap: every launch's grid is at most this many workgroups per view (0 = as sized; orbit_ctx_set_fused_grid)
 hipError_t launch_cull_fused_views(const FusedCullViews &all, const uint32_t *entity_draw_counts, uint32_t n,
-                                   uint32_t num_cus, hipStream_t s);
+                                   uint32_t num_cus, hipStream_t s, uint32_t grid_cap = 0);
 // The shard launch of the sharded engine (orbit_cull_shard; meshlet_eval.hip): entity stage + evaluation + record list of
 // one pass-0 view in ONE launch — f.m as for a cull with visible_list == 2 (a bound stream is used), the entity side as
 // for the one-launch cull (f.tile_flags unused).  At most kShardMaxChunks chunks of 256 entity-draws: every chunk adds
@@ -319,7 +320,7 @@ hipError_t launch_meshlet_eval_views_contracted(const MeshletCullViews &all, con
                                                 bool ortho, int src, uint32_t max_tiles, uint32_t num_cus, hipStream_t s);
 hipError_t launch_shard_cull_contracted(const FusedCullParams &f, uint32_t num_cus, hipStream_t s);
 hipError_t launch_cull_fused_views_contracted(const FusedCullViews &all, const uint32_t *entity_draw_counts, uint32_t n,
-                                              uint32_t num_cus, hipStream_t s);
+                                              uint32_t num_cus, hipStream_t s, uint32_t grid_cap = 0);
 #endif
 hipError_t launch_entity_cull_views(const EntityCullViews &all, uint32_t n, uint32_t max_entity_draw_count,
                                     uint32_t num_cus, hipStream_t s);

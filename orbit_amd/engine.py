@@ -752,6 +752,11 @@ class Engine:
         grid; tests)."""
         _lib.check(self._lib.orbit_ctx_set_raster_grid(self._ctx, int(max_workgroups)), self._ctx)
 
+    def set_fused_grid(self, max_workgroups):
+        """orbit_ctx_set_fused_grid: at most that many workgroups per view for every launch of the one-launch cull behind
+        cull_views, read when the launch is enqueued (0 = as sized; tests)."""
+        _lib.check(self._lib.orbit_ctx_set_fused_grid(self._ctx, int(max_workgroups)), self._ctx)
+
     def exchange_list(self, local_list, rank, world, out_buffers, ctrl_buffers, out_capacity, header_bytes, stride,
                       stream=None):
         """orbit_exchange_list: the rank-ordered all-gather of the ranks' lists with counts and completion signalled on
