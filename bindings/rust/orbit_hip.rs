@@ -176,6 +176,29 @@ pub struct OrbitVisibilityCompact {
     pub visible_capacity: u32, pub visible_data_words: u32, pub flags: u32, pub _pad: u32,
 }
 
+pub const ORBIT_SURFACE_CLEAR: u32 = 1;
+
+/// The counters of orbit_visibility_surface (32 B, DEVICE, cleared by the call): covered = written + foreign +
+/// unsupported + stale
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitSurfaceStats {
+    pub covered_pixels: u32, pub written_pixels: u32, pub foreign_pixels: u32, pub unsupported_pixels: u32,
+    pub stale_pixels: u32, pub degenerate_pixels: u32, pub _pad: [u32; 2],
+}
+
+/// orbit_visibility_surface's argument block (184 B, HOST): DEVICE pointers; bary (2 f32 per pixel), grad (4 f32),
+/// triangle (4 u32) and stats may be null, not all three outputs
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitVisibilitySurface {
+    pub visibility: *const u64, pub draw_commands: *const c_void, pub meshlet_data: *const u32,
+    pub vertices: *const c_void, pub entity_data: *const c_void,
+    pub bary: *mut f32, pub grad: *mut f32, pub triangle: *mut u32, pub stats: *mut OrbitSurfaceStats,
+    pub meshlet_data_words: u64, pub vertex_count: u64,
+    pub max_commands: u32, pub entity_count: u32, pub vertex_stride: u32, pub position_offset: u32,
+    pub width: u32, pub height: u32, pub flags: u32, pub command_base: u32,
+    pub view_proj: [f32; 16],
+}
+
 /// orbit_visibility_resolve's argument block (48 B, HOST): DEVICE pointers; each output may be null, not all
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct OrbitVisibilityResolve {
@@ -391,6 +414,9 @@ extern "C" {
     pub fn orbit_visibility_compact_workspace(max_commands: u32) -> u64;
     /// The exact visible draw list of a visibility buffer, optionally cut down to the visible triangles (C1-C6).
     pub fn orbit_visibility_compact(ctx: *mut OrbitCtx, job: *const OrbitVisibilityCompact, stream: *mut c_void) -> i32;
+    /// Perspective-correct barycentrics, their one-pixel differences and the triangle's ids of every pixel the list owns
+    /// (S1-S7): what a renderer shades from, by the raster's own rules.
+    pub fn orbit_visibility_surface(ctx: *mut OrbitCtx, job: *const OrbitVisibilitySurface, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

@@ -1259,6 +1259,107 @@ uint64_t orbit_visibility_compact_workspace(uint32_t max_commands);
 /* the exact visible draw list of a visibility buffer; see above */
 int32_t orbit_visibility_compact(OrbitCtx *ctx, const OrbitVisibilityCompact *job, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* The surface of a visibility buffer.  orbit_visibility_surface reads a    */
+/* buffer and the list that made it and writes, for each pixel the list     */
+/* owns, the perspective-correct barycentrics of the sample in the owning   */
+/* triangle, their one-pixel differences, and the triangle's entity and     */
+/* three global vertices: what a renderer behind a compute-only part needs  */
+/* to shade, without restating R1-R6.  It uses the functions of the raster  */
+/* (raster_common.h), so a written pixel has 0 <= l1, l2 <= 1.  ONE         */
+/* definition for the device and the host mirror                            */
+/* (orbit_host_visibility_surface); the two agree on every byte of every    */
+/* output.  Float arithmetic as in R2-R7: fp32, round to nearest, every     */
+/* operation rounded on its own, never contracted, IEEE divides.            */
+/*  S1 decode: n = min(count, max_commands), the count read ON THE DEVICE.  */
+/*     A word of 0 is uncovered.  Otherwise id = (word >> 8) & 0xFFFFFF, t  */
+/*     = word & 255, k = id - command_base (u32, wrapping); k >= n is a     */
+/*     FOREIGN pixel (C1's rule, not the resolve's).  Uncovered and foreign */
+/*     pixels are not written: a frame's two lists are two calls with two   */
+/*     bases into the same outputs, the second without ORBIT_SURFACE_CLEAR. */
+/*  S2 consistency of (k, t): command k passes R9 WHOLE, as the drawing     */
+/*     call asked it (its ranges, its entity, every index word and every    */
+/*     corner byte; nothing is read before it is known to be in range) and  */
+/*     V3's nt <= 256, and t < nt.  The three corners then go               */
+/*     through R1-R4 (clip_position, vertex_from_clip; not R4w).  A vertex  */
+/*     failing R3 or R4's guard makes the pixel UNSUPPORTED: what a buffer  */
+/*     drawn with ORBIT_RASTER_CLIP_NEAR or ORBIT_RASTER_WIDE_GUARD         */
+/*     legitimately holds; the status stays OK.  THE PIECES OF R3c AND THE  */
+/*     WIDE TRIANGLES OF R4w ARE OUT OF SCOPE.  Otherwise R5-R7's setup     */
+/*     runs with the facing not asked (it was the drawing call's decision). */
+/*     The pixel is STALE, and ORBIT_E_RANGE is latched, if a check above   */
+/*     failed, the setup does not draw (A == 0, an empty box), the sample   */
+/*     (256 x + 128, 256 y + 128) is not inside (R6, top-left rule), or R7's */
+/*     d there is not > 0 or its bits differ from the word's high half.     */
+/*     Unsupported and stale pixels are not written.                        */
+/*  S3 barycentrics B(px, py), defined for any sample: with R5's normalised */
+/*     vertices (A > 0, 1 and 2 possibly swapped) and edges j = 0, 1, 2     */
+/*     from vertex j to vertex j + 1, E_j = dx_j * (py - Y_j) - dy_j * (px  */
+/*     - X_j) in int64 (R6's E WITHOUT the top-left bias; E_0 + E_1 + E_2 = */
+/*     A); e_j = (float)(double)E_j; iw_j = 1.0f / w_j (R2's clip w);       */
+/*     q0 = e1 * iw0; q1 = e2 * iw1; q2 = e0 * iw2; s = (q0 + q1) + q2;     */
+/*     l1 = q1 / s; l2 = q2 / s; if R5 swapped, l1 and l2 are exchanged:    */
+/*     bary[p] = (l1, l2) refers to the corner order in meshlet_data, and   */
+/*     l0 is the consumer's 1 - l1 - l2.                                    */
+/*  S4 differences: grad[p] = (B(px + 256, py) - B(px, py), B(px, py + 256) */
+/*     - B(px, py)) as (dl1/dx, dl2/dx, dl1/dy, dl2/dy): the same triangle  */
+/*     at the neighbouring sample, as a quad derivative is.  An axis whose  */
+/*     neighbour has !(s > 0) gives (0, 0).                                 */
+/*  S5 no non-finite bytes: any of the six floats that is not finite is     */
+/*     written as +0.0f (a generated NaN's sign and payload differ between  */
+/*     processors).  A pixel with such a float, or with an axis zeroed by   */
+/*     S4, counts once in degenerate_pixels; it is still written and still  */
+/*     counted in written_pixels.  All six floats are evaluated whichever   */
+/*     outputs are given: no counter depends on a NULL output.              */
+/*  S6 triangle[p] = (entity, g0, g1, g2): cmd_first_instance and R1's      */
+/*     global vertices in meshlet_data's corner order.                      */
+/*  S7 ORBIT_SURFACE_CLEAR first fills the given outputs: bary and grad     */
+/*     with +0.0f, triangle with 0xFFFFFFFF.  stats (may be NULL) is        */
+/*     cleared by the call; covered_pixels = written + foreign +            */
+/*     unsupported + stale.  Every output depends on its own pixel only:    */
+/*     independent of scheduling.                                           */
+/*   ORBIT_E_INVALID  job, visibility, draw_commands, meshlet_data,         */
+/*                    vertices or entity_data NULL; bary, grad and triangle */
+/*                    all NULL; a pointer misaligned (visibility: 8 B,      */
+/*                    entity_data: 16 B, the rest: 4 B); vertex_stride <    */
+/*                    position_offset + 12, stride or offset no multiple of */
+/*                    4; width or height 0 or above ORBIT_RASTER_MAX_DIM;   */
+/*                    command_base + max_commands > ORBIT_VIS_MAX_COMMANDS; */
+/*                    triangle given with vertex_count > 2^32; unknown      */
+/*                    flags (the raster's flag values among them)           */
+/* No allocation, no scratch, no host wait, kernel nodes only: a graph      */
+/* captures the call on a fresh context's first call.                       */
+/* ------------------------------------------------------------------------ */
+#define ORBIT_SURFACE_CLEAR 1u /* flags: fill the given outputs first (S7) */
+typedef struct OrbitSurfaceStats { /* DEVICE, 32 B, cleared by the call */
+    uint32_t covered_pixels, written_pixels, foreign_pixels, unsupported_pixels, stale_pixels, degenerate_pixels, _pad[2];
+} OrbitSurfaceStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitSurfaceStats) == 32, "SurfaceStats is 32 B");
+typedef struct OrbitVisibilitySurface { /* HOST block, 184 B; every pointer a DEVICE pointer */
+    const uint64_t *visibility;         /* width * height u64, as orbit_raster_visibility left it */
+    const void *draw_commands;          /* the list that was rasterised with this command_base; the rest as OrbitRasterVisibility */
+    const uint32_t *meshlet_data;
+    const void *vertices;
+    const OrbitEntityData *entity_data;
+    float *bary;                        /* NULL, or 2 floats per pixel: (l1, l2) */
+    float *grad;                        /* NULL, or 4 floats per pixel: (dl1/dx, dl2/dx, dl1/dy, dl2/dy) */
+    uint32_t *triangle;                 /* NULL, or 4 words per pixel: (entity, g0, g1, g2) */
+    OrbitSurfaceStats *stats;           /* NULL, or the counters */
+    uint64_t meshlet_data_words, vertex_count;
+    uint32_t max_commands, entity_count, vertex_stride, position_offset, width, height, flags, command_base;
+    float view_proj[16];
+} OrbitVisibilitySurface;
+ORBIT_STATIC_ASSERT(sizeof(OrbitVisibilitySurface) == 184, "VisibilitySurface is 184 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilitySurface, bary) == 40, "bary @40");
+ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilitySurface, stats) == 64, "stats @64");
+ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilitySurface, meshlet_data_words) == 72, "meshlet_data_words @72");
+ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilitySurface, max_commands) == 88, "max_commands @88");
+ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilitySurface, command_base) == 116, "command_base @116");
+ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilitySurface, view_proj) == 120, "view_proj @120");
+
+/* barycentrics, their differences and the triangle's ids of every pixel the list owns; see above */
+int32_t orbit_visibility_surface(OrbitCtx *ctx, const OrbitVisibilitySurface *job, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,19 @@ class VisibilityCompact(C.Structure):  # OrbitVisibilityCompact (120 B)
 COMPACT_TRIANGLES = 1  # ORBIT_COMPACT_TRIANGLES
 
 
+class VisibilitySurface(C.Structure):  # OrbitVisibilitySurface (184 B)
+    _fields_ = [("visibility", C.c_void_p), ("draw_commands", C.c_void_p), ("meshlet_data", C.c_void_p),
+                ("vertices", C.c_void_p), ("entity_data", C.c_void_p), ("bary", C.c_void_p), ("grad", C.c_void_p),
+                ("triangle", C.c_void_p), ("stats", C.c_void_p), ("meshlet_data_words", C.c_uint64),
+                ("vertex_count", C.c_uint64), ("max_commands", C.c_uint32), ("entity_count", C.c_uint32),
+                ("vertex_stride", C.c_uint32), ("position_offset", C.c_uint32), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("flags", C.c_uint32), ("command_base", C.c_uint32),
+                ("view_proj", C.c_float * 16)]
+
+
+SURFACE_CLEAR = 1  # ORBIT_SURFACE_CLEAR
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -235,6 +248,7 @@ SYMBOLS = {
     "orbit_visibility_resolve": (C.c_int32, [C.c_void_p, C.POINTER(VisibilityResolve), C.c_void_p]),
     "orbit_visibility_compact_workspace": (C.c_uint64, [C.c_uint32]),
     "orbit_visibility_compact": (C.c_int32, [C.c_void_p, C.POINTER(VisibilityCompact), C.c_void_p]),
+    "orbit_visibility_surface": (C.c_int32, [C.c_void_p, C.POINTER(VisibilitySurface), C.c_void_p]),
 }
 
 _lib = None

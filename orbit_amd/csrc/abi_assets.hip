@@ -2,7 +2,8 @@
 // orbit_mesh_bounds, the refit of Meshlet and MeshInfo bounds on the device (meshlet_bounds.hip), orbit_raster_depth,
 // the depth prepass of the draw commands in compute (raster_depth.hip), and orbit_raster_visibility with
 // orbit_visibility_resolve, the same pass keeping the winner's identity and its resolve (raster_visibility.hip), and
-// orbit_visibility_compact, the visible draw list of such a buffer (visibility_compact.hip).
+// orbit_visibility_compact, the visible draw list of such a buffer (visibility_compact.hip), and
+// orbit_visibility_surface, its barycentrics, differences and ids per pixel (visibility_surface.hip).
 #include "abi_internal.h"
 
 namespace {
@@ -189,6 +190,36 @@ int32_t orbit_visibility_compact(OrbitCtx *ctx, const OrbitVisibilityCompact *jo
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_visibility_compact(j, ctx->num_cus, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_compact");
+    return ORBIT_OK;
+}
+
+// A clearing launch (stats, and the outputs with ORBIT_SURFACE_CLEAR) and the surface launch; the command count stays on
+// the device.  No allocation, no scratch, no host sync: capturable on the first call.  As orbit_visibility_compact, the job
+// is checked before the context is looked at, each error with a message of its own: a NULL context is the last error.
+int32_t orbit_visibility_surface(OrbitCtx *ctx, const OrbitVisibilitySurface *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "visibility_surface: job is NULL");
+    const OrbitVisibilitySurface &j = *job;
+    if (j.flags & ~ORBIT_SURFACE_CLEAR) return fail(ctx, ORBIT_E_INVALID, "visibility_surface: flags %#x", j.flags);
+    if (const int32_t rc = check_vertex_layout(ctx, "visibility_surface", j.vertex_stride, j.position_offset)) return rc;
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "visibility_surface: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS)
+        return fail(ctx, ORBIT_E_INVALID, "visibility_surface: command_base %u + max_commands %u > %u (24 bits of id)",
+                    j.command_base, j.max_commands, ORBIT_VIS_MAX_COMMANDS);
+    if (!j.visibility || !j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data)
+        return fail(ctx, ORBIT_E_INVALID, "visibility_surface: NULL buffer");
+    if (!j.bary && !j.grad && !j.triangle) return fail(ctx, ORBIT_E_INVALID, "visibility_surface: no output");
+    if (j.triangle && j.vertex_count > (1ull << 32))
+        return fail(ctx, ORBIT_E_INVALID, "visibility_surface: triangle with vertex_count %llu > 2^32 (a global vertex is a u32)",
+                    (unsigned long long)j.vertex_count);
+    if (((uintptr_t)j.visibility & 7u) || ((uintptr_t)j.entity_data & 15u) ||
+        (((uintptr_t)j.draw_commands | (uintptr_t)j.meshlet_data | (uintptr_t)j.vertices | (uintptr_t)j.bary | (uintptr_t)j.grad |
+          (uintptr_t)j.triangle | (uintptr_t)j.stats) & 3u))
+        return fail(ctx, ORBIT_E_INVALID, "visibility_surface: visibility must be 8-B aligned, entity_data 16-B aligned, every other buffer 4-B aligned");
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "visibility_surface: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_visibility_surface(j, ctx->num_cus, ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_surface");
     return ORBIT_OK;
 }
 

@@ -434,6 +434,9 @@ inline uint64_t visibility_compact_workspace_bytes(uint32_t max_commands) {
     return (((uint64_t)max_commands + kCompactChunk - 1u) / kCompactChunk + 1u) * kCompactCarryBytes;
 }
 hipError_t launch_visibility_compact(const OrbitVisibilityCompact &job, uint32_t num_cus, int32_t *status, hipStream_t s);
+// visibility_surface.hip: orbit_visibility_surface — `job` validated by the entry point.  One launch clears stats and, with
+// ORBIT_SURFACE_CLEAR, fills the outputs; the next reads every word once, a wave per 8 x 8 tile
+hipError_t launch_visibility_surface(const OrbitVisibilitySurface &job, uint32_t num_cus, int32_t *status, hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

@@ -433,6 +433,33 @@ class Engine:
         j.flags = _lib.COMPACT_TRIANGLES if triangles else 0
         _lib.check(self._lib.orbit_visibility_compact(self._ctx, C.byref(j), _stream(stream)), self._ctx)
 
+    # -- barycentrics, their differences and ids per pixel of a visibility buffer (orbit_visibility_surface)
+    def visibility_surface(self, visibility, width, height, draw_commands, max_commands, meshlet_data, vertices, vertex_count,
+                           entity_data, entity_count, view_proj, bary=None, grad=None, triangle=None, stats=None,
+                           command_base=0, clear=False, vertex_stride=12, position_offset=0, meshlet_data_words=None,
+                           stream=None):
+        """From the width x height u64 tensor `visibility` and the list that was rasterised into it with `command_base`
+        (the arguments of raster_visibility) to what a renderer shades from, for every pixel the list owns: bary (2
+        floats per pixel: the perspective-correct l1, l2 of the sample in the owning triangle, in meshlet_data's corner
+        order; l0 = 1 - l1 - l2), grad (4 floats: their differences to the samples one pixel right and one pixel down, as
+        dl1/dx, dl2/dx, dl1/dy, dl2/dy) and triangle (4 u32: entity, three global vertices).  Each may be None, not all.
+        Uncovered pixels, pixels of another list, and pixels of a near-cut or wide triangle (unsupported_pixels) are not
+        written; clear=True (ORBIT_SURFACE_CLEAR) fills the outputs first (0.0, 0xFFFFFFFF).  stats (32 bytes,
+        layouts.SURFACE_STATS, cleared by the call).  A pixel that the list cannot have drawn is counted in stale_pixels
+        and reported by status() (ORBIT_E_RANGE).  Byte-equal to orbit_amd.raster.host_visibility_surface.  Enqueued
+        on `stream`."""
+        nbytes = lambda t: 0 if t is None or isinstance(t, int) else t.numel() * t.element_size()  # noqa: E731
+        j = _lib.VisibilitySurface()
+        j.visibility, j.draw_commands, j.meshlet_data = _ptr(visibility), _ptr(draw_commands), _ptr(meshlet_data)
+        j.vertices, j.entity_data = _ptr(vertices), _ptr(entity_data)
+        j.bary, j.grad, j.triangle, j.stats = _ptr(bary), _ptr(grad), _ptr(triangle), _ptr(stats)
+        j.meshlet_data_words = nbytes(meshlet_data) // 4 if meshlet_data_words is None else int(meshlet_data_words)
+        j.vertex_count, j.max_commands, j.entity_count = int(vertex_count), int(max_commands), int(entity_count)
+        j.vertex_stride, j.position_offset, j.width, j.height = int(vertex_stride), int(position_offset), int(width), int(height)
+        j.flags, j.command_base = _lib.SURFACE_CLEAR if clear else 0, int(command_base)
+        j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
+        _lib.check(self._lib.orbit_visibility_surface(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                    entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,

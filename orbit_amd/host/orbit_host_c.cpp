@@ -604,6 +604,13 @@ int32_t orbit_host_visibility_compact(const OrbitVisibilityCompact *job, int32_t
     });
 }
 
+int32_t orbit_host_visibility_surface(const OrbitVisibilitySurface *job, int32_t *status) {
+    return guarded([&] {
+        if (!job) throw Panic("visibility_surface: job is NULL");
+        raster::visibility_surface(*job, status);
+    });
+}
+
 // ---------------------------------------------------------------- asset ingestion (orbit_gltf.hpp), host only
 void *orbit_host_gltf_load(const char *path) {
     gltf_loader::LoadedScene *scene = nullptr;

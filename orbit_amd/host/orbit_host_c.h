@@ -248,6 +248,10 @@ int32_t orbit_host_visibility_resolve(const uint64_t *visibility, uint32_t width
  * ORBIT_E_RANGE before ORBIT_E_CAPACITY before ORBIT_OK.  ORBIT_HOST_PANIC for what the device answers with
  * ORBIT_E_INVALID (alignment and the workspace aside). */
 int32_t orbit_host_visibility_compact(const OrbitVisibilityCompact *job, int32_t *status);
+/* the reference of orbit_visibility_surface (S1-S7): the device call's block with HOST pointers in it.  Every output
+ * holds the device's bytes.  *status (may be NULL): ORBIT_E_RANGE if a pixel was stale, else ORBIT_OK.  ORBIT_HOST_PANIC
+ * for what the device answers with ORBIT_E_INVALID (alignment aside). */
+int32_t orbit_host_visibility_surface(const OrbitVisibilitySurface *job, int32_t *status);
 
 /* ---- asset ingestion (orbit_gltf.hpp): glTF 2.0 (.glb / .gltf) -> materials, meshes with their LOD chains, entities ----
  * load_gltf (gltf_loader.rs:511-676) + GpuAssets::add_mesh (assets/mod.rs:325-476).  NULL + orbit_host_last_error()

@@ -46,5 +46,10 @@ void visibility_resolve(const uint64_t *visibility, uint32_t width, uint32_t hei
 // scan, which finds the first, runs before the emit, which finds the second).  Throws Panic for ORBIT_E_INVALID.
 void visibility_compact(const OrbitVisibilityCompact &job, int32_t *status);
 
+// orbit_visibility_surface (S1-S7, §4.21) on host buffers: the job's pointers are HOST pointers.  The obvious loop over
+// the pixels, each through ../csrc/surface_common.h.  *status (may be null) = what the device call latches: ORBIT_E_RANGE
+// if a pixel was stale, else ORBIT_OK.  Throws Panic for ORBIT_E_INVALID.
+void visibility_surface(const OrbitVisibilitySurface &job, int32_t *status);
+
 } // namespace raster
 } // namespace orbit

@@ -64,6 +64,9 @@ VIS_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "visible_commands",
 VIS_COMPACT_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "foreign_pixels", "visible_commands",
                                                    "visible_triangles", "written_commands", "dropped_commands",
                                                    "data_words_needed", "range_errors")])
+# OrbitSurfaceStats: the counters of orbit_visibility_surface
+SURFACE_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "written_pixels", "foreign_pixels", "unsupported_pixels",
+                                               "stale_pixels", "degenerate_pixels", "_pad0", "_pad1")])
 # types.glsl:92-110, src/assets/mod.rs:171-191
 MATERIAL = np.dtype([
     ("base_color", "<f4", (4,)), ("emissive_factor", "<f4", (3,)), ("metallic_factor", "<f4"),

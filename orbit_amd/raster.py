@@ -2,7 +2,9 @@
 ``orbit_visibility_resolve`` (``orbit_amd/host/orbit_raster.hpp``): the depth prepass of a MeshletDrawCommandBuffer on
 host arrays, the same pass keeping the winner's identity and its resolve — the references of ``Engine.raster_depth``,
 ``Engine.raster_visibility`` and ``Engine.visibility_resolve`` — and of ``orbit_visibility_compact``, the visible draw
-list of such a buffer, the reference of ``Engine.visibility_compact``.  Python adds nothing; host only."""
+list of such a buffer, the reference of ``Engine.visibility_compact``, and of ``orbit_visibility_surface``, the
+barycentrics and ids per pixel of such a buffer, the reference of ``Engine.visibility_surface``.  Python adds nothing;
+host only."""
 import ctypes as C
 
 import numpy as np
@@ -131,3 +133,46 @@ def host_visibility_compact(visibility, draw_commands, max_commands, command_bas
     _check(lib().orbit_host_visibility_compact(C.byref(j), C.byref(status)))
     return dict(masks=masks[:8 * int(max_commands)], commands=out[:1 + 7 * cap], ids=None if ids is None else ids[:cap],
                 data=None if vdata is None else vdata[:words], stats=stats[0], status=status.value)
+
+
+def host_visibility_surface(visibility, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data,
+                            view_proj, command_base=0, clear=True, into=None, want=("bary", "grad", "triangle"),
+                            vertex_stride=12, position_offset=0, entity_count=None, meshlet_data_words=None, fill=0,
+                            want_stats=True):
+    """orbit_host_visibility_surface on a (height, width) np.uint64 buffer and the arguments of host_raster_visibility
+    that made it -> dict(bary: np.float32 (height, width, 2), grad: np.float32 (height, width, 4), triangle: np.uint32
+    (height, width, 4), each None unless named in `want`; stats: np[layouts.SURFACE_STATS] scalar row or None; status:
+    what the device call latches).  `into`: the dict of an earlier call to write into (copied): a frame's second list,
+    clear=False.  Otherwise every output starts filled with the u32 `fill`: what the call does not write keeps it."""
+    vis = np.ascontiguousarray(visibility, dtype=np.uint64)
+    height, width = vis.shape
+    buf = np.ascontiguousarray(draw_commands).view(np.uint8).reshape(-1)
+    if buf.nbytes < 4 + 28 * int(max_commands):
+        raise ValueError("max_commands reaches beyond the command array")
+    data = np.ascontiguousarray(meshlet_data, dtype=np.uint32).reshape(-1)
+    vb = np.ascontiguousarray(vertices).view(np.uint8).reshape(-1)
+    if int(vertex_count) and (int(vertex_count) - 1) * int(vertex_stride) + int(position_offset) + 12 > vb.nbytes:
+        raise ValueError("vertex_count reaches beyond the vertex array")
+    ent = np.ascontiguousarray(entity_data).view(np.uint8).reshape(-1)
+    outs = {}
+    for name, per_pixel, dtype in (("bary", 2, np.float32), ("grad", 4, np.float32), ("triangle", 4, np.uint32)):
+        if name not in want:
+            outs[name] = None
+        elif into is not None:
+            outs[name] = np.array(into[name], dtype=dtype, order="C").reshape(height, width, per_pixel)
+        else:
+            outs[name] = np.full((height, width, per_pixel), fill, np.uint32).view(dtype)
+    stats = np.zeros(1, L.SURFACE_STATS) if want_stats else None
+    p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    j = _lib.VisibilitySurface()
+    j.visibility, j.draw_commands, j.meshlet_data, j.vertices, j.entity_data = p(vis), p(buf), p(data), p(vb), p(ent)
+    j.bary, j.grad, j.triangle, j.stats = p(outs["bary"]), p(outs["grad"]), p(outs["triangle"]), p(stats)
+    j.meshlet_data_words = len(data) if meshlet_data_words is None else int(meshlet_data_words)
+    j.vertex_count, j.max_commands = int(vertex_count), int(max_commands)
+    j.entity_count = ent.nbytes // 128 if entity_count is None else int(entity_count)
+    j.vertex_stride, j.position_offset, j.width, j.height = int(vertex_stride), int(position_offset), width, height
+    j.flags, j.command_base = _lib.SURFACE_CLEAR if clear else 0, int(command_base)
+    j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
+    status = C.c_int32(0)
+    _check(lib().orbit_host_visibility_surface(C.byref(j), C.byref(status)))
+    return dict(outs, stats=None if stats is None else stats[0], status=status.value)
