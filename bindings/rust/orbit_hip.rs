@@ -341,6 +341,7 @@ extern "C" {
     pub fn orbit_ctx_set_block_cull(ctx: *mut OrbitCtx, enable: u32) -> i32;
     pub fn orbit_ctx_set_block_cull_grid(ctx: *mut OrbitCtx, max_workgroups: u32) -> i32;
     pub fn orbit_ctx_set_raster_grid(ctx: *mut OrbitCtx, max_workgroups: u32) -> i32;
+    pub fn orbit_ctx_set_visibility_grid(ctx: *mut OrbitCtx, max_workgroups: u32) -> i32;
     pub fn orbit_ctx_set_fused_grid(ctx: *mut OrbitCtx, max_workgroups: u32) -> i32;
     pub fn orbit_meshlet_stream_block_bounds(ctx: *mut OrbitCtx, ms: *mut OrbitMeshletStream, first_block: u64, count: u64,
                                              out: *mut c_void, stream: *mut c_void) -> i32;

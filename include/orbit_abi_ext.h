@@ -235,6 +235,13 @@ int32_t orbit_ctx_set_raster_grid(OrbitCtx *ctx, uint32_t max_workgroups);
  * prepared call follows it too.  0, the default, restores the sized grid.  The outputs do not depend on the grid; the
  * shard launch and every other launch are not touched. */
 int32_t orbit_ctx_set_fused_grid(OrbitCtx *ctx, uint32_t max_workgroups);
+/* Tests: the strided launches of the visibility buffer's three readers — orbit_visibility_resolve's clear and its tile
+ * walk, orbit_visibility_compact's clear and its mark, orbit_visibility_surface's clear and its tile walk — take at most
+ * `max_workgroups` workgroups (of four waves; a wave takes its 8 x 8 tiles one after another, so under a cap of c wave g
+ * takes tiles g, g + 4c, ... of even a small target).  Read when the call is enqueued: a captured launch carries its
+ * grid.  0, the default, restores num_cus * 8.  The outputs do not depend on the grid; the compaction's scan, totals and
+ * emit, sized per chunk of commands, and every other launch are not touched. */
+int32_t orbit_ctx_set_visibility_grid(OrbitCtx *ctx, uint32_t max_workgroups);
 /* Tests: the bounds of blocks [first_block, first_block + count) (block = global meshlet index / 32) into the HOST
  * array `out`, 32 B each: {float centre[3], centre_radius, max_radius; uint32_t valid, pad[2]}.  Waits for `stream`. */
 int32_t orbit_meshlet_stream_block_bounds(OrbitCtx *ctx, OrbitMeshletStream *ms, uint64_t first_block, uint64_t count,

@@ -221,6 +221,7 @@ SYMBOLS = {
     "orbit_ctx_set_block_cull": (C.c_int32, [C.c_void_p, C.c_uint32]),
     "orbit_ctx_set_block_cull_grid": (C.c_int32, [C.c_void_p, C.c_uint32]),
     "orbit_ctx_set_raster_grid": (C.c_int32, [C.c_void_p, C.c_uint32]),
+    "orbit_ctx_set_visibility_grid": (C.c_int32, [C.c_void_p, C.c_uint32]),
     "orbit_ctx_set_fused_grid": (C.c_int32, [C.c_void_p, C.c_uint32]),
     "orbit_meshlet_stream_block_bounds": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                                       C.c_void_p]),

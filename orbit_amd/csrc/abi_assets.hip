@@ -152,7 +152,7 @@ int32_t orbit_visibility_resolve(OrbitCtx *ctx, const OrbitVisibilityResolve *jo
     if (((uintptr_t)j.depth | (uintptr_t)j.command_pixels | (uintptr_t)j.stats) & 3u)
         return fail(ctx, ORBIT_E_INVALID, "visibility_resolve: every output must be 4-B aligned");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_visibility_resolve(j, ctx->num_cus, (hipStream_t)stream);
+    const hipError_t e = launch_visibility_resolve(j, ctx->num_cus, ctx->visibility_grid, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_resolve");
     return ORBIT_OK;
 }
@@ -188,7 +188,7 @@ int32_t orbit_visibility_compact(OrbitCtx *ctx, const OrbitVisibilityCompact *jo
                     (unsigned long long)visibility_compact_workspace_bytes(j.max_commands));
     if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "visibility_compact: ctx is NULL");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_visibility_compact(j, ctx->num_cus, ctx->status, (hipStream_t)stream);
+    const hipError_t e = launch_visibility_compact(j, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_compact");
     return ORBIT_OK;
 }
@@ -218,7 +218,7 @@ int32_t orbit_visibility_surface(OrbitCtx *ctx, const OrbitVisibilitySurface *jo
         return fail(ctx, ORBIT_E_INVALID, "visibility_surface: visibility must be 8-B aligned, entity_data 16-B aligned, every other buffer 4-B aligned");
     if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "visibility_surface: ctx is NULL");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_visibility_surface(j, ctx->num_cus, ctx->status, (hipStream_t)stream);
+    const hipError_t e = launch_visibility_surface(j, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_surface");
     return ORBIT_OK;
 }

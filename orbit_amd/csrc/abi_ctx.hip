@@ -236,6 +236,13 @@ int32_t orbit_ctx_set_fused_grid(OrbitCtx *ctx, uint32_t max_workgroups) {
     return ORBIT_OK;
 }
 
+int32_t orbit_ctx_set_visibility_grid(OrbitCtx *ctx, uint32_t max_workgroups) {
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->visibility_grid = max_workgroups;
+    return ORBIT_OK;
+}
+
 int32_t orbit_ctx_status(OrbitCtx *ctx, void *stream, int32_t sync) {
     if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ctx is NULL");
     std::lock_guard<std::mutex> lock(ctx->mu);

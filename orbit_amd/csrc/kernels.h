@@ -424,8 +424,10 @@ template <RasterVariant V>
 uint32_t raster_depth_blocks_per_cu();
 template <RasterVariant V>
 uint32_t raster_visibility_blocks_per_cu();
-// ... and orbit_visibility_resolve: one launch clears command_pixels and stats, the next reads every word once
-hipError_t launch_visibility_resolve(const OrbitVisibilityResolve &job, uint32_t num_cus, hipStream_t s);
+// ... and orbit_visibility_resolve: one launch clears command_pixels and stats, the next reads every word once.  Both
+// stride over their work from min(need, num_cus * 8) workgroups, and from `grid_cap` at most where it is not 0
+// (orbit_ctx_set_visibility_grid); the same holds for the strided launches of the two calls below
+hipError_t launch_visibility_resolve(const OrbitVisibilityResolve &job, uint32_t num_cus, uint32_t grid_cap, hipStream_t s);
 // visibility_compact.hip: orbit_visibility_compact — `job` validated by the entry point.  Five launches: clear, mark, and
 // with max_commands > 0 scan, totals, emit.  The workspace holds one 16-B slot per kCompactChunk commands (a block of
 // the scan and the emit) and one more for the sums: what orbit_visibility_compact_workspace answers.
@@ -433,10 +435,13 @@ constexpr uint32_t kCompactChunk = 256, kCompactCarryBytes = 16;
 inline uint64_t visibility_compact_workspace_bytes(uint32_t max_commands) {
     return (((uint64_t)max_commands + kCompactChunk - 1u) / kCompactChunk + 1u) * kCompactCarryBytes;
 }
-hipError_t launch_visibility_compact(const OrbitVisibilityCompact &job, uint32_t num_cus, int32_t *status, hipStream_t s);
+// (grid_cap: clear and mark; scan, totals and emit are sized per chunk)
+hipError_t launch_visibility_compact(const OrbitVisibilityCompact &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
+                                     hipStream_t s);
 // visibility_surface.hip: orbit_visibility_surface — `job` validated by the entry point.  One launch clears stats and, with
 // ORBIT_SURFACE_CLEAR, fills the outputs; the next reads every word once, a wave per 8 x 8 tile
-hipError_t launch_visibility_surface(const OrbitVisibilitySurface &job, uint32_t num_cus, int32_t *status, hipStream_t s);
+hipError_t launch_visibility_surface(const OrbitVisibilitySurface &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
+                                     hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

@@ -120,8 +120,9 @@ __global__ __launch_bounds__(kResolveThreads) void visibility_resolve_kernel(con
 
 } // namespace
 
-hipError_t launch_visibility_resolve(const OrbitVisibilityResolve &job, uint32_t num_cus, hipStream_t s) {
-    const uint32_t cap = (num_cus ? num_cus : 64u) * 8u;
+hipError_t launch_visibility_resolve(const OrbitVisibilityResolve &job, uint32_t num_cus, uint32_t grid_cap, hipStream_t s) {
+    const uint32_t resident = (num_cus ? num_cus : 64u) * 8u;
+    const uint32_t cap = grid_cap != 0u && grid_cap < resident ? grid_cap : resident; // orbit_ctx_set_visibility_grid
     if (job.stats || (job.command_pixels && job.max_commands != 0u)) {
         const uint32_t need = job.command_pixels ? (job.max_commands + kResolveThreads * 4u - 1u) / (kResolveThreads * 4u) : 1u;
         hipLaunchKernelGGL(resolve_clear_kernel, dim3(need < 1u ? 1u : need < cap ? need : cap), dim3(kResolveThreads), 0, s,

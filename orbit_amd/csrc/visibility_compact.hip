@@ -278,8 +278,10 @@ __global__ __launch_bounds__(kThreads) void compact_emit_kernel(const OrbitVisib
 
 } // namespace
 
-hipError_t launch_visibility_compact(const OrbitVisibilityCompact &job, uint32_t num_cus, int32_t *status, hipStream_t s) {
-    const uint32_t cap = (num_cus ? num_cus : 64u) * 8u;
+hipError_t launch_visibility_compact(const OrbitVisibilityCompact &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
+                                     hipStream_t s) {
+    const uint32_t resident = (num_cus ? num_cus : 64u) * 8u;
+    const uint32_t cap = grid_cap != 0u && grid_cap < resident ? grid_cap : resident; // orbit_ctx_set_visibility_grid
     const uint32_t blocks = (job.max_commands + kChunk - 1u) / kChunk; // max_commands <= 2^24: at most 65536
     {
         // 8 * max_commands <= 2^27 mask words

@@ -164,8 +164,10 @@ __global__ __launch_bounds__(kThreads) void surface_kernel(const OrbitVisibility
 
 } // namespace
 
-hipError_t launch_visibility_surface(const OrbitVisibilitySurface &job, uint32_t num_cus, int32_t *status, hipStream_t s) {
-    const uint32_t cap = (num_cus ? num_cus : 64u) * 8u;
+hipError_t launch_visibility_surface(const OrbitVisibilitySurface &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
+                                     hipStream_t s) {
+    const uint32_t resident = (num_cus ? num_cus : 64u) * 8u;
+    const uint32_t cap = grid_cap != 0u && grid_cap < resident ? grid_cap : resident; // orbit_ctx_set_visibility_grid
     const size_t pixels = (size_t)job.width * job.height; // width, height <= 32768: at most 2^30
     const bool fill = (job.flags & ORBIT_SURFACE_CLEAR) != 0u;
     if (fill || job.stats) {

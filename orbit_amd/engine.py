@@ -784,6 +784,12 @@ class Engine:
         cull_views, read when the launch is enqueued (0 = as sized; tests)."""
         _lib.check(self._lib.orbit_ctx_set_fused_grid(self._ctx, int(max_workgroups)), self._ctx)
 
+    def set_visibility_grid(self, max_workgroups):
+        """orbit_ctx_set_visibility_grid: at most that many workgroups for the strided launches of visibility_resolve,
+        visibility_compact (clear and mark) and visibility_surface, read when the call is enqueued (0 = num_cus * 8;
+        tests)."""
+        _lib.check(self._lib.orbit_ctx_set_visibility_grid(self._ctx, int(max_workgroups)), self._ctx)
+
     def exchange_list(self, local_list, rank, world, out_buffers, ctrl_buffers, out_capacity, header_bytes, stride,
                       stream=None):
         """orbit_exchange_list: the rank-ordered all-gather of the ranks' lists with counts and completion signalled on
