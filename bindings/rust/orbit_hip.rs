@@ -179,11 +179,12 @@ pub struct OrbitVisibilityCompact {
 pub const ORBIT_SURFACE_CLEAR: u32 = 1;
 
 /// The counters of orbit_visibility_surface (32 B, DEVICE, cleared by the call): covered = written + foreign +
-/// unsupported + stale
+/// unsupported + stale.  cut_pixels and wide_pixels are orbit_visibility_surface_drawn's (written from a piece of a
+/// near-cut triangle, from a wide setup); orbit_visibility_surface leaves them 0
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct OrbitSurfaceStats {
     pub covered_pixels: u32, pub written_pixels: u32, pub foreign_pixels: u32, pub unsupported_pixels: u32,
-    pub stale_pixels: u32, pub degenerate_pixels: u32, pub _pad: [u32; 2],
+    pub stale_pixels: u32, pub degenerate_pixels: u32, pub cut_pixels: u32, pub wide_pixels: u32,
 }
 
 /// orbit_visibility_surface's argument block (184 B, HOST): DEVICE pointers; bary (2 f32 per pixel), grad (4 f32),
@@ -418,6 +419,7 @@ extern "C" {
     /// Perspective-correct barycentrics, their one-pixel differences and the triangle's ids of every pixel the list owns
     /// (S1-S7): what a renderer shades from, by the raster's own rules.
     pub fn orbit_visibility_surface(ctx: *mut OrbitCtx, job: *const OrbitVisibilitySurface, stream: *mut c_void) -> i32;
+    pub fn orbit_visibility_surface_drawn(ctx: *mut OrbitCtx, job: *const OrbitVisibilitySurface, raster_flags: u32, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

@@ -1339,7 +1339,8 @@ int32_t orbit_visibility_compact(OrbitCtx *ctx, const OrbitVisibilityCompact *jo
 /* ------------------------------------------------------------------------ */
 #define ORBIT_SURFACE_CLEAR 1u /* flags: fill the given outputs first (S7) */
 typedef struct OrbitSurfaceStats { /* DEVICE, 32 B, cleared by the call */
-    uint32_t covered_pixels, written_pixels, foreign_pixels, unsupported_pixels, stale_pixels, degenerate_pixels, _pad[2];
+    uint32_t covered_pixels, written_pixels, foreign_pixels, unsupported_pixels, stale_pixels, degenerate_pixels;
+    uint32_t cut_pixels, wide_pixels; /* orbit_visibility_surface_drawn only: written from a piece of R3c, from a wide setup; else 0 */
 } OrbitSurfaceStats;
 ORBIT_STATIC_ASSERT(sizeof(OrbitSurfaceStats) == 32, "SurfaceStats is 32 B");
 typedef struct OrbitVisibilitySurface { /* HOST block, 184 B; every pointer a DEVICE pointer */
@@ -1366,6 +1367,77 @@ ORBIT_STATIC_ASSERT(offsetof(OrbitVisibilitySurface, view_proj) == 120, "view_pr
 
 /* barycentrics, their differences and the triangle's ids of every pixel the list owns; see above */
 int32_t orbit_visibility_surface(OrbitCtx *ctx, const OrbitVisibilitySurface *job, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* The surface of a buffer drawn with ORBIT_RASTER_CLIP_NEAR and / or       */
+/* ORBIT_RASTER_WIDE_GUARD.  orbit_visibility_surface_drawn takes           */
+/* orbit_visibility_surface's block and, in raster_flags, how the buffer    */
+/* was drawn: any subset of the two flags (CLIP, WIDE below).  With         */
+/* raster_flags == 0 it IS orbit_visibility_surface: the same kernels, the  */
+/* same bytes, counters and latched status.  Otherwise S1 and S4-S7 stand   */
+/* as they are and S2, S3 are extended as follows; ONE definition for the   */
+/* device and the host mirror (orbit_host_visibility_surface_drawn), equal  */
+/* on every byte; float rules as in S1-S7.                                  */
+/*  S2d the classes of a key (k, t).  Command k passes R9 and V3 and t < nt */
+/*     as in S2 (else STALE).  c_i = clip_position(...), v_i =              */
+/*     vertex_from_clip(c_i, W, H, false, WIDE) of the three corners.       */
+/*     (a) every clip_in(c_i) holds and every vertex is narrow: S2-S6       */
+/*         exactly, by the same functions, the same bytes.                  */
+/*     (b) every clip_in(c_i) holds and some vertex fails the guard.        */
+/*         Without WIDE: UNSUPPORTED.  With WIDE: a vertex out of band      */
+/*         makes the pixel STALE (the raster guard_skipped it); otherwise   */
+/*         setup_triangle_wide(cull_none = true) runs, and the pixel is     */
+/*         STALE unless the setup draws, edge_at_wide >= 0 on all three     */
+/*         edges and depth_at(SetupW) is > 0 and bit-equal to the word's    */
+/*         high half.  Barycentrics by S3w.                                 */
+/*     (c) some clip_in(c_i) fails.  Without CLIP: UNSUPPORTED.  With CLIP: */
+/*         clip_near_pieces(c0, c1, c2, W, H, pieces, WIDE); count == 0 is  */
+/*         STALE.  Otherwise the pieces q = 0 .. count - 1 are CANDIDATES   */
+/*         in that order, with piece_vertices' vertices.  A piece with an   */
+/*         out-of-band vertex is left out; one with a guard-failing vertex  */
+/*         and no WIDE is left out AS NOT COVERED BY THE FLAGS; an          */
+/*         all-narrow piece goes through setup_triangle(cull_none = true),  */
+/*         edge_at and depth_at, a piece with a wide vertex through their   */
+/*         wide forms.  A candidate OWNS the pixel iff its setup draws, the */
+/*         sample is inside and the depth is > 0 and bit-equal to the       */
+/*         word's high half.  The first owning candidate is the pixel's     */
+/*         piece (in exact terms there is at most one: both pieces keep the */
+/*         orientation and share the diagonal with identical snapped ends). */
+/*         If none owns it the pixel is UNSUPPORTED when a piece was left   */
+/*         out as not covered by the flags, STALE otherwise.                */
+/*     With both flags given nothing is unsupported.                        */
+/*  S3w a wide setup: S3 with E_j in 128-bit integers (R6w's expression     */
+/*     without the bias) and e_j = (float)((double)(int64)(E_j >> 64) *     */
+/*     2^64 + (double)(uint64)E_j): R7w's conversion, then one rounding to  */
+/*     float.  The rest as S3.                                              */
+/*  S3c a piece, in terms of the ORIGINAL corners.  P_0, P_1, P_2: the      */
+/*     piece's vertices in piece_vertices' order.  w_i: the vertex's clip   */
+/*     w; R2's for an original corner, for a new vertex N(i, o) the float   */
+/*     w_i + t * (w_o - w_i) that R3c tests for > 0.  Q_i = e_opp(i) *      */
+/*     (1.0f / w_i): S3's q of vertex P_i, R5's swap of the piece undone    */
+/*     (e by S3, or by S3w for a wide piece).  Each P_i has weights m_i[c]  */
+/*     over the original corners c = 0, 1, 2 in meshlet_data's order: an    */
+/*     original corner c has m[c] = 1 and the others 0; N(i, o) has m[i] =  */
+/*     1.0f - t, m[o] = t and the third 0, t = b_i / den being R3c's own    */
+/*     float.  Then n_c = (Q_0 * m_0[c] + Q_1 * m_1[c]) + Q_2 * m_2[c];     */
+/*     s = (n_0 + n_1) + n_2; l1 = n_1 / s; l2 = n_2 / s; S4's "positive"   */
+/*     is s > 0.  The cut is linear in clip space, so (l1, l2) are the      */
+/*     perspective-correct barycentrics of the UNCUT triangle: a consumer   */
+/*     interpolates the original vertices' attributes and never sees the    */
+/*     cut.  Inside a piece every Q_i >= 0 and 0 <= t <= 1, so n_c >= 0, s  */
+/*     >= n_c and 0.0f <= l <= 1.0f on the bit patterns, as for S3.  S4     */
+/*     uses the same piece at the neighbouring samples; triangle[p] holds   */
+/*     the original three global vertices.                                  */
+/*  stats: cut_pixels and wide_pixels count the written pixels of a piece   */
+/*     and of a wide setup; a wide piece counts in both.                    */
+/*   ORBIT_E_INVALID  orbit_visibility_surface's, under the prefix          */
+/*                    visibility_surface_drawn:, and any bit of             */
+/*                    raster_flags but the two; all checked before the      */
+/*                    context is looked at                                  */
+/* Kernel launches only: no allocation, no scratch, no host wait; a graph   */
+/* captures the call on a fresh context's first call.                       */
+/* ------------------------------------------------------------------------ */
+int32_t orbit_visibility_surface_drawn(OrbitCtx *ctx, const OrbitVisibilitySurface *job, uint32_t raster_flags, void *stream);
 
 #ifdef __cplusplus
 }

@@ -250,6 +250,7 @@ SYMBOLS = {
     "orbit_visibility_compact_workspace": (C.c_uint64, [C.c_uint32]),
     "orbit_visibility_compact": (C.c_int32, [C.c_void_p, C.POINTER(VisibilityCompact), C.c_void_p]),
     "orbit_visibility_surface": (C.c_int32, [C.c_void_p, C.POINTER(VisibilitySurface), C.c_void_p]),
+    "orbit_visibility_surface_drawn": (C.c_int32, [C.c_void_p, C.POINTER(VisibilitySurface), C.c_uint32, C.c_void_p]),
 }
 
 _lib = None

@@ -3,7 +3,8 @@
 // the depth prepass of the draw commands in compute (raster_depth.hip), and orbit_raster_visibility with
 // orbit_visibility_resolve, the same pass keeping the winner's identity and its resolve (raster_visibility.hip), and
 // orbit_visibility_compact, the visible draw list of such a buffer (visibility_compact.hip), and
-// orbit_visibility_surface, its barycentrics, differences and ids per pixel (visibility_surface.hip).
+// orbit_visibility_surface, its barycentrics, differences and ids per pixel (visibility_surface.hip), with
+// orbit_visibility_surface_drawn, the same for a buffer drawn with the raster flags (visibility_surface_drawn.hip).
 #include "abi_internal.h"
 
 namespace {
@@ -193,33 +194,57 @@ int32_t orbit_visibility_compact(OrbitCtx *ctx, const OrbitVisibilityCompact *jo
     return ORBIT_OK;
 }
 
+// What orbit_visibility_surface and orbit_visibility_surface_drawn ask of their block, each error with a message of its
+// own under the prefix `what`.  Reads neither the context nor a device.
+static int32_t check_surface_job(OrbitCtx *ctx, const char *what, const OrbitVisibilitySurface &j) {
+    if (j.flags & ~ORBIT_SURFACE_CLEAR) return fail(ctx, ORBIT_E_INVALID, "%s: flags %#x", what, j.flags);
+    if (const int32_t rc = check_vertex_layout(ctx, what, j.vertex_stride, j.position_offset)) return rc;
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "%s: target %u x %u (1..%u each)", what, j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS)
+        return fail(ctx, ORBIT_E_INVALID, "%s: command_base %u + max_commands %u > %u (24 bits of id)", what, j.command_base,
+                    j.max_commands, ORBIT_VIS_MAX_COMMANDS);
+    if (!j.visibility || !j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data)
+        return fail(ctx, ORBIT_E_INVALID, "%s: NULL buffer", what);
+    if (!j.bary && !j.grad && !j.triangle) return fail(ctx, ORBIT_E_INVALID, "%s: no output", what);
+    if (j.triangle && j.vertex_count > (1ull << 32))
+        return fail(ctx, ORBIT_E_INVALID, "%s: triangle with vertex_count %llu > 2^32 (a global vertex is a u32)", what,
+                    (unsigned long long)j.vertex_count);
+    if (((uintptr_t)j.visibility & 7u) || ((uintptr_t)j.entity_data & 15u) ||
+        (((uintptr_t)j.draw_commands | (uintptr_t)j.meshlet_data | (uintptr_t)j.vertices | (uintptr_t)j.bary | (uintptr_t)j.grad |
+          (uintptr_t)j.triangle | (uintptr_t)j.stats) & 3u))
+        return fail(ctx, ORBIT_E_INVALID, "%s: visibility must be 8-B aligned, entity_data 16-B aligned, every other buffer 4-B aligned", what);
+    return ORBIT_OK;
+}
+
 // A clearing launch (stats, and the outputs with ORBIT_SURFACE_CLEAR) and the surface launch; the command count stays on
 // the device.  No allocation, no scratch, no host sync: capturable on the first call.  As orbit_visibility_compact, the job
 // is checked before the context is looked at, each error with a message of its own: a NULL context is the last error.
 int32_t orbit_visibility_surface(OrbitCtx *ctx, const OrbitVisibilitySurface *job, void *stream) {
     if (!job) return fail(ctx, ORBIT_E_INVALID, "visibility_surface: job is NULL");
-    const OrbitVisibilitySurface &j = *job;
-    if (j.flags & ~ORBIT_SURFACE_CLEAR) return fail(ctx, ORBIT_E_INVALID, "visibility_surface: flags %#x", j.flags);
-    if (const int32_t rc = check_vertex_layout(ctx, "visibility_surface", j.vertex_stride, j.position_offset)) return rc;
-    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
-        return fail(ctx, ORBIT_E_INVALID, "visibility_surface: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
-    if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS)
-        return fail(ctx, ORBIT_E_INVALID, "visibility_surface: command_base %u + max_commands %u > %u (24 bits of id)",
-                    j.command_base, j.max_commands, ORBIT_VIS_MAX_COMMANDS);
-    if (!j.visibility || !j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data)
-        return fail(ctx, ORBIT_E_INVALID, "visibility_surface: NULL buffer");
-    if (!j.bary && !j.grad && !j.triangle) return fail(ctx, ORBIT_E_INVALID, "visibility_surface: no output");
-    if (j.triangle && j.vertex_count > (1ull << 32))
-        return fail(ctx, ORBIT_E_INVALID, "visibility_surface: triangle with vertex_count %llu > 2^32 (a global vertex is a u32)",
-                    (unsigned long long)j.vertex_count);
-    if (((uintptr_t)j.visibility & 7u) || ((uintptr_t)j.entity_data & 15u) ||
-        (((uintptr_t)j.draw_commands | (uintptr_t)j.meshlet_data | (uintptr_t)j.vertices | (uintptr_t)j.bary | (uintptr_t)j.grad |
-          (uintptr_t)j.triangle | (uintptr_t)j.stats) & 3u))
-        return fail(ctx, ORBIT_E_INVALID, "visibility_surface: visibility must be 8-B aligned, entity_data 16-B aligned, every other buffer 4-B aligned");
+    if (const int32_t rc = check_surface_job(ctx, "visibility_surface", *job)) return rc;
     if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "visibility_surface: ctx is NULL");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_visibility_surface(j, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
+    const hipError_t e = launch_visibility_surface(*job, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_surface");
+    return ORBIT_OK;
+}
+
+// orbit_visibility_surface for a buffer drawn with the raster flags `raster_flags` (S2d, S3c, S3w): the same two launches,
+// the same checks.  With no flag it IS orbit_visibility_surface's launches; with one, visibility_surface_drawn.hip's.
+int32_t orbit_visibility_surface_drawn(OrbitCtx *ctx, const OrbitVisibilitySurface *job, uint32_t raster_flags, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "visibility_surface_drawn: job is NULL");
+    if (raster_flags & ~(ORBIT_RASTER_CLIP_NEAR | ORBIT_RASTER_WIDE_GUARD))
+        return fail(ctx, ORBIT_E_INVALID, "visibility_surface_drawn: raster_flags %#x (ORBIT_RASTER_CLIP_NEAR | ORBIT_RASTER_WIDE_GUARD)",
+                    raster_flags);
+    if (const int32_t rc = check_surface_job(ctx, "visibility_surface_drawn", *job)) return rc;
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "visibility_surface_drawn: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = raster_flags == 0u
+                             ? launch_visibility_surface(*job, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream)
+                             : launch_visibility_surface_drawn(*job, raster_flags, ctx->num_cus, ctx->visibility_grid, ctx->status,
+                                                               (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_surface_drawn");
     return ORBIT_OK;
 }
 

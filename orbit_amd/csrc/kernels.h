@@ -442,6 +442,10 @@ hipError_t launch_visibility_compact(const OrbitVisibilityCompact &job, uint32_t
 // ORBIT_SURFACE_CLEAR, fills the outputs; the next reads every word once, a wave per 8 x 8 tile
 hipError_t launch_visibility_surface(const OrbitVisibilitySurface &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
                                      hipStream_t s);
+// visibility_surface_drawn.hip: orbit_visibility_surface_drawn with raster_flags != 0 — the same two launches, the surface
+// launch following the pieces of R3c and the wide setups of R4w (S2d, S3c, S3w)
+hipError_t launch_visibility_surface_drawn(const OrbitVisibilitySurface &job, uint32_t raster_flags, uint32_t num_cus,
+                                           uint32_t grid_cap, int32_t *status, hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

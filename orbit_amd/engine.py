@@ -437,7 +437,7 @@ class Engine:
     def visibility_surface(self, visibility, width, height, draw_commands, max_commands, meshlet_data, vertices, vertex_count,
                            entity_data, entity_count, view_proj, bary=None, grad=None, triangle=None, stats=None,
                            command_base=0, clear=False, vertex_stride=12, position_offset=0, meshlet_data_words=None,
-                           stream=None):
+                           stream=None, raster_flags=None):
         """From the width x height u64 tensor `visibility` and the list that was rasterised into it with `command_base`
         (the arguments of raster_visibility) to what a renderer shades from, for every pixel the list owns: bary (2
         floats per pixel: the perspective-correct l1, l2 of the sample in the owning triangle, in meshlet_data's corner
@@ -458,7 +458,21 @@ class Engine:
         j.vertex_stride, j.position_offset, j.width, j.height = int(vertex_stride), int(position_offset), int(width), int(height)
         j.flags, j.command_base = _lib.SURFACE_CLEAR if clear else 0, int(command_base)
         j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
-        _lib.check(self._lib.orbit_visibility_surface(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+        if raster_flags is None:
+            _lib.check(self._lib.orbit_visibility_surface(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+        else:
+            _lib.check(self._lib.orbit_visibility_surface_drawn(self._ctx, C.byref(j), C.c_uint32(raster_flags), _stream(stream)),
+                       self._ctx)
+
+    def visibility_surface_drawn(self, *args, clip_near=False, wide_guard=False, **kwargs):
+        """visibility_surface for a buffer drawn with clip_near (ORBIT_RASTER_CLIP_NEAR) and / or wide_guard
+        (ORBIT_RASTER_WIDE_GUARD), the flags raster_visibility was given: the pixels of a near-cut triangle's pieces are
+        written with the barycentrics of the UNCUT triangle, those of a wide triangle from 128-bit edge values, and
+        nothing is unsupported once both flags are named.  stats: layouts.SURFACE_DRAWN_STATS (cut_pixels, wide_pixels).
+        Neither flag: visibility_surface's kernels and bytes.  Byte-equal to
+        orbit_amd.raster.host_visibility_surface_drawn.  Enqueued on `stream`."""
+        flags = (_lib.RASTER_CLIP_NEAR if clip_near else 0) | (_lib.RASTER_WIDE_GUARD if wide_guard else 0)
+        self.visibility_surface(*args, raster_flags=flags, **kwargs)
 
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,

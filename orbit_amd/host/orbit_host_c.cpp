@@ -611,6 +611,13 @@ int32_t orbit_host_visibility_surface(const OrbitVisibilitySurface *job, int32_t
     });
 }
 
+int32_t orbit_host_visibility_surface_drawn(const OrbitVisibilitySurface *job, uint32_t raster_flags, int32_t *status) {
+    return guarded([&] {
+        if (!job) throw Panic("visibility_surface_drawn: job is NULL");
+        raster::visibility_surface_drawn(*job, raster_flags, status);
+    });
+}
+
 // ---------------------------------------------------------------- asset ingestion (orbit_gltf.hpp), host only
 void *orbit_host_gltf_load(const char *path) {
     gltf_loader::LoadedScene *scene = nullptr;

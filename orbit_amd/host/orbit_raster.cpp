@@ -325,5 +325,62 @@ void visibility_surface(const OrbitVisibilitySurface &j, int32_t *status) {
     if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
 }
 
+void visibility_surface_drawn(const OrbitVisibilitySurface &j, uint32_t raster_flags, int32_t *status) {
+    if (raster_flags & ~(ORBIT_RASTER_CLIP_NEAR | ORBIT_RASTER_WIDE_GUARD)) throw Panic("visibility_surface_drawn: unknown raster_flags");
+    if (j.flags & ~ORBIT_SURFACE_CLEAR) throw Panic("visibility_surface_drawn: unknown flags");
+    if (!j.visibility || !j.draw_commands || !j.meshlet_data || !j.vertices || !j.entity_data) throw Panic("visibility_surface_drawn: NULL argument");
+    if (!j.bary && !j.grad && !j.triangle) throw Panic("visibility_surface_drawn: no output");
+    if ((uint64_t)j.vertex_stride < (uint64_t)j.position_offset + 12u || (j.vertex_stride & 3u) || (j.position_offset & 3u))
+        throw Panic("visibility_surface_drawn: vertex_stride / position_offset");
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        throw Panic("visibility_surface_drawn: target size");
+    if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS) throw Panic("visibility_surface_drawn: command_base + max_commands");
+    if (j.triangle && j.vertex_count > (1ull << 32)) throw Panic("visibility_surface_drawn: triangle with vertex_count > 2^32");
+    const size_t pixels = (size_t)j.width * j.height;
+    if (j.flags & ORBIT_SURFACE_CLEAR) { // S7
+        if (j.bary) std::memset(j.bary, 0, pixels * 8);
+        if (j.grad) std::memset(j.grad, 0, pixels * 16);
+        if (j.triangle) std::memset(j.triangle, 0xFF, pixels * 16);
+    }
+    const uint32_t *commands = static_cast<const uint32_t *>(j.draw_commands);
+    const uint32_t n = commands[0] < j.max_commands ? commands[0] : j.max_commands;
+    OrbitSurfaceStats st{};
+    for (size_t p = 0; p < pixels; p++) {
+        const uint64_t word = j.visibility[p];
+        if (word == 0) continue;
+        st.covered_pixels++;
+        const uint32_t id = (uint32_t)(word >> 8) & 0xFFFFFFu, t = (uint32_t)word & 255u;
+        if (id < j.command_base || id - j.command_base >= n) { // S1
+            st.foreign_pixels++;
+            continue;
+        }
+        const uint32_t k = id - j.command_base;
+        const SurfaceCommand cmd = surface_command(j, k);
+        bool command_ok = cmd.in_range; // R9, V3
+        for (uint32_t v = 0; v < cmd.vcount && command_ok; v++) command_ok = surface_index_word_ok(j, cmd, v);
+        for (uint32_t b = 0; b < 3u * cmd.nt && command_ok; b++) command_ok = surface_corner_byte_ok(j, cmd, b);
+        SurfaceTriangle tri;
+        SurfaceSlow slow;
+        surface_triangle_drawn(j, k, t, command_ok, raster_flags, tri, slow); // S2d
+        float out[6];
+        bool degenerate;
+        uint32_t cand_flags;
+        const uint32_t verdict = surface_pixel_drawn(tri, slow, (int32_t)(p % j.width), (int32_t)(p / j.width), (uint32_t)(word >> 32), out,
+                                                     degenerate, cand_flags);
+        if (verdict == kSurfaceUnsupported) st.unsupported_pixels++;
+        if (verdict == kSurfaceStale) st.stale_pixels++;
+        if (verdict != kSurfaceWritten) continue;
+        st.written_pixels++;
+        if (degenerate) st.degenerate_pixels++;
+        if (cand_flags & kCandCut) st.cut_pixels++;
+        if (cand_flags & kCandWide) st.wide_pixels++;
+        if (j.bary) std::memcpy(j.bary + 2 * p, out, 8);
+        if (j.grad) std::memcpy(j.grad + 4 * p, out + 2, 16);
+        if (j.triangle) std::memcpy(j.triangle + 4 * p, tri.ids, 16);
+    }
+    if (j.stats) *j.stats = st;
+    if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
+}
+
 } // namespace raster
 } // namespace orbit

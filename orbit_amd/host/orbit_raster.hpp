@@ -51,5 +51,10 @@ void visibility_compact(const OrbitVisibilityCompact &job, int32_t *status);
 // if a pixel was stale, else ORBIT_OK.  Throws Panic for ORBIT_E_INVALID.
 void visibility_surface(const OrbitVisibilitySurface &job, int32_t *status);
 
+// orbit_visibility_surface_drawn (S2d, S3c, S3w, §4.23) on host buffers: the same loop, each pixel through
+// surface_triangle_drawn and surface_pixel_drawn.  raster_flags: how the buffer was drawn, a subset of
+// ORBIT_RASTER_CLIP_NEAR | ORBIT_RASTER_WIDE_GUARD; 0 gives visibility_surface's bytes.
+void visibility_surface_drawn(const OrbitVisibilitySurface &job, uint32_t raster_flags, int32_t *status);
+
 } // namespace raster
 } // namespace orbit

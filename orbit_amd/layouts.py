@@ -67,6 +67,8 @@ VIS_COMPACT_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "foreign_pi
 # OrbitSurfaceStats: the counters of orbit_visibility_surface
 SURFACE_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "written_pixels", "foreign_pixels", "unsupported_pixels",
                                                "stale_pixels", "degenerate_pixels", "_pad0", "_pad1")])
+# the same 32 bytes as orbit_visibility_surface_drawn fills them: the last two words are its own counters
+SURFACE_DRAWN_STATS = np.dtype([(n, "<u4") for n in SURFACE_STATS.names[:6] + ("cut_pixels", "wide_pixels")])
 # types.glsl:92-110, src/assets/mod.rs:171-191
 MATERIAL = np.dtype([
     ("base_color", "<f4", (4,)), ("emissive_factor", "<f4", (3,)), ("metallic_factor", "<f4"),

@@ -138,7 +138,7 @@ def host_visibility_compact(visibility, draw_commands, max_commands, command_bas
 def host_visibility_surface(visibility, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data,
                             view_proj, command_base=0, clear=True, into=None, want=("bary", "grad", "triangle"),
                             vertex_stride=12, position_offset=0, entity_count=None, meshlet_data_words=None, fill=0,
-                            want_stats=True):
+                            want_stats=True, _drawn=None):
     """orbit_host_visibility_surface on a (height, width) np.uint64 buffer and the arguments of host_raster_visibility
     that made it -> dict(bary: np.float32 (height, width, 2), grad: np.float32 (height, width, 4), triangle: np.uint32
     (height, width, 4), each None unless named in `want`; stats: np[layouts.SURFACE_STATS] scalar row or None; status:
@@ -162,7 +162,7 @@ def host_visibility_surface(visibility, draw_commands, max_commands, meshlet_dat
             outs[name] = np.array(into[name], dtype=dtype, order="C").reshape(height, width, per_pixel)
         else:
             outs[name] = np.full((height, width, per_pixel), fill, np.uint32).view(dtype)
-    stats = np.zeros(1, L.SURFACE_STATS) if want_stats else None
+    stats = np.zeros(1, L.SURFACE_STATS if _drawn is None else L.SURFACE_DRAWN_STATS) if want_stats else None
     p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     j = _lib.VisibilitySurface()
     j.visibility, j.draw_commands, j.meshlet_data, j.vertices, j.entity_data = p(vis), p(buf), p(data), p(vb), p(ent)
@@ -174,5 +174,16 @@ def host_visibility_surface(visibility, draw_commands, max_commands, meshlet_dat
     j.flags, j.command_base = _lib.SURFACE_CLEAR if clear else 0, int(command_base)
     j.view_proj = (C.c_float * 16)(*np.asarray(view_proj, dtype=np.float32).reshape(16))
     status = C.c_int32(0)
-    _check(lib().orbit_host_visibility_surface(C.byref(j), C.byref(status)))
+    if _drawn is None:
+        _check(lib().orbit_host_visibility_surface(C.byref(j), C.byref(status)))
+    else:
+        _check(lib().orbit_host_visibility_surface_drawn(C.byref(j), C.c_uint32(_drawn), C.byref(status)))
     return dict(outs, stats=None if stats is None else stats[0], status=status.value)
+
+
+def host_visibility_surface_drawn(*args, clip_near=False, wide_guard=False, raster_flags=None, **kwargs):
+    """orbit_host_visibility_surface_drawn: host_visibility_surface's arguments and result for a buffer drawn with
+    clip_near (ORBIT_RASTER_CLIP_NEAR) and / or wide_guard (ORBIT_RASTER_WIDE_GUARD); `raster_flags` gives the word
+    itself.  stats: np[layouts.SURFACE_DRAWN_STATS].  Neither flag: host_visibility_surface's bytes."""
+    flags = (CLIP_NEAR if clip_near else 0) | (WIDE_GUARD if wide_guard else 0) if raster_flags is None else int(raster_flags)
+    return host_visibility_surface(*args, _drawn=flags, **kwargs)
