@@ -130,6 +130,12 @@ ORBIT_BLK_FN BlockBound block_bound_of(const float *spheres, uint32_t n) {
     return block_bound_finish(cx, cy, cz, dist, r_max, r_min, finite);
 }
 
+// What the plane loop below needs of a plane alone, not of the record: |n| rounded up.  The evaluation computes it once
+// per workgroup and plane (meshlet_eval_blocks.hip plane_nn), not once per record and plane.
+ORBIT_BLK_FN float block_plane_norm(float nx, float ny, float nz) {
+    return sqrtf(fmaf(nz, nz, fmaf(ny, ny, nx * nx))) * kBlkUp + kBlkTiny;
+}
+
 // A record's precomputation.  m = view x model, column-major (m[4 c + r]); affine: its last row is 0 0 0 1 and its
 // translation finite (WaveTileLds::affine_rows); scale: the slab's largest column norm; planes: n_planes x {nx, ny, nz, w};
 // covered: the record starts on a multiple of 32 and the stream holds all its meshlets; ratio: the record is sparse only
@@ -174,12 +180,98 @@ ORBIT_BLK_FN BlockRecord block_record_setup(const float *m, bool affine, float s
     bool inside = sparse;
     for (uint32_t i = 0; i < n_planes; i++) {
         const float nx = planes[4 * i], ny = planes[4 * i + 1], nz = planes[4 * i + 2], w = planes[4 * i + 3];
-        const float nn = sqrtf(fmaf(nz, nz, fmaf(ny, ny, nx * nx))) * kBlkUp + kBlkTiny;
+        const float nn = block_plane_norm(nx, ny, nz);
         const float dist = fmaf(nz, dz, fmaf(ny, dy, fmaf(nx, dx, w))) - nn * rcp;
         const float margin = fmaf(kBlkEps, fmaf(nn, mag, fabsf(w)), kBlkTiny);
         inside = inside && dist > margin; // then fl(n . p + w) > 0 >= -radius x scale for every meshlet of the block
     }
     o.flags = (sparse ? kBlkSparse : 0u) | (inside ? kBlkInside : 0u);
+    return o;
+}
+
+// The same precomputation on FOUR lanes per record (the evaluation's blk_setup: lane k = lane & 3 of record lane >> 2).
+// Every value that reaches the BlockRecord is computed by the expression tree block_record_setup computes it by — the
+// same operations on the same operands in the same order — only by another lane, so the two forms agree in every bit
+// (tests/test_block_setup_quad_cpu.py) and no bound above needs deriving again: nothing is summed across lanes.
+//   lane k reads row k of m and two of its columns, A = column {0, 1, 2, 0}[k] and B = column {1, 2, 2, 2}[k], and
+//   computes d_k and ap_k (k < 3), the Gram diagonal of A (k < 3: g00, g11, g22) and |A . B| (k = 0, 1, 3: g01, g12, g02);
+//   the quad exchanges these twelve (BlockQuadSums); every lane runs the scalar tail (BlockQuadTail), lane k < 3 adds
+//   component k of g = L^T d from its column A, lane 3 has D; plane i goes to lane i & 3, and the record is inside if
+//   every lane's planes say so.
+ORBIT_BLK_FN int block_quad_col_a(int k) { return k == 3 ? 0 : k; }
+ORBIT_BLK_FN int block_quad_col_b(int k) { return k < 2 ? k + 1 : 2; }
+struct BlockQuadShare {
+    float d, ap, gd, go;
+};
+ORBIT_BLK_FN BlockQuadShare block_quad_share(const float row[4], const float a[3], const float b[3], float Cx, float Cy, float Cz) {
+    BlockQuadShare s;
+    s.d = fmaf(row[2], Cz, fmaf(row[1], Cy, fmaf(row[0], Cx, row[3])));
+    s.ap = fmaf(fabsf(row[2]), fabsf(Cz), fmaf(fabsf(row[1]), fabsf(Cy), fmaf(fabsf(row[0]), fabsf(Cx), fabsf(row[3]))));
+    s.gd = fmaf(a[2], a[2], fmaf(a[1], a[1], a[0] * a[0]));
+    s.go = fabsf(fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0])));
+    return s;
+}
+struct BlockQuadSums { // lane:
+    float dx, dy, dz;     // d of 0, 1, 2
+    float apx, apy, apz;  // ap of 0, 1, 2
+    float g00, g11, g22;  // gd of 0, 1, 2
+    float g01, g12, g02;  // go of 0, 1, 3
+};
+struct BlockQuadTail {
+    float sigma, rcp, D, mag, bk, rr;
+    bool sparse;
+};
+constexpr float kBlkKf = 0x1.020408p-7f; // the reference's 1 / 127 (orbit_device.h snorm8)
+ORBIT_BLK_FN BlockQuadTail block_quad_tail(const BlockQuadSums &q, bool affine, float scale, const BlockBound &b, bool covered,
+                                           float ratio) {
+    BlockQuadTail t;
+    const float s2 = blk_max(q.g00 + q.g01 + q.g02, blk_max(q.g11 + q.g01 + q.g12, q.g22 + q.g02 + q.g12));
+    t.sigma = sqrtf(s2) * (1.0f + 0x1p-16f) + 0x1p-60f;
+    const float ap = (blk_max(q.apx, blk_max(q.apy, q.apz)) + 2.0f * t.sigma * b.rc) * kBlkUp;
+    t.rcp = fmaf(kBlkEps, ap, t.sigma * b.rc * kBlkUp);
+    t.D = sqrtf(fmaf(q.dz, q.dz, fmaf(q.dy, q.dy, q.dx * q.dx)));
+    t.mag = ap + t.D + t.rcp;
+    t.bk = kBlkKf * fmaf(kBlkEps, t.mag, t.rcp) * kBlkSlack;
+    t.rr = b.r_max * scale * kBlkSlack + kBlkTiny;
+    t.sparse = affine && covered && b.valid != 0u && t.D > ratio * t.rcp && t.D > 0x1p-40f && t.mag < kBlkHuge &&
+               t.sigma < 0x1p40f && t.rr < kBlkHuge && scale >= 0.0f;
+    return t;
+}
+// lane k < 3: k_f g_k from its column A (column k); lane 3: k_f D — the record's first four floats, one per lane
+ORBIT_BLK_FN float block_quad_out(int k, const float a[3], const BlockQuadSums &q, const BlockQuadTail &t) {
+    const float g = fmaf(a[2], q.dz, fmaf(a[1], q.dy, a[0] * q.dx));
+    return (k == 3 ? t.D : g) * kBlkKf;
+}
+// one plane {nx, ny, nz, w} with nn = block_plane_norm(nx, ny, nz): the block is certainly inside it
+ORBIT_BLK_FN bool block_quad_plane(const float pl[4], float nn, const BlockQuadSums &q, const BlockQuadTail &t) {
+    const float dist = fmaf(pl[2], q.dz, fmaf(pl[1], q.dy, fmaf(pl[0], q.dx, pl[3]))) - nn * t.rcp;
+    const float margin = fmaf(kBlkEps, fmaf(nn, t.mag, fabsf(pl[3])), kBlkTiny);
+    return dist > margin;
+}
+// The quad form with arrays of four where the device has four lanes and an exchange (plane_nn[i]: block_plane_norm of
+// plane i, as the evaluation's workgroup holds it).
+ORBIT_BLK_FN BlockRecord block_record_setup_quad(const float *m, bool affine, float scale, const BlockBound &b, bool covered,
+                                                 const float *planes, const float *plane_nn, uint32_t n_planes,
+                                                 float ratio = ORBIT_BLK_RATIO) {
+    BlockQuadShare s[4];
+    for (int k = 0; k < 4; k++) {
+        const float row[4] = {m[k], m[4 + k], m[8 + k], m[12 + k]};
+        s[k] = block_quad_share(row, m + 4 * block_quad_col_a(k), m + 4 * block_quad_col_b(k), b.cx, b.cy, b.cz);
+    }
+    const BlockQuadSums q = {s[0].d,  s[1].d,  s[2].d,  s[0].ap, s[1].ap, s[2].ap,
+                             s[0].gd, s[1].gd, s[2].gd, s[0].go, s[1].go, s[3].go};
+    float out[4];
+    BlockQuadTail t[4];
+    bool pass = true;
+    for (int k = 0; k < 4; k++) {
+        t[k] = block_quad_tail(q, affine, scale, b, covered, ratio);
+        out[k] = block_quad_out(k, m + 4 * block_quad_col_a(k), q, t[k]);
+        for (uint32_t i = (uint32_t)k; i < n_planes; i += 4u) pass = block_quad_plane(planes + 4 * i, plane_nn[i], q, t[k]) && pass;
+    }
+    BlockRecord o;
+    o.gx = out[0], o.gy = out[1], o.gz = out[2], o.dk = out[3];
+    o.sigma = t[0].sigma, o.bk = t[0].bk, o.rr = t[0].rr;
+    o.flags = (t[0].sparse ? kBlkSparse : 0u) | (t[0].sparse && pass ? kBlkInside : 0u);
     return o;
 }
 

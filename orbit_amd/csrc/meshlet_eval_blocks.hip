@@ -45,47 +45,73 @@ __device__ __forceinline__ bool row_is_sparse(const WaveTileLds &L, int r) {
     return (((uint32_t)__builtin_amdgcn_readfirstlane((int)w) >> (2 * r)) & 1u) != 0u;
 }
 
-// The block bound of record `lane` of a tile (lanes 0..15; `rec` is held by lanes 4 record .. 4 record + 3), and whether
-// the record starts a block and lies inside the stream.  Unconditional loads: everybody else reads the zero page.
+// The block bound of a lane's record (`rec` is held by lanes 4 record .. 4 record + 3, and so is its bound: the four lanes
+// of blk_setup's quad), and whether the record starts a block and lies inside the stream.  Unconditional loads: everybody
+// else reads the zero page.
 struct BoundRegs {
     float4 q; // centre, BlockBound::packed (0, not valid, also where the record is not covered: the zero page)
 };
-__device__ __forceinline__ BoundRegs blk_load_bound(const MeshletCullParams &p, const BlockBound *blk, const uint4 &rec, int lane) {
-    const int src_lane = (lane & 15) * 4;
-    const uint32_t y = (uint32_t)__shfl((int)rec.y, src_lane, 64), z = (uint32_t)__shfl((int)rec.z, src_lane, 64);
+__device__ __forceinline__ BoundRegs blk_load_bound(const MeshletCullParams &p, const BlockBound *blk, const uint4 &rec) {
+    const uint32_t y = rec.y, z = rec.z;
     const uint32_t rel = y - p.ms.first;
     BoundRegs b;
-    const bool covered = lane < (int)kTileRecords && z != 0u && (y & 31u) == 0u && rel < p.ms.count && z <= p.ms.count - rel;
+    const bool covered = z != 0u && (y & 31u) == 0u && rel < p.ms.count && z <= p.ms.count - rel;
     const float4 *src = covered ? reinterpret_cast<const float4 *>(blk + (y >> 5)) : reinterpret_cast<const float4 *>(p.zero_page);
     b.q = src[0];
     return b;
 }
 
-// Behind setup_write of the same slab (which ends in a wave barrier): lane r < 16 derives record r's BlockRecord.
+// lane K of the caller's quad's x (quad_perm broadcast, as setup_write_cls)
+template <int K>
+__device__ __forceinline__ float quad_bcast(float x) {
+    return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), K * 0x55, 0xF, 0xF, false));
+}
+
+// Behind setup_write of the same slab (which ends in a wave barrier): the four lanes that hold record lane >> 2 (`rec`,
+// `bb`) derive its BlockRecord — block_pretest.h's quad form, which says who computes what and why the bits are
+// block_record_setup's.  plane_nn: block_plane_norm of the planes in use (the kernel's prologue).
 __device__ __forceinline__ void blk_setup(const MeshletCullParams &p, WaveTileLds &L, BlockTileLds &B, const PlaneLds &P,
-                                          const BoundRegs &bb, int lane) {
-    uint32_t flags = 0u;
-    if (lane < (int)kTileRecords) {
-        const RecordLds &R = L.r[lane];
-        float m[16];
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const float4 col = R.mcol[c];
-            m[4 * c] = col.x, m[4 * c + 1] = col.y, m[4 * c + 2] = col.z, m[4 * c + 3] = col.w;
-        }
-        const BlockBound b = block_bound_unpack(bb.q.x, bb.q.y, bb.q.z, __float_as_uint(bb.q.w));
-        const uint32_t aw = reinterpret_cast<const uint32_t *>(&L.affine_rows)[lane >> 3];
-        const bool affine = ((aw >> (8 * ((lane >> 1) & 3))) & 1u) != 0u;
-        // (covered: a record that is not reads the zero page, whose bound is not valid)
-        BlockRecord o = block_record_setup(m, affine, R.scale, b, true, reinterpret_cast<const float *>(P.plane),
-                                           min(p.ci.cull_plane_count, (uint32_t)ORBIT_MAX_CULL_PLANES));
-        if (R.rec.z == 0u) o.flags = kBlkSparse; // no record: no lane of it is ever allowed, it holds no row back
-        B.r[lane] = o;
-        flags = o.flags;
+                                          const float *plane_nn, const uint4 &rec, const BoundRegs &bb, int lane) {
+    const int rid = lane >> 2, k = lane & 3;
+    const RecordLds &R = L.r[rid];
+    const float *mf = reinterpret_cast<const float *>(R.mcol);
+    const float row[4] = {mf[k], mf[4 + k], mf[8 + k], mf[12 + k]};
+    const float4 ca = R.mcol[block_quad_col_a(k)], cb = R.mcol[block_quad_col_b(k)];
+    const float a[3] = {ca.x, ca.y, ca.z}, bcol[3] = {cb.x, cb.y, cb.z};
+    const BlockBound b = block_bound_unpack(bb.q.x, bb.q.y, bb.q.z, __float_as_uint(bb.q.w));
+    const BlockQuadShare s = block_quad_share(row, a, bcol, b.cx, b.cy, b.cz);
+    const BlockQuadSums q = {quad_bcast<0>(s.d),  quad_bcast<1>(s.d),  quad_bcast<2>(s.d),  quad_bcast<0>(s.ap),
+                             quad_bcast<1>(s.ap), quad_bcast<2>(s.ap), quad_bcast<0>(s.gd), quad_bcast<1>(s.gd),
+                             quad_bcast<2>(s.gd), quad_bcast<0>(s.go), quad_bcast<1>(s.go), quad_bcast<3>(s.go)};
+    const uint32_t aw = reinterpret_cast<const uint32_t *>(&L.affine_rows)[lane >> 5];
+    const bool affine = ((aw >> (8 * ((lane >> 3) & 3))) & 1u) != 0u;
+    // (covered: a record that is not reads the zero page, whose bound is not valid)
+    const BlockQuadTail t = block_quad_tail(q, affine, R.scale, b, true, ORBIT_BLK_RATIO);
+    reinterpret_cast<float *>(&B.r[rid])[k] = block_quad_out(k, a, q, t); // gx, gy, gz, dk
+    const uint32_t n = min(p.ci.cull_plane_count, (uint32_t)ORBIT_MAX_CULL_PLANES);
+    bool pass = true;
+    for (uint32_t i0 = 0; i0 < n; i0 += 4u) { // plane i0 + k
+        const bool has = i0 + (uint32_t)k < n;
+        const uint32_t i = has ? i0 + (uint32_t)k : 0u;
+        const float4 pl4 = P.plane[i];
+        const float pl[4] = {pl4.x, pl4.y, pl4.z, pl4.w};
+        pass &= block_quad_plane(pl, plane_nn[i], q, t) | !has; // (no branch: a lane without a plane reads plane 0)
     }
-    uint64_t m = __ballot((flags & kBlkSparse) != 0u);
-    m &= m >> 1; // bit 2 r: both records of row r
-    if (lane == 0) L.pad_ = m & 0x5555ull;
+    uint64_t in = ballot(pass);
+    in &= in >> 1;
+    in &= in >> 2; // bit 4 record: every lane of the quad
+    const bool none = rec.z == 0u; // no record: no lane of it is ever allowed, it holds no row back
+    if (k == 0) {
+        const uint32_t flags = none ? kBlkSparse : (t.sparse ? kBlkSparse | (lane_of(in) ? kBlkInside : 0u) : 0u);
+        reinterpret_cast<float4 *>(&B.r[rid])[1] = make_float4(t.sigma, t.bk, t.rr, __uint_as_float(flags));
+    }
+    uint64_t m = ballot(t.sparse || none); // four equal bits per record, eight lanes per row
+    m &= m >> 4;                           // bit 8 r: both records of row r
+    m &= 0x0101010101010101ull;            // ... moved to bit 2 r, the word row_is_sparse and tile_is_sparse read
+    m = (m | m >> 6) & 0x0005000500050005ull;
+    m = (m | m >> 12) & 0x0000005500000055ull;
+    m = (m | m >> 24) & 0x5555ull;
+    if (lane == 0) L.pad_ = m;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -124,23 +150,17 @@ __device__ __forceinline__ void blk_row_load(const MeshletCullParams &p, const W
     v[0] = sp[0], v[1] = sp[1], v[2] = sp[2], v[3] = sp[3];
 }
 
-// The eight cone words of an all-sparse tile into v[0..7]: eight loads back to back, no sphere load at all.  Range-checked
-// lane by lane as blk_row_load does it (the status is latched once, behind the loads: first error wins either way).
-__device__ __forceinline__ void blk_tile_load(const MeshletCullParams &p, const WaveTileLds &L, int lane, uint32_t *v,
-                                              const StreamRsrc &SR) {
+// The eight cone words of an all-sparse tile into v[0..7]: eight loads back to back, no sphere load at all.  No range
+// check as blk_row_load has it: a record with meshlets is sparse only if blk_load_bound found it covered — inside the
+// stream with all its meshlets — so no active lane of such a tile can lie outside (uncovered records make dense rows).
+__device__ __forceinline__ void blk_tile_load(const WaveTileLds &L, int lane, uint32_t *v, const StreamRsrc &SR) {
     const uint32_t half = lane >> 5, ml = lane & 31;
-    bool bad = false;
 #pragma unroll
     for (int r = 0; r < (int)kTileRows; r++) {
         const uint4 rec = L.r[2 * r + half].rec;
-        const bool active = ml < rec.z;
-        const uint32_t rel = rec.y + ml - SR.first;
-        const bool in = active & (rel < SR.count);
-        bad |= active & !in;
-        const uint32_t i = in ? rel : kNoOffset >> 4;
+        const uint32_t i = ml < rec.z ? rec.y + ml - SR.first : kNoOffset >> 4;
         v[r] = __builtin_amdgcn_raw_buffer_load_b32(SR.cone, i << 2, 0, ORBIT_EVAL_LOAD_AUX);
     }
-    if (bad) latch_status(p.status, ORBIT_E_RANGE);
 }
 
 // A dense row from v[0..4]: rows_eval unchanged.
@@ -206,6 +226,7 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
     __shared__ BlockTileLds blds[kBkWaves][2]; // of tile i in [i & 1]: written when tile i - 2 is through its rows
     __shared__ PlaneLds planes;
     __shared__ CandRing rings[kBkWaves];
+    __shared__ float plane_nn[ORBIT_MAX_CULL_PLANES]; // block_plane_norm of the planes in use: constant for the launch
     __shared__ uint32_t cls_sel[8]; // [2 c + k] = all ones if alpha class c has predicate bit k (alpha_bits)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // the ramp, the tile assignment (static share + tickets) and the priorities: meshlet_eval_body, which explains them
@@ -217,6 +238,10 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
     uint4 r1 = setup_load_rec(p, wave_g + stride, wave_g + stride < cap_tiles, p.dispatch_capacity, lane);
     uint4 rec2 = setup_load_rec(p, wave_g + 2u * stride, wave_g + 2u * stride < cap_tiles, p.dispatch_capacity, lane);
     planes_to_lds(p, planes);
+    if (threadIdx.x < min(p.ci.cull_plane_count, (uint32_t)ORBIT_MAX_CULL_PLANES)) {
+        const float *pl = p.ci.cull_planes[threadIdx.x];
+        plane_nn[threadIdx.x] = block_plane_norm(pl[0], pl[1], pl[2]);
+    }
     clear_chunk_sums(p, kBkWaves * 64);
     if (threadIdx.x < 6) cls_sel[threadIdx.x] = ((alpha_bits(p.ci, threadIdx.x >> 1) >> (threadIdx.x & 1u)) & 1u) ? ~0u : 0u;
     __syncthreads();
@@ -272,23 +297,23 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
         const float4 m0 = setup_load_mat(p, r0, lane);
         const float4 m1 = setup_load_mat(p, r1, lane);
         const uint32_t c0 = setup_load_cls(p, r0, lane), c1 = setup_load_cls(p, r1, lane);
-        const BoundRegs b0 = blk_load_bound(p, blk, r0, lane), b1 = blk_load_bound(p, blk, r1, lane);
+        const BoundRegs b0 = blk_load_bound(p, blk, r0), b1 = blk_load_bound(p, blk, r1);
         setup_write_cls(lds[wave][0], cls_sel, r0, c0, lane);
         setup_write_cls(lds[wave][1], cls_sel, r1, c1, lane);
         setup_write(p, lds[wave][0], r0, m0, lane);
-        blk_setup(p, lds[wave][0], blds[wave][0], planes, b0, lane);
+        blk_setup(p, lds[wave][0], blds[wave][0], planes, plane_nn, r0, b0, lane);
         // tile 0's first loads go out once its slab says which of its rows are sparse, behind the second slab's loads
         // and ahead of its setup: no sphere is read for a row that never looks at it
         whole = tile_is_sparse(lds[wave][0]);
         if (whole) {
-            blk_tile_load(p, lds[wave][0], lane, q.v, SR);
+            blk_tile_load(lds[wave][0], lane, q.v, SR);
             q.v[8] = q.v[9] = 0u;
         } else {
             blk_row_load<0>(p, lds[wave][0], row_is_sparse(lds[wave][0], 0), lane, qa, SR);
             blk_row_load<1>(p, lds[wave][0], row_is_sparse(lds[wave][0], 1), lane, qb, SR);
         }
         setup_write(p, lds[wave][1], r1, m1, lane);
-        blk_setup(p, lds[wave][1], blds[wave][1], planes, b1, lane);
+        blk_setup(p, lds[wave][1], blds[wave][1], planes, plane_nn, r1, b1, lane);
     }
     uint32_t it = 0;
     const uint32_t prio_rank = blockIdx.x / max(gridDim.x / (uint32_t)kBkWavesPerSimd, 1u);
@@ -320,7 +345,7 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
             // registers with no load between them.
             PipeRegs tn;
             if (nxt_whole) {
-                blk_tile_load(p, Ln, lane, tn.v, SR);
+                blk_tile_load(Ln, lane, tn.v, SR);
                 tn.v[8] = tn.v[9] = 0u;
             } else {
                 blk_row_load<0>(p, Ln, row_is_sparse(Ln, 0), lane, tn.v, SR);
@@ -328,7 +353,7 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
             }
             mat2 = setup_load_mat(p, rec2, lane);
             cls2 = setup_load_cls(p, rec2, lane);
-            bnd2 = blk_load_bound(p, blk, rec2, lane);
+            bnd2 = blk_load_bound(p, blk, rec2);
             rec3 = setup_load_rec(p, w3, w3 < ntiles, nrec, lane);
             blk_row_eval<0>(L, B, ring, lane, q.v[0], rs);
             blk_row_eval<1>(L, B, ring, lane, q.v[1], rs);
@@ -359,7 +384,7 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
             BK_FLUSH()
             mat2 = setup_load_mat(p, rec2, lane);
             cls2 = setup_load_cls(p, rec2, lane);
-            bnd2 = blk_load_bound(p, blk, rec2, lane);
+            bnd2 = blk_load_bound(p, blk, rec2);
             rec3 = setup_load_rec(p, w3, w3 < ntiles, nrec, lane);
             BK_ROW(4, qa)
             blk_row_load<6>(p, L, row_is_sparse(L, 6), lane, qa, SR);
@@ -369,7 +394,7 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
             if (!nxt_whole) blk_row_load<0>(p, Ln, row_is_sparse(Ln, 0), lane, qa, SR);
             BK_ROW(7, qb)
             if (nxt_whole) {
-                blk_tile_load(p, Ln, lane, q.v, SR);
+                blk_tile_load(Ln, lane, q.v, SR);
                 q.v[8] = q.v[9] = 0u;
             } else {
                 blk_row_load<1>(p, Ln, row_is_sparse(Ln, 1), lane, qb, SR);
@@ -380,7 +405,7 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
         whole = nxt_whole;
         setup_write_cls(lds[wave][(it + 2) % 3], cls_sel, rec2, cls2, lane);
         setup_write(p, lds[wave][(it + 2) % 3], rec2, mat2, lane);
-        blk_setup(p, lds[wave][(it + 2) % 3], blds[wave][it & 1u], planes, bnd2, lane); // (this tile's rows are through)
+        blk_setup(p, lds[wave][(it + 2) % 3], blds[wave][it & 1u], planes, plane_nn, rec2, bnd2, lane); // (this tile's rows are through)
         while (rs.count > 0u) blk_flush(p, L, planes, ring, SR, lane, rs, min(rs.count, kBkFlush));
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // the mask writes of this tile
         __builtin_amdgcn_wave_barrier();

@@ -708,4 +708,23 @@ uint32_t orbit_host_block_pretest(const float m[16], int32_t affine, float scale
     return r.flags;
 }
 
+void orbit_host_block_record(const float m[16], int32_t affine, float scale, const void *bound, const float *planes,
+                             uint32_t n_planes, float ratio, int32_t quad, void *out) {
+    orbit::BlockBound in;
+    memcpy(&in, bound, sizeof(in));
+    const orbit::BlockBound b = orbit::block_bound_unpack(in.cx, in.cy, in.cz, in.packed);
+    const float rt = ratio < 0.0f ? ORBIT_BLK_RATIO : ratio;
+    orbit::BlockRecord r;
+    if (quad != 0) {
+        std::vector<float> nn(n_planes); // as the evaluation's workgroup holds them
+        for (uint32_t i = 0; i < n_planes; i++) nn[i] = orbit::block_plane_norm(planes[4 * i], planes[4 * i + 1], planes[4 * i + 2]);
+        r = orbit::block_record_setup_quad(m, affine != 0, scale, b, true, planes, nn.data(), n_planes, rt);
+    } else {
+        r = orbit::block_record_setup(m, affine != 0, scale, b, true, planes, n_planes, rt);
+    }
+    memcpy(out, &r, sizeof(r));
+}
+
+float orbit_host_block_plane_norm(float nx, float ny, float nz) { return orbit::block_plane_norm(nx, ny, nz); }
+
 } // extern "C"

@@ -293,10 +293,16 @@ void orbit_host_transform_from_mat4(const float matrix[16], float position[3], f
  * against `count` cone words.  verdicts[i]: 0 = the record is dense or the meshlet's verdict open (the literal evaluation
  * decides), 1 = certainly culled by the cone, 2 = certainly kept by the cone, 2 | 4 = ... and certainly inside every plane.
  * ratio: the record is sparse only if its block is further than ratio x its view-space radius (< 0: the evaluation's).
- * Returns the record's flags (1: sparse, 2: inside). */
+ * Returns the record's flags (1: sparse, 2: inside).
+ * orbit_host_block_record: the record's 32-B BlockRecord itself, from block_record_setup (quad = 0) or from the form the
+ * evaluation runs on four lanes per record (quad != 0: block_record_setup_quad, plane norms from block_plane_norm) — the
+ * two must agree in every bit.  orbit_host_block_plane_norm: block_plane_norm of one plane's normal. */
 void orbit_host_block_bounds(const float *spheres, uint64_t count, void *out);
 uint32_t orbit_host_block_pretest(const float m[16], int32_t affine, float scale, const void *bound, const float *planes,
                                   uint32_t n_planes, float ratio, const uint32_t *cones, uint64_t count, uint8_t *verdicts);
+void orbit_host_block_record(const float m[16], int32_t affine, float scale, const void *bound, const float *planes,
+                             uint32_t n_planes, float ratio, int32_t quad, void *out);
+float orbit_host_block_plane_norm(float nx, float ny, float nz);
 #ifdef __cplusplus
 }
 #endif
