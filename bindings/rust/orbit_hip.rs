@@ -200,6 +200,32 @@ pub struct OrbitVisibilitySurface {
     pub view_proj: [f32; 16],
 }
 
+pub const ORBIT_FRAGMENTS_CLEAR: u32 = 1;
+
+/// The counters of orbit_surface_fragments (32 B, DEVICE, cleared by the call): covered = written + foreign + unshaded +
+/// stale
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitFragmentStats {
+    pub covered_pixels: u32, pub written_pixels: u32, pub foreign_pixels: u32, pub unshaded_pixels: u32,
+    pub stale_pixels: u32, pub degenerate_pixels: u32, pub _pad: [u32; 2],
+}
+
+/// orbit_surface_fragments' argument block (176 B, HOST): DEVICE pointers; bary, grad and triangle as a surface call left
+/// them (grad may be null, then uv_grad is); the six outputs and stats may be null, not all six.  MeshVertex (mesh.rs:14-20)
+/// is vertex_stride 32 with position / normal / uv / tangent at 0 / 12 / 16 / 24
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitSurfaceFragments {
+    pub visibility: *const u64, pub draw_commands: *const c_void, pub meshlets: *const c_void,
+    pub bary: *const f32, pub grad: *const f32, pub triangle: *const u32,
+    pub vertices: *const c_void, pub entity_data: *const c_void,
+    pub world_pos: *mut f32, pub normal: *mut f32, pub tangent: *mut f32, pub uv: *mut f32, pub uv_grad: *mut f32,
+    pub material: *mut u32, pub stats: *mut OrbitFragmentStats,
+    pub vertex_count: u64,
+    pub meshlet_count: u32, pub max_commands: u32, pub entity_count: u32, pub vertex_stride: u32,
+    pub position_offset: u32, pub normal_offset: u32, pub uv_offset: u32, pub tangent_offset: u32,
+    pub width: u32, pub height: u32, pub flags: u32, pub command_base: u32,
+}
+
 /// orbit_visibility_resolve's argument block (48 B, HOST): DEVICE pointers; each output may be null, not all
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct OrbitVisibilityResolve {
@@ -420,6 +446,7 @@ extern "C" {
     /// (S1-S7): what a renderer shades from, by the raster's own rules.
     pub fn orbit_visibility_surface(ctx: *mut OrbitCtx, job: *const OrbitVisibilitySurface, stream: *mut c_void) -> i32;
     pub fn orbit_visibility_surface_drawn(ctx: *mut OrbitCtx, job: *const OrbitVisibilitySurface, raster_flags: u32, stream: *mut c_void) -> i32;
+    pub fn orbit_surface_fragments(ctx: *mut OrbitCtx, job: *const OrbitSurfaceFragments, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

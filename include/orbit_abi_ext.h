@@ -235,8 +235,9 @@ int32_t orbit_ctx_set_raster_grid(OrbitCtx *ctx, uint32_t max_workgroups);
  * prepared call follows it too.  0, the default, restores the sized grid.  The outputs do not depend on the grid; the
  * shard launch and every other launch are not touched. */
 int32_t orbit_ctx_set_fused_grid(OrbitCtx *ctx, uint32_t max_workgroups);
-/* Tests: the strided launches of the visibility buffer's three readers — orbit_visibility_resolve's clear and its tile
- * walk, orbit_visibility_compact's clear and its mark, orbit_visibility_surface's clear and its tile walk — take at most
+/* Tests: the strided launches of the visibility buffer's four readers — orbit_visibility_resolve's clear and its tile
+ * walk, orbit_visibility_compact's clear and its mark, orbit_visibility_surface's clear and its tile walk (and
+ * orbit_visibility_surface_drawn's), orbit_surface_fragments' clear and its tile walk — take at most
  * `max_workgroups` workgroups (of four waves; a wave takes its 8 x 8 tiles one after another, so under a cap of c wave g
  * takes tiles g, g + 4c, ... of even a small target).  Read when the call is enqueued: a captured launch carries its
  * grid.  0, the default, restores num_cus * 8.  The outputs do not depend on the grid; the compaction's scan, totals and
@@ -1438,6 +1439,122 @@ int32_t orbit_visibility_surface(OrbitCtx *ctx, const OrbitVisibilitySurface *jo
 /* captures the call on a fresh context's first call.                       */
 /* ------------------------------------------------------------------------ */
 int32_t orbit_visibility_surface_drawn(OrbitCtx *ctx, const OrbitVisibilitySurface *job, uint32_t raster_flags, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* The fragment inputs of a visibility buffer.  orbit_surface_fragments      */
+/* reads a buffer, the list that made it, what a surface call left (bary,   */
+/* grad, triangle) and the vertex attributes, and writes, for each pixel    */
+/* the list owns, what the reference's fragment shader receives: the        */
+/* VERTEX_OUTPUT block of shaders/forward/forward_common.glsl:22-28         */
+/* (world_pos, uv, normal, tangent, flat material_index) and the dFdx /     */
+/* dFdy of uv (forward.frag:250-251).  ONE definition for the device and    */
+/* the host mirror (orbit_host_surface_fragments); the two agree on every   */
+/* byte of every output.  Float arithmetic as in R2-R7 and S1-S7: fp32,     */
+/* round to nearest, every operation rounded on its own, never contracted,  */
+/* IEEE divides and square roots.                                           */
+/*  F1 ownership is S1's decode: n = min(count, max_commands), the count    */
+/*     read ON THE DEVICE.  A word of 0 is uncovered; k = id - command_base */
+/*     (u32, wrapping) >= n is a FOREIGN pixel.  Neither is written: a      */
+/*     frame's two lists are two calls with two bases into the same         */
+/*     outputs, the second without ORBIT_FRAGMENTS_CLEAR.                   */
+/*  F2 consistency of an owned pixel p of command k, with T = triangle[p] = */
+/*     (entity, g0, g1, g2).  T.entity == 0xFFFFFFFF: the surface call left */
+/*     the pixel out (unsupported or stale there, under its clear); the     */
+/*     pixel is UNSHADED: not written, the status stays OK.  Otherwise the  */
+/*     pixel is STALE, ORBIT_E_RANGE is latched and it is not written, if   */
+/*     T.entity >= entity_count, T.entity != cmd[k].cmd_first_instance,     */
+/*     some g_i >= vertex_count, or cmd[k].meshlet_index >= meshlet_count.  */
+/*     Nothing is read before it is known to be in range.                   */
+/*  F3 the vertex stage of corner c = 0, 1, 2 (forward.vert:15-30).  pos: 3 */
+/*     floats at g_c * vertex_stride + position_offset; n_c = snorm8 of 3   */
+/*     int8 at normal_offset (its 4 bytes are read, the fourth is not       */
+/*     used); t_c = snorm8 of 4 int8 at tangent_offset; uv_c: 2 floats at   */
+/*     uv_offset.  snorm8(i) = (float)i * 0x3C010204 (the float of those    */
+/*     bits: the canonical one of the cull path); -128 is NOT clamped, as   */
+/*     forward.vert:26 does not clamp.  wp_c = model_matrix x (pos, 1) by   */
+/*     R2's clip_position expression: component r = ((m[r] * x + m[4 + r] * */
+/*     y) + m[8 + r] * z) + m[12 + r] * 1.0f.  M3 x v, with M3 rows and     */
+/*     columns 0..2 of normal_matrix: component r = (m[r] * x + m[4 + r] *  */
+/*     y) + m[8 + r] * z.  normalize(v) = v / sqrtf((x * x + y * y) + z *   */
+/*     z), component by component.  GLSL LEAVES Normalize's PRECISION TO    */
+/*     THE DRIVER: THIS EXPRESSION IS THIS PROJECT'S CHOICE.  N_c =         */
+/*     normalize(M3 x n_c); T_c = (normalize(M3 x t_c.xyz), t_c.w).         */
+/*  F4 interpolation: (l1, l2) = bary[p]; l0 = (1.0f - l1) - l2, and l0 <   */
+/*     0.0f becomes +0.0f.  Every component a of world_pos (4), normal (3), */
+/*     tangent (4) and uv (2) is (a_0 * l0 + a_1 * l1) + a_2 * l2.  The     */
+/*     normal is NOT renormalised (forward.frag:280 uses it as it arrives). */
+/*  F5 uv_grad[p] = (du/dx, dv/dx, du/dy, dv/dy): with grad[p] = (a, b, c,  */
+/*     d), d/dx = (uv_1 - uv_0) * a + (uv_2 - uv_0) * b per component, d/dy */
+/*     the same with c, d.  The edge form keeps large uv values from        */
+/*     cancelling.  With grad NULL (uv_grad is then NULL too) nothing of it */
+/*     is read and the four floats are +0.0f.                               */
+/*  F6 material[p] = meshlets[cmd[k].meshlet_index].material_index, widened */
+/*     to u32 (forward.vert:32-33).  render_mode 9 is not served.           */
+/*  F7 no non-finite bytes, as S5: any of the 17 floats that is not finite  */
+/*     is written as +0.0f, and the pixel counts once in degenerate_pixels; */
+/*     it is still written and still counted in written_pixels.  All 17     */
+/*     floats are evaluated whichever outputs are given: no counter depends */
+/*     on a NULL output.                                                    */
+/*  F8 ORBIT_FRAGMENTS_CLEAR first fills the given float outputs with       */
+/*     +0.0f and material with 0xFFFFFFFF.  stats (may be NULL) is cleared  */
+/*     by the call; covered_pixels = written + foreign + unshaded + stale.  */
+/*     Every output depends on its own pixel only: independent of           */
+/*     scheduling.                                                          */
+/* The reference's MeshVertex (types.glsl:64-73, assets/mesh.rs:14-20) is   */
+/* vertex_stride 32 with position, normal, uv, tangent at 0 / 12 / 16 / 24. */
+/* Only the attributes' own bytes are read (12 + 4 + 8 + 4 per vertex): a   */
+/* buffer may end with the last attribute of its last vertex.               */
+/*   ORBIT_E_INVALID  (message prefix surface_fragments:) job, visibility,  */
+/*                    draw_commands, meshlets, bary, triangle, vertices or  */
+/*                    entity_data NULL; all six outputs NULL; uv_grad given */
+/*                    with grad NULL; a pointer misaligned (visibility: 8   */
+/*                    B, entity_data: 16 B, the rest: 4 B); vertex_stride   */
+/*                    or an offset no multiple of 4; vertex_stride smaller  */
+/*                    than an attribute's offset + size (12, 4, 8, 4);      */
+/*                    width or height 0 or above ORBIT_RASTER_MAX_DIM;      */
+/*                    command_base + max_commands > ORBIT_VIS_MAX_COMMANDS; */
+/*                    vertex_count > 2^32; unknown flags; an output pointer */
+/*                    equal to an input pointer.  All checked before the    */
+/*                    context is looked at.                                 */
+/* Kernel launches only: no allocation, no scratch, no host wait; a graph   */
+/* captures the call on a fresh context's first call.                       */
+/* ------------------------------------------------------------------------ */
+#define ORBIT_FRAGMENTS_CLEAR 1u /* flags: fill the given outputs first (F8) */
+typedef struct OrbitFragmentStats { /* DEVICE, 32 B, cleared by the call */
+    uint32_t covered_pixels, written_pixels, foreign_pixels, unshaded_pixels, stale_pixels, degenerate_pixels;
+    uint32_t _pad[2];
+} OrbitFragmentStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitFragmentStats) == 32, "FragmentStats is 32 B");
+typedef struct OrbitSurfaceFragments { /* HOST block, 176 B; every pointer a DEVICE pointer */
+    const uint64_t *visibility;         /* width * height u64, as orbit_raster_visibility left it */
+    const void *draw_commands;          /* the list that was rasterised with this command_base */
+    const OrbitMeshlet *meshlets;       /* meshlet_count records of 32 B; only material_index is read */
+    const float *bary;                  /* 2 floats per pixel, as a surface call left them */
+    const float *grad;                  /* NULL (then uv_grad is NULL), or 4 floats per pixel */
+    const uint32_t *triangle;           /* 4 words per pixel: (entity, g0, g1, g2) */
+    const void *vertices;
+    const OrbitEntityData *entity_data;
+    float *world_pos;                   /* NULL, or 4 floats per pixel */
+    float *normal;                      /* NULL, or 3 floats per pixel */
+    float *tangent;                     /* NULL, or 4 floats per pixel */
+    float *uv;                          /* NULL, or 2 floats per pixel */
+    float *uv_grad;                     /* NULL, or 4 floats per pixel: du/dx, dv/dx, du/dy, dv/dy */
+    uint32_t *material;                 /* NULL, or 1 word per pixel */
+    OrbitFragmentStats *stats;          /* NULL, or the counters */
+    uint64_t vertex_count;
+    uint32_t meshlet_count, max_commands, entity_count, vertex_stride, position_offset, normal_offset, uv_offset,
+        tangent_offset, width, height, flags, command_base;
+} OrbitSurfaceFragments;
+ORBIT_STATIC_ASSERT(sizeof(OrbitSurfaceFragments) == 176, "SurfaceFragments is 176 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSurfaceFragments, bary) == 24, "bary @24");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSurfaceFragments, world_pos) == 64, "world_pos @64");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSurfaceFragments, stats) == 112, "stats @112");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSurfaceFragments, vertex_count) == 120, "vertex_count @120");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSurfaceFragments, vertex_stride) == 140, "vertex_stride @140");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSurfaceFragments, command_base) == 172, "command_base @172");
+
+/* forward.frag's inputs of every pixel the list owns; see above */
+int32_t orbit_surface_fragments(OrbitCtx *ctx, const OrbitSurfaceFragments *job, void *stream);
 
 #ifdef __cplusplus
 }

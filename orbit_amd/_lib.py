@@ -146,6 +146,20 @@ class VisibilitySurface(C.Structure):  # OrbitVisibilitySurface (184 B)
 SURFACE_CLEAR = 1  # ORBIT_SURFACE_CLEAR
 
 
+class SurfaceFragments(C.Structure):  # OrbitSurfaceFragments (176 B)
+    _fields_ = [("visibility", C.c_void_p), ("draw_commands", C.c_void_p), ("meshlets", C.c_void_p), ("bary", C.c_void_p),
+                ("grad", C.c_void_p), ("triangle", C.c_void_p), ("vertices", C.c_void_p), ("entity_data", C.c_void_p),
+                ("world_pos", C.c_void_p), ("normal", C.c_void_p), ("tangent", C.c_void_p), ("uv", C.c_void_p),
+                ("uv_grad", C.c_void_p), ("material", C.c_void_p), ("stats", C.c_void_p), ("vertex_count", C.c_uint64),
+                ("meshlet_count", C.c_uint32), ("max_commands", C.c_uint32), ("entity_count", C.c_uint32),
+                ("vertex_stride", C.c_uint32), ("position_offset", C.c_uint32), ("normal_offset", C.c_uint32),
+                ("uv_offset", C.c_uint32), ("tangent_offset", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("flags", C.c_uint32), ("command_base", C.c_uint32)]
+
+
+FRAGMENTS_CLEAR = 1  # ORBIT_FRAGMENTS_CLEAR
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -251,6 +265,7 @@ SYMBOLS = {
     "orbit_visibility_compact": (C.c_int32, [C.c_void_p, C.POINTER(VisibilityCompact), C.c_void_p]),
     "orbit_visibility_surface": (C.c_int32, [C.c_void_p, C.POINTER(VisibilitySurface), C.c_void_p]),
     "orbit_visibility_surface_drawn": (C.c_int32, [C.c_void_p, C.POINTER(VisibilitySurface), C.c_uint32, C.c_void_p]),
+    "orbit_surface_fragments": (C.c_int32, [C.c_void_p, C.POINTER(SurfaceFragments), C.c_void_p]),
 }
 
 _lib = None

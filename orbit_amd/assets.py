@@ -71,3 +71,25 @@ def meshlet_triangles(meshlet, meshlet_data):
     verts = meshlet_data[d0:d0 + nv]
     corners = meshlet_data.view(np.uint8)[(d0 + nv) * 4:(d0 + nv) * 4 + 3 * nt].reshape(nt, 3)
     return verts[corners]
+
+
+def pack_snorm8(values):
+    """pack_f32_to_snorm_u8 (math.rs:201-203) of an array: clamp to [-1, 1], times 127 in float32, truncated toward zero;
+    NaN -> 0 (Rust's `as i8`)."""
+    f = np.asarray(values, dtype=np.float32)
+    scaled = np.clip(f, np.float32(-1.0), np.float32(1.0)) * np.float32(127.0)
+    return np.where(np.isnan(f), np.float32(0.0), np.trunc(scaled)).astype(np.int8)
+
+
+def pack_mesh_vertices(positions, normals, uvs, tangents):
+    """GpuMeshVertex::new (assets/mesh.rs:23-31) of n vertices -> np[layouts.MESH_VERTEX] rows of 32 B: positions (n, 3)
+    and uvs (n, 2) as float32, normals (n, 3) and tangents (n, 4) through pack_snorm8; the normal's fourth byte and the
+    padding are 0.  What orbit_surface_fragments reads with vertex_stride 32 and offsets 0 / 12 / 16 / 24."""
+    pos = np.asarray(positions, dtype=np.float32).reshape(-1, 3)
+    n = len(pos)
+    out = np.zeros(n, L.MESH_VERTEX)
+    out["position"] = pos
+    out["normal"][:, :3] = pack_snorm8(np.asarray(normals, dtype=np.float32).reshape(n, 3))
+    out["uv"] = np.asarray(uvs, dtype=np.float32).reshape(n, 2)
+    out["tangent"] = pack_snorm8(np.asarray(tangents, dtype=np.float32).reshape(n, 4))
+    return out

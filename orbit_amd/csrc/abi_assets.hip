@@ -4,7 +4,9 @@
 // orbit_visibility_resolve, the same pass keeping the winner's identity and its resolve (raster_visibility.hip), and
 // orbit_visibility_compact, the visible draw list of such a buffer (visibility_compact.hip), and
 // orbit_visibility_surface, its barycentrics, differences and ids per pixel (visibility_surface.hip), with
-// orbit_visibility_surface_drawn, the same for a buffer drawn with the raster flags (visibility_surface_drawn.hip).
+// orbit_visibility_surface_drawn, the same for a buffer drawn with the raster flags (visibility_surface_drawn.hip), and
+// orbit_surface_fragments, the fragment shader's inputs per pixel from those and the vertex attributes
+// (surface_fragments.hip).
 #include "abi_internal.h"
 
 namespace {
@@ -245,6 +247,50 @@ int32_t orbit_visibility_surface_drawn(OrbitCtx *ctx, const OrbitVisibilitySurfa
                              : launch_visibility_surface_drawn(*job, raster_flags, ctx->num_cus, ctx->visibility_grid, ctx->status,
                                                                (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch visibility_surface_drawn");
+    return ORBIT_OK;
+}
+
+// A clearing launch (stats, and the outputs with ORBIT_FRAGMENTS_CLEAR) and the fragment launch (surface_fragments.hip);
+// the command count stays on the device.  No allocation, no scratch, no host sync: capturable on the first call.  As its
+// siblings, the job is checked before the context is looked at, each error with a message of its own.
+int32_t orbit_surface_fragments(OrbitCtx *ctx, const OrbitSurfaceFragments *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "surface_fragments: job is NULL");
+    const OrbitSurfaceFragments &j = *job;
+    if (j.flags & ~ORBIT_FRAGMENTS_CLEAR) return fail(ctx, ORBIT_E_INVALID, "surface_fragments: flags %#x", j.flags);
+    if ((j.vertex_stride | j.position_offset | j.normal_offset | j.uv_offset | j.tangent_offset) & 3u)
+        return fail(ctx, ORBIT_E_INVALID, "surface_fragments: vertex_stride %u, offsets %u / %u / %u / %u (multiples of 4)", j.vertex_stride,
+                    j.position_offset, j.normal_offset, j.uv_offset, j.tangent_offset);
+    if ((uint64_t)j.vertex_stride < (uint64_t)j.position_offset + 12u || (uint64_t)j.vertex_stride < (uint64_t)j.normal_offset + 4u ||
+        (uint64_t)j.vertex_stride < (uint64_t)j.uv_offset + 8u || (uint64_t)j.vertex_stride < (uint64_t)j.tangent_offset + 4u)
+        return fail(ctx, ORBIT_E_INVALID, "surface_fragments: vertex_stride %u below an attribute's end (position %u + 12, normal %u + 4, uv %u + 8, tangent %u + 4)",
+                    j.vertex_stride, j.position_offset, j.normal_offset, j.uv_offset, j.tangent_offset);
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "surface_fragments: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS)
+        return fail(ctx, ORBIT_E_INVALID, "surface_fragments: command_base %u + max_commands %u > %u (24 bits of id)", j.command_base,
+                    j.max_commands, ORBIT_VIS_MAX_COMMANDS);
+    if (j.vertex_count > (1ull << 32))
+        return fail(ctx, ORBIT_E_INVALID, "surface_fragments: vertex_count %llu > 2^32 (a global vertex is a u32)",
+                    (unsigned long long)j.vertex_count);
+    if (!j.visibility || !j.draw_commands || !j.meshlets || !j.bary || !j.triangle || !j.vertices || !j.entity_data)
+        return fail(ctx, ORBIT_E_INVALID, "surface_fragments: NULL buffer");
+    if (!j.world_pos && !j.normal && !j.tangent && !j.uv && !j.uv_grad && !j.material)
+        return fail(ctx, ORBIT_E_INVALID, "surface_fragments: no output");
+    if (j.uv_grad && !j.grad) return fail(ctx, ORBIT_E_INVALID, "surface_fragments: uv_grad needs grad");
+    const void *const inputs[8] = {j.visibility, j.draw_commands, j.meshlets, j.bary, j.grad, j.triangle, j.vertices, j.entity_data};
+    const void *const outputs[7] = {j.world_pos, j.normal, j.tangent, j.uv, j.uv_grad, j.material, j.stats};
+    uintptr_t low_bits = 0;
+    for (const void *in : inputs) low_bits |= (uintptr_t)in;
+    for (const void *out : outputs) low_bits |= (uintptr_t)out;
+    if (((uintptr_t)j.visibility & 7u) || ((uintptr_t)j.entity_data & 15u) || (low_bits & 3u))
+        return fail(ctx, ORBIT_E_INVALID, "surface_fragments: visibility must be 8-B aligned, entity_data 16-B aligned, every other buffer 4-B aligned");
+    for (const void *out : outputs)
+        for (const void *in : inputs)
+            if (out && out == in) return fail(ctx, ORBIT_E_INVALID, "surface_fragments: an output is an input (%p)", out);
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "surface_fragments: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_surface_fragments(j, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch surface_fragments");
     return ORBIT_OK;
 }
 

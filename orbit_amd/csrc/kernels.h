@@ -446,6 +446,10 @@ hipError_t launch_visibility_surface(const OrbitVisibilitySurface &job, uint32_t
 // launch following the pieces of R3c and the wide setups of R4w (S2d, S3c, S3w)
 hipError_t launch_visibility_surface_drawn(const OrbitVisibilitySurface &job, uint32_t raster_flags, uint32_t num_cus,
                                            uint32_t grid_cap, int32_t *status, hipStream_t s);
+// surface_fragments.hip: orbit_surface_fragments — `job` validated by the entry point.  One launch clears stats and, with
+// ORBIT_FRAGMENTS_CLEAR, fills the outputs; the next reads every word once, a wave per 8 x 8 tile, a lane per pixel
+hipError_t launch_surface_fragments(const OrbitSurfaceFragments &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
+                                    hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

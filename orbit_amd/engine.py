@@ -474,6 +474,33 @@ class Engine:
         flags = (_lib.RASTER_CLIP_NEAR if clip_near else 0) | (_lib.RASTER_WIDE_GUARD if wide_guard else 0)
         self.visibility_surface(*args, raster_flags=flags, **kwargs)
 
+    # -- forward.frag's inputs per pixel of a visibility buffer and its surface (orbit_surface_fragments)
+    def surface_fragments(self, visibility, width, height, draw_commands, max_commands, meshlets, meshlet_count, bary, triangle,
+                          vertices, vertex_count, entity_data, entity_count, grad=None, world_pos=None, normal=None,
+                          tangent=None, uv=None, uv_grad=None, material=None, stats=None, command_base=0, clear=False,
+                          vertex_stride=32, position_offset=0, normal_offset=12, uv_offset=16, tangent_offset=24,
+                          stream=None):
+        """From the width x height u64 tensor `visibility`, the list that was rasterised into it with `command_base`, what
+        visibility_surface[_drawn] left for that list (bary, triangle, and grad when uv_grad is wanted), the 32-B meshlet
+        records and the vertex rows (the reference's MeshVertex by default: stride 32, position / snorm8 normal / uv /
+        snorm8 tangent at 0 / 12 / 16 / 24) to the inputs of the reference's fragment shader for every pixel the list
+        owns: world_pos (4 floats per pixel), normal (3, not renormalised), tangent (4), uv (2), uv_grad (4: du/dx, dv/dx,
+        du/dy, dv/dy) and material (1 u32).  Each may be None, not all.  Uncovered pixels, pixels of another list and
+        pixels the surface call left out (unshaded_pixels) are not written; clear=True (ORBIT_FRAGMENTS_CLEAR) fills the
+        outputs first (0.0, 0xFFFFFFFF).  stats (32 bytes, layouts.SURFACE_FRAGMENT_STATS, cleared by the call).  A pixel
+        whose triangle record does not fit the list is counted in stale_pixels and reported by status()
+        (ORBIT_E_RANGE).  Byte-equal to orbit_amd.raster.host_surface_fragments.  Enqueued on `stream`."""
+        j = _lib.SurfaceFragments()
+        j.visibility, j.draw_commands, j.meshlets = _ptr(visibility), _ptr(draw_commands), _ptr(meshlets)
+        j.bary, j.grad, j.triangle, j.vertices, j.entity_data = _ptr(bary), _ptr(grad), _ptr(triangle), _ptr(vertices), _ptr(entity_data)
+        j.world_pos, j.normal, j.tangent, j.uv = _ptr(world_pos), _ptr(normal), _ptr(tangent), _ptr(uv)
+        j.uv_grad, j.material, j.stats = _ptr(uv_grad), _ptr(material), _ptr(stats)
+        j.vertex_count, j.meshlet_count, j.max_commands, j.entity_count = int(vertex_count), int(meshlet_count), int(max_commands), int(entity_count)
+        j.vertex_stride, j.position_offset, j.normal_offset = int(vertex_stride), int(position_offset), int(normal_offset)
+        j.uv_offset, j.tangent_offset, j.width, j.height = int(uv_offset), int(tangent_offset), int(width), int(height)
+        j.flags, j.command_base = _lib.FRAGMENTS_CLEAR if clear else 0, int(command_base)
+        _lib.check(self._lib.orbit_surface_fragments(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                    entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,

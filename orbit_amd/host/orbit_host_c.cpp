@@ -618,6 +618,13 @@ int32_t orbit_host_visibility_surface_drawn(const OrbitVisibilitySurface *job, u
     });
 }
 
+int32_t orbit_host_surface_fragments(const OrbitSurfaceFragments *job, int32_t *status) {
+    return guarded([&] {
+        if (!job) throw Panic("surface_fragments: job is NULL");
+        raster::surface_fragments(*job, status);
+    });
+}
+
 // ---------------------------------------------------------------- asset ingestion (orbit_gltf.hpp), host only
 void *orbit_host_gltf_load(const char *path) {
     gltf_loader::LoadedScene *scene = nullptr;

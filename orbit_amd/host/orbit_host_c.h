@@ -255,6 +255,10 @@ int32_t orbit_host_visibility_surface(const OrbitVisibilitySurface *job, int32_t
 /* the reference of orbit_visibility_surface_drawn (S2d, S3c, S3w): as above, with the raster flags the buffer was drawn
  * with (ORBIT_RASTER_CLIP_NEAR | ORBIT_RASTER_WIDE_GUARD; any other bit is ORBIT_HOST_PANIC) */
 int32_t orbit_host_visibility_surface_drawn(const OrbitVisibilitySurface *job, uint32_t raster_flags, int32_t *status);
+/* the reference of orbit_surface_fragments (F1-F8): the device call's block with HOST pointers in it.  Every output holds
+ * the device's bytes.  *status (may be NULL): ORBIT_E_RANGE if a pixel was stale, else ORBIT_OK.  ORBIT_HOST_PANIC for
+ * what the device answers with ORBIT_E_INVALID (alignment and aliasing aside). */
+int32_t orbit_host_surface_fragments(const OrbitSurfaceFragments *job, int32_t *status);
 
 /* ---- asset ingestion (orbit_gltf.hpp): glTF 2.0 (.glb / .gltf) -> materials, meshes with their LOD chains, entities ----
  * load_gltf (gltf_loader.rs:511-676) + GpuAssets::add_mesh (assets/mod.rs:325-476).  NULL + orbit_host_last_error()

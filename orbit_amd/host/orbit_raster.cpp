@@ -5,6 +5,7 @@
 
 #include "../csrc/raster_common.h"
 #include "../csrc/surface_common.h"
+#include "../csrc/fragment_common.h"
 #include "orbit_host.hpp"
 
 namespace orbit {
@@ -377,6 +378,62 @@ void visibility_surface_drawn(const OrbitVisibilitySurface &j, uint32_t raster_f
         if (j.bary) std::memcpy(j.bary + 2 * p, out, 8);
         if (j.grad) std::memcpy(j.grad + 4 * p, out + 2, 16);
         if (j.triangle) std::memcpy(j.triangle + 4 * p, tri.ids, 16);
+    }
+    if (j.stats) *j.stats = st;
+    if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
+}
+
+void surface_fragments(const OrbitSurfaceFragments &j, int32_t *status) {
+    if (j.flags & ~ORBIT_FRAGMENTS_CLEAR) throw Panic("surface_fragments: unknown flags");
+    if (!j.visibility || !j.draw_commands || !j.meshlets || !j.bary || !j.triangle || !j.vertices || !j.entity_data)
+        throw Panic("surface_fragments: NULL argument");
+    if (!j.world_pos && !j.normal && !j.tangent && !j.uv && !j.uv_grad && !j.material) throw Panic("surface_fragments: no output");
+    if (j.uv_grad && !j.grad) throw Panic("surface_fragments: uv_grad needs grad");
+    if ((j.vertex_stride | j.position_offset | j.normal_offset | j.uv_offset | j.tangent_offset) & 3u)
+        throw Panic("surface_fragments: vertex_stride / offsets no multiples of 4");
+    if ((uint64_t)j.vertex_stride < (uint64_t)j.position_offset + 12u || (uint64_t)j.vertex_stride < (uint64_t)j.normal_offset + 4u ||
+        (uint64_t)j.vertex_stride < (uint64_t)j.uv_offset + 8u || (uint64_t)j.vertex_stride < (uint64_t)j.tangent_offset + 4u)
+        throw Panic("surface_fragments: vertex_stride below an attribute's end");
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        throw Panic("surface_fragments: target size");
+    if ((uint64_t)j.command_base + j.max_commands > ORBIT_VIS_MAX_COMMANDS) throw Panic("surface_fragments: command_base + max_commands");
+    if (j.vertex_count > (1ull << 32)) throw Panic("surface_fragments: vertex_count > 2^32");
+    const size_t pixels = (size_t)j.width * j.height;
+    if (j.flags & ORBIT_FRAGMENTS_CLEAR) { // F8
+        if (j.world_pos) std::memset(j.world_pos, 0, pixels * 16);
+        if (j.normal) std::memset(j.normal, 0, pixels * 12);
+        if (j.tangent) std::memset(j.tangent, 0, pixels * 16);
+        if (j.uv) std::memset(j.uv, 0, pixels * 8);
+        if (j.uv_grad) std::memset(j.uv_grad, 0, pixels * 16);
+        if (j.material) std::memset(j.material, 0xFF, pixels * 4);
+    }
+    const uint32_t *commands = static_cast<const uint32_t *>(j.draw_commands);
+    const uint32_t n = commands[0] < j.max_commands ? commands[0] : j.max_commands;
+    OrbitFragmentStats st{};
+    for (size_t p = 0; p < pixels; p++) {
+        const uint64_t word = j.visibility[p];
+        if (word == 0) continue;
+        st.covered_pixels++;
+        const uint32_t id = (uint32_t)(word >> 8) & 0xFFFFFFu;
+        if (id < j.command_base || id - j.command_base >= n) { // F1
+            st.foreign_pixels++;
+            continue;
+        }
+        float out[kFragmentFloats];
+        uint32_t material;
+        bool degenerate;
+        const uint32_t verdict = fragment_pixel(j, id - j.command_base, p, out, material, degenerate);
+        if (verdict == kFragmentUnshaded) st.unshaded_pixels++;
+        if (verdict == kFragmentStale) st.stale_pixels++;
+        if (verdict != kFragmentWritten) continue;
+        st.written_pixels++;
+        if (degenerate) st.degenerate_pixels++;
+        if (j.world_pos) std::memcpy(j.world_pos + 4 * p, out, 16);
+        if (j.normal) std::memcpy(j.normal + 3 * p, out + 4, 12);
+        if (j.tangent) std::memcpy(j.tangent + 4 * p, out + 7, 16);
+        if (j.uv) std::memcpy(j.uv + 2 * p, out + 11, 8);
+        if (j.uv_grad) std::memcpy(j.uv_grad + 4 * p, out + 13, 16);
+        if (j.material) j.material[p] = material;
     }
     if (j.stats) *j.stats = st;
     if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;

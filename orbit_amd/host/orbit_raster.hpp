@@ -56,5 +56,10 @@ void visibility_surface(const OrbitVisibilitySurface &job, int32_t *status);
 // ORBIT_RASTER_CLIP_NEAR | ORBIT_RASTER_WIDE_GUARD; 0 gives visibility_surface's bytes.
 void visibility_surface_drawn(const OrbitVisibilitySurface &job, uint32_t raster_flags, int32_t *status);
 
+// orbit_surface_fragments (F1-F8, §4.24) on host buffers: the job's pointers are HOST pointers.  The obvious loop over
+// the pixels, each through ../csrc/fragment_common.h.  *status (may be null) = what the device call latches: ORBIT_E_RANGE
+// if a pixel was stale, else ORBIT_OK.  Throws Panic for ORBIT_E_INVALID (alignment and aliasing aside).
+void surface_fragments(const OrbitSurfaceFragments &job, int32_t *status);
+
 } // namespace raster
 } // namespace orbit

@@ -69,6 +69,12 @@ SURFACE_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "written_pixels
                                                "stale_pixels", "degenerate_pixels", "_pad0", "_pad1")])
 # the same 32 bytes as orbit_visibility_surface_drawn fills them: the last two words are its own counters
 SURFACE_DRAWN_STATS = np.dtype([(n, "<u4") for n in SURFACE_STATS.names[:6] + ("cut_pixels", "wide_pixels")])
+# OrbitFragmentStats: the counters of orbit_surface_fragments
+SURFACE_FRAGMENT_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "written_pixels", "foreign_pixels", "unshaded_pixels",
+                                                        "stale_pixels", "degenerate_pixels", "_pad0", "_pad1")])
+# types.glsl:64-73, src/assets/mesh.rs:14-20: the reference's MeshVertex, 32 B (normal and tangent as snorm8)
+MESH_VERTEX = np.dtype([("position", "<f4", (3,)), ("normal", "i1", (4,)), ("uv", "<f4", (2,)), ("tangent", "i1", (4,)),
+                        ("_padding", "<u4")])
 # types.glsl:92-110, src/assets/mod.rs:171-191
 MATERIAL = np.dtype([
     ("base_color", "<f4", (4,)), ("emissive_factor", "<f4", (3,)), ("metallic_factor", "<f4"),

@@ -3,8 +3,9 @@
 host arrays, the same pass keeping the winner's identity and its resolve — the references of ``Engine.raster_depth``,
 ``Engine.raster_visibility`` and ``Engine.visibility_resolve`` — and of ``orbit_visibility_compact``, the visible draw
 list of such a buffer, the reference of ``Engine.visibility_compact``, and of ``orbit_visibility_surface``, the
-barycentrics and ids per pixel of such a buffer, the reference of ``Engine.visibility_surface``.  Python adds nothing;
-host only."""
+barycentrics and ids per pixel of such a buffer, the reference of ``Engine.visibility_surface``, and of
+``orbit_surface_fragments``, the fragment shader's inputs per pixel from those, the reference of
+``Engine.surface_fragments``.  Python adds nothing; host only."""
 import ctypes as C
 
 import numpy as np
@@ -187,3 +188,61 @@ def host_visibility_surface_drawn(*args, clip_near=False, wide_guard=False, rast
     itself.  stats: np[layouts.SURFACE_DRAWN_STATS].  Neither flag: host_visibility_surface's bytes."""
     flags = (CLIP_NEAR if clip_near else 0) | (WIDE_GUARD if wide_guard else 0) if raster_flags is None else int(raster_flags)
     return host_visibility_surface(*args, _drawn=flags, **kwargs)
+
+
+FRAGMENT_OUTPUTS = (("world_pos", 4, np.float32), ("normal", 3, np.float32), ("tangent", 4, np.float32), ("uv", 2, np.float32),
+                    ("uv_grad", 4, np.float32), ("material", 1, np.uint32))
+
+
+def host_surface_fragments(visibility, draw_commands, max_commands, meshlets, surface, vertices, vertex_count, entity_data,
+                           command_base=0, clear=True, into=None, want=tuple(n for n, _, _ in FRAGMENT_OUTPUTS),
+                           vertex_stride=32, position_offset=0, normal_offset=12, uv_offset=16, tangent_offset=24,
+                           entity_count=None, meshlet_count=None, fill=0, want_stats=True):
+    """orbit_host_surface_fragments on a (height, width) np.uint64 buffer, the {count; commands} words that were
+    rasterised into it, the 32-B meshlet records, `surface` (the dict of host_visibility_surface[_drawn]: bary, triangle
+    and, may be None, grad) and the vertex rows -> dict(world_pos (height, width, 4), normal (.., 3), tangent (.., 4), uv
+    (.., 2), uv_grad (.., 4) np.float32, material (.., 1) np.uint32, each None unless named in `want`; stats:
+    np[layouts.SURFACE_FRAGMENT_STATS] scalar row or None; status: what the device call latches).  `into`: the dict of an
+    earlier call to write into (copied): a frame's second list, clear=False.  Otherwise every output starts filled with
+    the u32 `fill`: what the call does not write keeps it."""
+    vis = np.ascontiguousarray(visibility, dtype=np.uint64)
+    height, width = vis.shape
+    buf = np.ascontiguousarray(draw_commands).view(np.uint8).reshape(-1)
+    if buf.nbytes < 4 + 28 * int(max_commands):
+        raise ValueError("max_commands reaches beyond the command array")
+    mlt = np.ascontiguousarray(meshlets).view(np.uint8).reshape(-1)
+    meshlet_count = mlt.nbytes // 32 if meshlet_count is None else int(meshlet_count)
+    if meshlet_count and (meshlet_count - 1) * 32 + 30 > mlt.nbytes:
+        raise ValueError("meshlet_count reaches beyond the meshlet array")
+    vb = np.ascontiguousarray(vertices).view(np.uint8).reshape(-1)
+    ends = (int(position_offset) + 12, int(normal_offset) + 4, int(uv_offset) + 8, int(tangent_offset) + 4)
+    if int(vertex_count) and (int(vertex_count) - 1) * int(vertex_stride) + max(ends) > vb.nbytes:
+        raise ValueError("vertex_count reaches beyond the vertex array")
+    ent = np.ascontiguousarray(entity_data).view(np.uint8).reshape(-1)
+    shaped = lambda a, per, dtype: None if a is None else np.ascontiguousarray(a, dtype=dtype).reshape(height, width, per)  # noqa: E731
+    bary, grad, tri = shaped(surface["bary"], 2, np.float32), shaped(surface.get("grad"), 4, np.float32), shaped(surface["triangle"], 4, np.uint32)
+    if bary is None or tri is None:
+        raise ValueError("surface needs bary and triangle")
+    outs = {}
+    for name, per_pixel, dtype in FRAGMENT_OUTPUTS:
+        if name not in want:
+            outs[name] = None
+        elif into is not None:
+            outs[name] = np.array(into[name], dtype=dtype, order="C").reshape(height, width, per_pixel)
+        else:
+            outs[name] = np.full((height, width, per_pixel), fill, np.uint32).view(dtype)
+    stats = np.zeros(1, L.SURFACE_FRAGMENT_STATS) if want_stats else None
+    p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    j = _lib.SurfaceFragments()
+    j.visibility, j.draw_commands, j.meshlets, j.vertices, j.entity_data = p(vis), p(buf), p(mlt), p(vb), p(ent)
+    j.bary, j.grad, j.triangle, j.stats = p(bary), p(grad), p(tri), p(stats)
+    for name, _, _ in FRAGMENT_OUTPUTS:
+        setattr(j, name, p(outs[name]))
+    j.vertex_count, j.meshlet_count, j.max_commands = int(vertex_count), meshlet_count, int(max_commands)
+    j.entity_count = ent.nbytes // 128 if entity_count is None else int(entity_count)
+    j.vertex_stride, j.position_offset, j.normal_offset = int(vertex_stride), int(position_offset), int(normal_offset)
+    j.uv_offset, j.tangent_offset, j.width, j.height = int(uv_offset), int(tangent_offset), width, height
+    j.flags, j.command_base = _lib.FRAGMENTS_CLEAR if clear else 0, int(command_base)
+    status = C.c_int32(0)
+    _check(lib().orbit_host_surface_fragments(C.byref(j), C.byref(status)))
+    return dict(outs, stats=None if stats is None else stats[0], status=status.value)
