@@ -6,7 +6,8 @@ compaction's totals launch into its second round, and the clears striding from o
 1921 x 1081 target drawn on the device, where the resident grid itself takes several trips; a capped first call of a fresh
 context captured into a graph; the hook.  Bytes, counters and latched status equal the host mirror's on the same buffers
 (tests/test_visibility_tiles_cpu.py holds it to the restatements); every buffer sits between sentinel guards, inputs come
-back unchanged.  No tolerance anywhere.  No test provokes a fault: a stale word is data that the range checks reject."""
+back unchanged.  No tolerance anywhere.  No test provokes a fault: a stale word is data that the range checks reject.
+The two later readers, orbit_visibility_surface_drawn and orbit_surface_fragments: tests/test_surface_tiles_gpu.py."""
 import numpy as np
 import pytest
 
