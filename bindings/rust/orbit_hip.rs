@@ -226,6 +226,36 @@ pub struct OrbitSurfaceFragments {
     pub width: u32, pub height: u32, pub flags: u32, pub command_base: u32,
 }
 
+pub const ORBIT_SHADE_CLEAR: u32 = 1;
+pub const ORBIT_SHADE_FORCE_PER_LANE: u32 = 2;
+pub const ORBIT_SHADE_FORCE_STAGED: u32 = 4;
+
+/// The counters of orbit_fragments_shade (32 B, DEVICE, cleared by the call): covered = written + unshaded + stale; the
+/// other five count written pixels
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitShadeStats {
+    pub covered_pixels: u32, pub written_pixels: u32, pub unshaded_pixels: u32, pub stale_pixels: u32,
+    pub outside_pixels: u32, pub degenerate_pixels: u32, pub textured_pixels: u32, pub unserved_pixels: u32,
+}
+
+/// orbit_fragments_shade's argument block (160 B, HOST): DEVICE pointers; world_pos, normal and material as
+/// orbit_surface_fragments left them under ORBIT_FRAGMENTS_CLEAR; cluster_offset_image and light_index_buffer
+/// (ClusterLightIndices, index_capacity indices behind its 4-byte header) as orbit_compute_clusters left them; cluster_count,
+/// tile_size_px, z_scale, z_bias, luminance_cutoff: the fields of GpuClusterInfoBuffer (cluster.rs:322-335); z_near and
+/// view_pos: PerFrameBuffer's; render_mode 0 or 8; lights_walked and stats may be null
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitFragmentsShade {
+    pub visibility: *const u64, pub world_pos: *const f32, pub normal: *const f32, pub material: *const u32,
+    pub materials: *const c_void, pub lights: *const c_void, pub cluster_offset_image: *const u32,
+    pub light_index_buffer: *const c_void,
+    pub color: *mut f32, pub lights_walked: *mut u32, pub stats: *mut OrbitShadeStats,
+    pub material_count: u32, pub light_count: u32, pub index_capacity: u32,
+    pub cluster_count: [u32; 3], pub tile_size_px: u32,
+    pub z_scale: f32, pub z_bias: f32, pub luminance_cutoff: f32,
+    pub z_near: f32, pub view_pos: [f32; 3],
+    pub render_mode: u32, pub width: u32, pub height: u32, pub flags: u32,
+}
+
 /// orbit_visibility_resolve's argument block (48 B, HOST): DEVICE pointers; each output may be null, not all
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct OrbitVisibilityResolve {
@@ -447,6 +477,9 @@ extern "C" {
     pub fn orbit_visibility_surface(ctx: *mut OrbitCtx, job: *const OrbitVisibilitySurface, stream: *mut c_void) -> i32;
     pub fn orbit_visibility_surface_drawn(ctx: *mut OrbitCtx, job: *const OrbitVisibilitySurface, raster_flags: u32, stream: *mut c_void) -> i32;
     pub fn orbit_surface_fragments(ctx: *mut OrbitCtx, job: *const OrbitSurfaceFragments, stream: *mut c_void) -> i32;
+    /// forward.frag's clustered lighting of every visible pixel (L1-L9): the texture-free part of render_mode 0, and
+    /// render_mode 8, from the fragments call's planes and the cluster chain's light lists.
+    pub fn orbit_fragments_shade(ctx: *mut OrbitCtx, job: *const OrbitFragmentsShade, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

@@ -235,9 +235,10 @@ int32_t orbit_ctx_set_raster_grid(OrbitCtx *ctx, uint32_t max_workgroups);
  * prepared call follows it too.  0, the default, restores the sized grid.  The outputs do not depend on the grid; the
  * shard launch and every other launch are not touched. */
 int32_t orbit_ctx_set_fused_grid(OrbitCtx *ctx, uint32_t max_workgroups);
-/* Tests: the strided launches of the visibility buffer's four readers — orbit_visibility_resolve's clear and its tile
+/* Tests: the strided launches of the visibility buffer's five readers — orbit_visibility_resolve's clear and its tile
  * walk, orbit_visibility_compact's clear and its mark, orbit_visibility_surface's clear and its tile walk (and
- * orbit_visibility_surface_drawn's), orbit_surface_fragments' clear and its tile walk — take at most
+ * orbit_visibility_surface_drawn's), orbit_surface_fragments' clear and its tile walk, orbit_fragments_shade's clear and
+ * its tile walk — take at most
  * `max_workgroups` workgroups (of four waves; a wave takes its 8 x 8 tiles one after another, so under a cap of c wave g
  * takes tiles g, g + 4c, ... of even a small target).  Read when the call is enqueued: a captured launch carries its
  * grid.  0, the default, restores num_cus * 8.  The outputs do not depend on the grid; the compaction's scan, totals and
@@ -1555,6 +1556,140 @@ ORBIT_STATIC_ASSERT(offsetof(OrbitSurfaceFragments, command_base) == 172, "comma
 
 /* forward.frag's inputs of every pixel the list owns; see above */
 int32_t orbit_surface_fragments(OrbitCtx *ctx, const OrbitSurfaceFragments *job, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* Clustered lighting of a visibility buffer.  orbit_fragments_shade reads  */
+/* a buffer, what orbit_surface_fragments left under ORBIT_FRAGMENTS_CLEAR  */
+/* (world_pos, normal, material), the material and light tables and the     */
+/* per-cluster light lists of orbit_compute_clusters, and writes the colour */
+/* of every visible pixel: the texture-free part of forward.frag's          */
+/* render_mode 0 (material factors, point and directional lights through    */
+/* calculate_light) and render_mode 8, the light-count heat map.  ONE       */
+/* definition for the device and the host mirror                            */
+/* (orbit_host_fragments_shade); the two agree on every byte.  Arithmetic   */
+/* as in F1-F8: fp32, round to nearest, every operation rounded on its own, */
+/* never contracted, IEEE '/' and sqrtf, GLSL max / clamp (x < y ? y : x).  */
+/* dot(a, b) = (ax * bx + ay * by) + az * bz; normalize is F3's v /         */
+/* sqrtf((x * x + y * y) + z * z).                                          */
+/*  L1 which pixels.  A word of 0 is uncovered.  A covered pixel with       */
+/*     material[p] == 0xFFFFFFFF is UNSHADED: not written, the status stays */
+/*     OK (the fragments calls of a frame's two lists already merged them:  */
+/*     one shade call serves both).  material[p] >= material_count is       */
+/*     STALE: ORBIT_E_RANGE is latched, the pixel is not written.           */
+/*  L2 the cluster (forward.frag:352-363).  tile = (x / tile_size_px, y /   */
+/*     tile_size_px); d = the float of the word's high half (gl_FragCoord.z */
+/*     and the float the mark stage read when the clusters were built from  */
+/*     orbit_visibility_resolve's depth); slice = uint(fma(log2c(z_near /   */
+/*     d), z_scale, z_bias)), saturating, NaN -> 0: the integer of the mark */
+/*     stage (the device may take it through the hardware log2 inside the   */
+/*     proven guard band: the same integer by construction).  A tile or a   */
+/*     slice outside cluster_count is OUTSIDE: zero lights, as an imageLoad */
+/*     outside the image returns 0; the pixel is written and counts in      */
+/*     outside.  Otherwise (offset, count) = image[tile.x + tile.y * cx +   */
+/*     slice * cx * cy] and n = min(count, 256).  The pixel is STALE if     */
+/*     offset + n > index_capacity (indices behind the 4-byte header), or   */
+/*     if one of the n walked indices is >= light_count.  Nothing is read   */
+/*     before it is known to be in range.  lights_walked[p] = n.            */
+/*  L3 the material (forward.frag:277-339): the factors base_color.rgb,     */
+/*     metallic_factor, roughness_factor, emissive_factor.  Textures are    */
+/*     not served: a material with a texture index != 0xFFFFFFFF is shaded  */
+/*     from its factors and the pixel counts in textured.  N = normal[p] as */
+/*     it arrives; ao is unused.                                            */
+/*  L4 V = normalize(view_pos - world_pos.xyz).                             */
+/*  L5 the walk, in list order, light_sum starting at emissive.  lc_c =     */
+/*     color_c * intensity.  POINT (:460-486): Ld = position - wp; dist =   */
+/*     sqrtf(dot(Ld, Ld)); Ld = Ld / dist; dist = max(dist, inner_radius);  */
+/*     d2 = dist * dist; att = max(intensity / d2 - (luminance_cutoff * d2) */
+/*     / (outer_radius * outer_radius), 0).  DIRECTIONAL: Ld = direction as */
+/*     stored, att = 1, shadow = 1: shadow maps are not served, a light     */
+/*     with shadow_data_index != 0xFFFFFFFF makes the pixel count in        */
+/*     unserved.  SKY is skipped (cube maps) and the pixel counts in        */
+/*     unserved.  Any other type is ignored, as the switch has no default.  */
+/*     light_sum_c = light_sum_c + L6_c.                                    */
+/*  L6 calculate_light (:186-216, functions.glsl:82-100).  EPS = 0.0001f,   */
+/*     PI = the float of 3.14159265359.  H = normalize(V + Ld); ndv =       */
+/*     max(dot(N, V), EPS); ndl = max(dot(N, Ld), EPS); ndh = max(dot(N,    */
+/*     H), 0); hv = max(dot(H, V), 0); r = roughness, a = r * r, a2 = a *   */
+/*     a; den = (ndh * ndh) * (a2 - 1) + 1, then den = (PI * den) * den; D  */
+/*     = a2 / max(den, EPS); rr = r + 1, k = (rr * rr) / 8; G = (ndv / (ndv */
+/*     * (1 - k) + k)) * (ndl / (ndl * (1 - k) + k)); f0_c = 0.04f * (1 -   */
+/*     metallic) + albedo_c * metallic; x = 1 - hv, p5 = ((x * x) * (x *    */
+/*     x)) * x; F_c = f0_c + (1 - f0_c) * p5; spec_c = ((D * G) * F_c) /    */
+/*     ((4 * ndv) * ndl); kD_c = (1 - F_c) * (1 - metallic); the light's    */
+/*     term is ((((kD_c * albedo_c) / PI) + spec_c) * (lc_c * att)) * ndl.  */
+/*     GLSL LEAVES pow's PRECISION TO THE DRIVER: p5 AS THREE PRODUCTS IS   */
+/*     THIS PROJECT'S CHOICE.                                               */
+/*  L7 color[p] = (light_sum, 1.0f).  render_mode 8 (:564-567): color[p] =  */
+/*     heat_colormap(clamp((float)n / 32.0f, 0, 1)) of functions.glsl:      */
+/*     142-171 (red: x < 0.7f ? 4 * x - 1.5f : -4 * x + 4.5f; green: x <    */
+/*     0.5f ? 4 * x - 0.5f : -4 * x + 3.5f; blue: x < 0.3f ? 4 * x + 0.5f : */
+/*     -4 * x + 2.5f; each clamped to [0, 1]), alpha 1.  L1-L3 hold as in   */
+/*     mode 0 (the indices are range-checked), the light rows are not read: */
+/*     unserved and degenerate stay 0.                                      */
+/*  L8 no non-finite bytes: a colour float that is not finite is written as */
+/*     +0.0f and the pixel counts once in degenerate; it is still written.  */
+/*  L9 ORBIT_SHADE_CLEAR first fills color with +0.0f and lights_walked     */
+/*     with 0.  stats (may be NULL) is cleared by the call; covered =       */
+/*     written + unshaded + stale.  Every output depends on its own pixel   */
+/*     only: independent of scheduling and of the form of the walk.         */
+/* Two forms of the walk give the same bytes (every pixel adds its own list */
+/* in list order): per lane, and staged through LDS per cluster when        */
+/* tile_size_px is a multiple of 8.  ORBIT_SHADE_FORCE_PER_LANE /           */
+/* ORBIT_SHADE_FORCE_STAGED select one; with neither the library chooses.   */
+/*   ORBIT_E_INVALID  (message prefix fragments_shade:) job or a required   */
+/*                    pointer NULL (all but lights_walked and stats); a     */
+/*                    pointer misaligned (visibility, cluster_offset_image: */
+/*                    8 B, materials, lights: 16 B, the rest: 4 B); width   */
+/*                    or height 0 or above ORBIT_RASTER_MAX_DIM; a zero in  */
+/*                    cluster_count or tile_size_px; cluster_count[2] > 32; */
+/*                    cx * cy * cz > 2^31; render_mode not 0 or 8; unknown  */
+/*                    flags; both FORCE flags; FORCE_STAGED with            */
+/*                    tile_size_px % 8 != 0; an output pointer equal to an  */
+/*                    input pointer.  All checked before the context is     */
+/*                    looked at.                                            */
+/* Kernel launches only: no allocation, no scratch, no host wait; a graph   */
+/* captures the call on a fresh context's first call.                       */
+/* ------------------------------------------------------------------------ */
+#define ORBIT_SHADE_CLEAR 1u          /* flags: fill color and lights_walked first (L9) */
+#define ORBIT_SHADE_FORCE_PER_LANE 2u /* flags: every lane walks its own list */
+#define ORBIT_SHADE_FORCE_STAGED 4u   /* flags: a wave stages each cluster's list in LDS (tile_size_px % 8 == 0) */
+#define ORBIT_SHADE_MAX_WALK 256u     /* forward.frag:363 */
+typedef struct OrbitShadeStats { /* DEVICE, 32 B, cleared by the call */
+    uint32_t covered_pixels, written_pixels, unshaded_pixels, stale_pixels, outside_pixels, degenerate_pixels,
+        textured_pixels, unserved_pixels;
+} OrbitShadeStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitShadeStats) == 32, "ShadeStats is 32 B");
+typedef struct OrbitFragmentsShade { /* HOST block, 160 B; every pointer a DEVICE pointer */
+    const uint64_t *visibility;           /* width * height u64, as orbit_raster_visibility left it */
+    const float *world_pos;               /* 4 floats per pixel, as orbit_surface_fragments left them */
+    const float *normal;                  /* 3 floats per pixel */
+    const uint32_t *material;             /* 1 word per pixel; 0xFFFFFFFF: unshaded */
+    const OrbitMaterialData *materials;   /* material_count rows of 80 B */
+    const OrbitLightData *lights;         /* light_count rows of 64 B */
+    const uint32_t *cluster_offset_image; /* cx * cy * cz (offset, count) pairs, as orbit_cluster_assign writes them */
+    const void *light_index_buffer;       /* ClusterLightIndices: indices at byte 4 */
+    float *color;                         /* 4 floats per pixel */
+    uint32_t *lights_walked;              /* NULL, or 1 word per pixel */
+    OrbitShadeStats *stats;               /* NULL, or the counters */
+    uint32_t material_count, light_count, index_capacity;
+    uint32_t cluster_count[3], tile_size_px; /* OrbitGpuClusterInfoBuffer's */
+    float z_scale, z_bias, luminance_cutoff; /* OrbitGpuClusterInfoBuffer's */
+    float z_near, view_pos[3];               /* PerFrameBuffer's */
+    uint32_t render_mode;                    /* 0 or 8 */
+    uint32_t width, height, flags;
+} OrbitFragmentsShade;
+ORBIT_STATIC_ASSERT(sizeof(OrbitFragmentsShade) == 160, "FragmentsShade is 160 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShade, materials) == 32, "materials @32");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShade, color) == 64, "color @64");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShade, material_count) == 88, "material_count @88");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShade, cluster_count) == 100, "cluster_count @100");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShade, z_scale) == 116, "z_scale @116");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShade, z_near) == 128, "z_near @128");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShade, render_mode) == 144, "render_mode @144");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShade, flags) == 156, "flags @156");
+
+/* forward.frag's clustered lighting of every visible pixel; see above */
+int32_t orbit_fragments_shade(OrbitCtx *ctx, const OrbitFragmentsShade *job, void *stream);
 
 #ifdef __cplusplus
 }

@@ -160,6 +160,31 @@ class SurfaceFragments(C.Structure):  # OrbitSurfaceFragments (176 B)
 FRAGMENTS_CLEAR = 1  # ORBIT_FRAGMENTS_CLEAR
 
 
+class FragmentsShade(C.Structure):  # OrbitFragmentsShade (160 B)
+    _fields_ = [("visibility", C.c_void_p), ("world_pos", C.c_void_p), ("normal", C.c_void_p), ("material", C.c_void_p),
+                ("materials", C.c_void_p), ("lights", C.c_void_p), ("cluster_offset_image", C.c_void_p),
+                ("light_index_buffer", C.c_void_p), ("color", C.c_void_p), ("lights_walked", C.c_void_p), ("stats", C.c_void_p),
+                ("material_count", C.c_uint32), ("light_count", C.c_uint32), ("index_capacity", C.c_uint32),
+                ("cluster_count", C.c_uint32 * 3), ("tile_size_px", C.c_uint32), ("z_scale", C.c_float), ("z_bias", C.c_float),
+                ("luminance_cutoff", C.c_float), ("z_near", C.c_float), ("view_pos", C.c_float * 3), ("render_mode", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32)]
+
+
+SHADE_CLEAR, SHADE_FORCE_PER_LANE, SHADE_FORCE_STAGED = 1, 2, 4  # ORBIT_SHADE_*
+
+
+def fill_fragments_shade(j, cluster_count, tile_size_px, z_scale, z_bias, luminance_cutoff, z_near, view_pos, render_mode, width,
+                         height, clear, form):
+    """The by-value fields of an OrbitFragmentsShade; form: None (the library chooses), "per_lane", "staged" or raw
+    flag bits."""
+    j.cluster_count[:] = [int(c) for c in cluster_count]
+    j.tile_size_px, j.z_scale, j.z_bias, j.luminance_cutoff = int(tile_size_px), float(z_scale), float(z_bias), float(luminance_cutoff)
+    j.z_near, j.render_mode, j.width, j.height = float(z_near), int(render_mode), int(width), int(height)
+    j.view_pos[:] = [float(v) for v in view_pos]
+    forms = {None: 0, "per_lane": SHADE_FORCE_PER_LANE, "staged": SHADE_FORCE_STAGED}
+    j.flags = (SHADE_CLEAR if clear else 0) | (form if isinstance(form, int) else forms[form])  # an int: raw flag bits
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -266,6 +291,7 @@ SYMBOLS = {
     "orbit_visibility_surface": (C.c_int32, [C.c_void_p, C.POINTER(VisibilitySurface), C.c_void_p]),
     "orbit_visibility_surface_drawn": (C.c_int32, [C.c_void_p, C.POINTER(VisibilitySurface), C.c_uint32, C.c_void_p]),
     "orbit_surface_fragments": (C.c_int32, [C.c_void_p, C.POINTER(SurfaceFragments), C.c_void_p]),
+    "orbit_fragments_shade": (C.c_int32, [C.c_void_p, C.POINTER(FragmentsShade), C.c_void_p]),
 }
 
 _lib = None

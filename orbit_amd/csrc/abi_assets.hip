@@ -6,7 +6,7 @@
 // orbit_visibility_surface, its barycentrics, differences and ids per pixel (visibility_surface.hip), with
 // orbit_visibility_surface_drawn, the same for a buffer drawn with the raster flags (visibility_surface_drawn.hip), and
 // orbit_surface_fragments, the fragment shader's inputs per pixel from those and the vertex attributes
-// (surface_fragments.hip).
+// (surface_fragments.hip), and orbit_fragments_shade, the clustered lighting of those pixels (fragments_shade.hip).
 #include "abi_internal.h"
 
 namespace {
@@ -291,6 +291,47 @@ int32_t orbit_surface_fragments(OrbitCtx *ctx, const OrbitSurfaceFragments *job,
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_surface_fragments(j, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch surface_fragments");
+    return ORBIT_OK;
+}
+
+// A clearing launch (stats, and with ORBIT_SHADE_CLEAR color and lights_walked) and the shading launch
+// (fragments_shade.hip).  No allocation, no scratch, no host sync: capturable on the first call.  As its siblings, the
+// job is checked before the context is looked at, each error with a message of its own.
+int32_t orbit_fragments_shade(OrbitCtx *ctx, const OrbitFragmentsShade *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: job is NULL");
+    const OrbitFragmentsShade &j = *job;
+    const uint32_t known = ORBIT_SHADE_CLEAR | ORBIT_SHADE_FORCE_PER_LANE | ORBIT_SHADE_FORCE_STAGED;
+    if (j.flags & ~known) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: flags %#x", j.flags);
+    if ((j.flags & ORBIT_SHADE_FORCE_PER_LANE) && (j.flags & ORBIT_SHADE_FORCE_STAGED))
+        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: ORBIT_SHADE_FORCE_PER_LANE and ORBIT_SHADE_FORCE_STAGED together");
+    if (j.render_mode != 0u && j.render_mode != 8u) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: render_mode %u (0 or 8)", j.render_mode);
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if (j.cluster_count[0] == 0 || j.cluster_count[1] == 0 || j.cluster_count[2] == 0 || j.tile_size_px == 0)
+        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: cluster_count %u x %u x %u, tile_size_px %u (none may be 0)", j.cluster_count[0],
+                    j.cluster_count[1], j.cluster_count[2], j.tile_size_px);
+    if (j.cluster_count[2] > 32u) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: cluster_count[2] %u > 32", j.cluster_count[2]);
+    if ((uint64_t)j.cluster_count[0] * j.cluster_count[1] > (1ull << 31) / j.cluster_count[2])
+        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: %u x %u x %u clusters > 2^31", j.cluster_count[0], j.cluster_count[1], j.cluster_count[2]);
+    if ((j.flags & ORBIT_SHADE_FORCE_STAGED) && j.tile_size_px % 8u != 0u)
+        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: ORBIT_SHADE_FORCE_STAGED needs tile_size_px %u %% 8 == 0", j.tile_size_px);
+    if (!j.visibility || !j.world_pos || !j.normal || !j.material || !j.materials || !j.lights || !j.cluster_offset_image ||
+        !j.light_index_buffer || !j.color)
+        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: NULL buffer");
+    const void *const inputs[8] = {j.visibility, j.world_pos, j.normal, j.material, j.materials, j.lights, j.cluster_offset_image, j.light_index_buffer};
+    const void *const outputs[3] = {j.color, j.lights_walked, j.stats};
+    uintptr_t low_bits = 0;
+    for (const void *in : inputs) low_bits |= (uintptr_t)in;
+    for (const void *out : outputs) low_bits |= (uintptr_t)out;
+    if ((((uintptr_t)j.visibility | (uintptr_t)j.cluster_offset_image) & 7u) || (((uintptr_t)j.materials | (uintptr_t)j.lights) & 15u) || (low_bits & 3u))
+        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: visibility and cluster_offset_image must be 8-B aligned, materials and lights 16-B aligned, every other buffer 4-B aligned");
+    for (const void *out : outputs)
+        for (const void *in : inputs)
+            if (out && out == in) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: an output is an input (%p)", out);
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "fragments_shade: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_fragments_shade(j, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch fragments_shade");
     return ORBIT_OK;
 }
 

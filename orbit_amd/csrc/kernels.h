@@ -450,6 +450,11 @@ hipError_t launch_visibility_surface_drawn(const OrbitVisibilitySurface &job, ui
 // ORBIT_FRAGMENTS_CLEAR, fills the outputs; the next reads every word once, a wave per 8 x 8 tile, a lane per pixel
 hipError_t launch_surface_fragments(const OrbitSurfaceFragments &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
                                     hipStream_t s);
+// fragments_shade.hip: orbit_fragments_shade — `job` validated by the entry point.  One launch clears stats and, with
+// ORBIT_SHADE_CLEAR, color and lights_walked; the next shades, a wave per 8 x 8 tile, a lane per pixel, walking the
+// cluster's light list per lane or staged through LDS (tile_size_px % 8 == 0, the default there)
+hipError_t launch_fragments_shade(const OrbitFragmentsShade &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
+                                  hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

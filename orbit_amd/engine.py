@@ -501,6 +501,31 @@ class Engine:
         j.flags, j.command_base = _lib.FRAGMENTS_CLEAR if clear else 0, int(command_base)
         _lib.check(self._lib.orbit_surface_fragments(self._ctx, C.byref(j), _stream(stream)), self._ctx)
 
+    # -- forward.frag's clustered lighting per pixel of a visibility buffer (orbit_fragments_shade)
+    def fragments_shade(self, visibility, width, height, world_pos, normal, material, materials, material_count, lights,
+                        light_count, cluster_offset_image, light_index_buffer, index_capacity, cluster_count, tile_size_px,
+                        z_scale, z_bias, luminance_cutoff, z_near, view_pos, color, lights_walked=None, stats=None,
+                        render_mode=0, clear=False, form=None, stream=None):
+        """From the width x height u64 tensor `visibility`, the planes surface_fragments left under clear=True (world_pos,
+        normal, material), the 80-B material rows, the 64-B light rows and the cluster chain's light lists (the (offset,
+        count) image and ClusterLightIndices with `index_capacity` indices behind its 4-byte header; cluster_count,
+        tile_size_px, z_scale, z_bias and luminance_cutoff as in the cluster info buffer) to `color` (4 floats per pixel):
+        the texture-free part of the reference's forward.frag, render_mode 0 (material factors, point and directional
+        lights) or 8 (the light-count heat map).  lights_walked (1 u32 per pixel) and stats (32 bytes,
+        layouts.SHADE_STATS, cleared by the call) may be None.  Uncovered pixels and pixels whose material is 0xFFFFFFFF
+        are not written; clear=True (ORBIT_SHADE_CLEAR) fills color and lights_walked first.  A pixel whose material or
+        light list does not fit the tables is counted in stale_pixels and reported by status() (ORBIT_E_RANGE).  form:
+        None (the library chooses), "per_lane" or "staged" (tile_size_px % 8 == 0): equal bytes.  Byte-equal to
+        orbit_amd.raster.host_fragments_shade.  Enqueued on `stream`."""
+        j = _lib.FragmentsShade()
+        j.visibility, j.world_pos, j.normal, j.material = _ptr(visibility), _ptr(world_pos), _ptr(normal), _ptr(material)
+        j.materials, j.lights, j.cluster_offset_image = _ptr(materials), _ptr(lights), _ptr(cluster_offset_image)
+        j.light_index_buffer, j.color, j.lights_walked, j.stats = _ptr(light_index_buffer), _ptr(color), _ptr(lights_walked), _ptr(stats)
+        j.material_count, j.light_count, j.index_capacity = int(material_count), int(light_count), int(index_capacity)
+        _lib.fill_fragments_shade(j, cluster_count, tile_size_px, z_scale, z_bias, luminance_cutoff, z_near, view_pos, render_mode,
+                                  width, height, clear, form)
+        _lib.check(self._lib.orbit_fragments_shade(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                    entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,
@@ -827,8 +852,8 @@ class Engine:
 
     def set_visibility_grid(self, max_workgroups):
         """orbit_ctx_set_visibility_grid: at most that many workgroups for the strided launches of visibility_resolve,
-        visibility_compact (clear and mark) and visibility_surface, read when the call is enqueued (0 = num_cus * 8;
-        tests)."""
+        visibility_compact (clear and mark), visibility_surface, surface_fragments and fragments_shade, read when the call is
+        enqueued (0 = num_cus * 8; tests)."""
         _lib.check(self._lib.orbit_ctx_set_visibility_grid(self._ctx, int(max_workgroups)), self._ctx)
 
     def exchange_list(self, local_list, rank, world, out_buffers, ctrl_buffers, out_capacity, header_bytes, stride,

@@ -12,6 +12,7 @@
 #include "orbit_raster.hpp"
 #include "orbit_scene.hpp"
 #include "../csrc/block_pretest.h"
+#include "../csrc/shade_common.h"
 
 using namespace orbit;
 using namespace orbit::passes;
@@ -623,6 +624,19 @@ int32_t orbit_host_surface_fragments(const OrbitSurfaceFragments *job, int32_t *
         if (!job) throw Panic("surface_fragments: job is NULL");
         raster::surface_fragments(*job, status);
     });
+}
+
+int32_t orbit_host_fragments_shade(const OrbitFragmentsShade *job, int32_t *status) {
+    return guarded([&] {
+        if (!job) throw Panic("fragments_shade: job is NULL");
+        raster::fragments_shade(*job, status);
+    });
+}
+
+// canonical log2 and slice of shade_common.h, for tests
+float orbit_host_shade_log2(float x) { return raster::shade_log2c(x); }
+uint32_t orbit_host_shade_slice(float z_near, float d, float z_scale, float z_bias) {
+    return raster::shade_slice_canonical(z_near, d, z_scale, z_bias);
 }
 
 // ---------------------------------------------------------------- asset ingestion (orbit_gltf.hpp), host only

@@ -260,6 +260,14 @@ int32_t orbit_host_visibility_surface_drawn(const OrbitVisibilitySurface *job, u
  * what the device answers with ORBIT_E_INVALID (alignment and aliasing aside). */
 int32_t orbit_host_surface_fragments(const OrbitSurfaceFragments *job, int32_t *status);
 
+/* the reference of orbit_fragments_shade (L1-L9): the device call's block with HOST pointers in it.  color, lights_walked
+ * and stats hold the device's bytes.  *status (may be NULL): ORBIT_E_RANGE if a pixel was stale, else ORBIT_OK.
+ * ORBIT_HOST_PANIC for what the device answers with ORBIT_E_INVALID (alignment and aliasing aside). */
+int32_t orbit_host_fragments_shade(const OrbitFragmentsShade *job, int32_t *status);
+/* tests: the host restatement of the canonical log2 (held to the oracle's) and L2's slice of a depth d */
+float orbit_host_shade_log2(float x);
+uint32_t orbit_host_shade_slice(float z_near, float d, float z_scale, float z_bias);
+
 /* ---- asset ingestion (orbit_gltf.hpp): glTF 2.0 (.glb / .gltf) -> materials, meshes with their LOD chains, entities ----
  * load_gltf (gltf_loader.rs:511-676) + GpuAssets::add_mesh (assets/mod.rs:325-476).  NULL + orbit_host_last_error()
  * on failure.  The arrays stay valid until orbit_host_gltf_free. */

@@ -6,6 +6,7 @@
 #include "../csrc/raster_common.h"
 #include "../csrc/surface_common.h"
 #include "../csrc/fragment_common.h"
+#include "../csrc/shade_common.h"
 #include "orbit_host.hpp"
 
 namespace orbit {
@@ -434,6 +435,51 @@ void surface_fragments(const OrbitSurfaceFragments &j, int32_t *status) {
         if (j.uv) std::memcpy(j.uv + 2 * p, out + 11, 8);
         if (j.uv_grad) std::memcpy(j.uv_grad + 4 * p, out + 13, 16);
         if (j.material) j.material[p] = material;
+    }
+    if (j.stats) *j.stats = st;
+    if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
+}
+
+void fragments_shade(const OrbitFragmentsShade &j, int32_t *status) {
+    const uint32_t known = ORBIT_SHADE_CLEAR | ORBIT_SHADE_FORCE_PER_LANE | ORBIT_SHADE_FORCE_STAGED;
+    if (j.flags & ~known) throw Panic("fragments_shade: unknown flags");
+    if ((j.flags & ORBIT_SHADE_FORCE_PER_LANE) && (j.flags & ORBIT_SHADE_FORCE_STAGED)) throw Panic("fragments_shade: both forms forced");
+    if (j.render_mode != 0u && j.render_mode != 8u) throw Panic("fragments_shade: render_mode");
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        throw Panic("fragments_shade: target size");
+    if (j.cluster_count[0] == 0 || j.cluster_count[1] == 0 || j.cluster_count[2] == 0 || j.tile_size_px == 0)
+        throw Panic("fragments_shade: a zero in cluster_count or tile_size_px");
+    if (j.cluster_count[2] > 32u) throw Panic("fragments_shade: cluster_count[2] > 32");
+    if ((uint64_t)j.cluster_count[0] * j.cluster_count[1] > (1ull << 31) / j.cluster_count[2]) throw Panic("fragments_shade: clusters > 2^31");
+    if ((j.flags & ORBIT_SHADE_FORCE_STAGED) && j.tile_size_px % 8u != 0u) throw Panic("fragments_shade: staged needs tile_size_px % 8 == 0");
+    if (!j.visibility || !j.world_pos || !j.normal || !j.material || !j.materials || !j.lights || !j.cluster_offset_image ||
+        !j.light_index_buffer || !j.color)
+        throw Panic("fragments_shade: NULL argument");
+    const size_t pixels = (size_t)j.width * j.height;
+    if (j.flags & ORBIT_SHADE_CLEAR) { // L9
+        std::memset(j.color, 0, pixels * 16);
+        if (j.lights_walked) std::memset(j.lights_walked, 0, pixels * 4);
+    }
+    OrbitShadeStats st{};
+    for (size_t p = 0; p < pixels; p++) {
+        const uint64_t word = j.visibility[p];
+        if (word == 0) continue;
+        st.covered_pixels++;
+        const uint32_t x = (uint32_t)(p % j.width), y = (uint32_t)(p / j.width);
+        const uint32_t slice = shade_slice_canonical(j.z_near, bits_float((int32_t)(uint32_t)(word >> 32)), j.z_scale, j.z_bias); // L2
+        float color[4];
+        uint32_t n, marks;
+        const uint32_t verdict = shade_pixel(j, x, y, p, slice, color, n, marks);
+        if (verdict == kShadeUnshaded) st.unshaded_pixels++;
+        if (verdict == kShadeStale) st.stale_pixels++;
+        if (verdict != kShadeWritten) continue;
+        st.written_pixels++;
+        if (marks & kShadeOutside) st.outside_pixels++;
+        if (marks & kShadeDegenerate) st.degenerate_pixels++;
+        if (marks & kShadeTextured) st.textured_pixels++;
+        if (marks & kShadeUnserved) st.unserved_pixels++;
+        std::memcpy(j.color + 4 * p, color, 16);
+        if (j.lights_walked) j.lights_walked[p] = n;
     }
     if (j.stats) *j.stats = st;
     if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;

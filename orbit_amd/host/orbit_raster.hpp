@@ -61,5 +61,11 @@ void visibility_surface_drawn(const OrbitVisibilitySurface &job, uint32_t raster
 // if a pixel was stale, else ORBIT_OK.  Throws Panic for ORBIT_E_INVALID (alignment and aliasing aside).
 void surface_fragments(const OrbitSurfaceFragments &job, int32_t *status);
 
+// orbit_fragments_shade (L1-L9, §4.25) on host buffers: the job's pointers are HOST pointers.  The obvious loop over the
+// pixels, each through ../csrc/shade_common.h with the canonical slice; the FORCE flags are checked and change nothing.
+// *status (may be null) = what the device call latches: ORBIT_E_RANGE if a pixel was stale, else ORBIT_OK.  Throws Panic
+// for ORBIT_E_INVALID (alignment and aliasing aside).
+void fragments_shade(const OrbitFragmentsShade &job, int32_t *status);
+
 } // namespace raster
 } // namespace orbit

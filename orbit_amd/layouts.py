@@ -72,6 +72,9 @@ SURFACE_DRAWN_STATS = np.dtype([(n, "<u4") for n in SURFACE_STATS.names[:6] + ("
 # OrbitFragmentStats: the counters of orbit_surface_fragments
 SURFACE_FRAGMENT_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "written_pixels", "foreign_pixels", "unshaded_pixels",
                                                         "stale_pixels", "degenerate_pixels", "_pad0", "_pad1")])
+# OrbitShadeStats: the counters of orbit_fragments_shade
+SHADE_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "written_pixels", "unshaded_pixels", "stale_pixels", "outside_pixels",
+                                             "degenerate_pixels", "textured_pixels", "unserved_pixels")])
 # types.glsl:64-73, src/assets/mesh.rs:14-20: the reference's MeshVertex, 32 B (normal and tangent as snorm8)
 MESH_VERTEX = np.dtype([("position", "<f4", (3,)), ("normal", "i1", (4,)), ("uv", "<f4", (2,)), ("tangent", "i1", (4,)),
                         ("_padding", "<u4")])

@@ -5,7 +5,8 @@ host arrays, the same pass keeping the winner's identity and its resolve — the
 list of such a buffer, the reference of ``Engine.visibility_compact``, and of ``orbit_visibility_surface``, the
 barycentrics and ids per pixel of such a buffer, the reference of ``Engine.visibility_surface``, and of
 ``orbit_surface_fragments``, the fragment shader's inputs per pixel from those, the reference of
-``Engine.surface_fragments``.  Python adds nothing; host only."""
+``Engine.surface_fragments``, and of ``orbit_fragments_shade``, the clustered lighting of those pixels, the reference of
+``Engine.fragments_shade``.  Python adds nothing; host only."""
 import ctypes as C
 
 import numpy as np
@@ -246,3 +247,64 @@ def host_surface_fragments(visibility, draw_commands, max_commands, meshlets, su
     status = C.c_int32(0)
     _check(lib().orbit_host_surface_fragments(C.byref(j), C.byref(status)))
     return dict(outs, stats=None if stats is None else stats[0], status=status.value)
+
+
+def host_fragments_shade(visibility, world_pos, normal, material, materials, lights, cluster_offset_image, light_index_buffer,
+                         cluster_count, tile_size_px, z_scale, z_bias, luminance_cutoff, z_near, view_pos, render_mode=0,
+                         clear=True, into=None, form=None, material_count=None, light_count=None, index_capacity=None, fill=0,
+                         want_walked=True, want_stats=True):
+    """orbit_host_fragments_shade on a (height, width) np.uint64 buffer, the planes of host_surface_fragments (world_pos
+    (.., 4), normal (.., 3) np.float32, material (.., 1) np.uint32), np[layouts.MATERIAL] and np[layouts.LIGHT] rows, the
+    (offset, count) image (cx * cy * cz pairs of u32) and the ClusterLightIndices bytes (indices at byte 4) -> dict(color
+    (height, width, 4) np.float32, lights_walked (height, width) np.uint32 or None, stats: np[layouts.SHADE_STATS] scalar
+    row or None, status: what the device call latches).  `into`: the dict of an earlier call to write into (copied),
+    clear=False.  Otherwise color and lights_walked start filled with the u32 `fill`: what the call does not write keeps
+    it.  The counts default to what the arrays hold."""
+    vis = np.ascontiguousarray(visibility, dtype=np.uint64)
+    height, width = vis.shape
+    wp = np.ascontiguousarray(world_pos, dtype=np.float32).reshape(height, width, 4)
+    nrm = np.ascontiguousarray(normal, dtype=np.float32).reshape(height, width, 3)
+    mat = np.ascontiguousarray(material, dtype=np.uint32).reshape(height, width)
+    mats = np.ascontiguousarray(materials).view(np.uint8).reshape(-1)
+    lts = np.ascontiguousarray(lights).view(np.uint8).reshape(-1)
+    img = np.ascontiguousarray(cluster_offset_image).view(np.uint32).reshape(-1)
+    lib_ = np.ascontiguousarray(light_index_buffer).view(np.uint8).reshape(-1)
+    cx, cy, cz = (int(c) for c in cluster_count)
+    if img.size < 2 * cx * cy * cz:
+        raise ValueError("cluster_count reaches beyond the offset image")
+    material_count = mats.nbytes // 80 if material_count is None else int(material_count)
+    light_count = lts.nbytes // 64 if light_count is None else int(light_count)
+    index_capacity = max(lib_.nbytes - 4, 0) // 4 if index_capacity is None else int(index_capacity)
+    if material_count * 80 > mats.nbytes or light_count * 64 > lts.nbytes or 4 + 4 * index_capacity > max(lib_.nbytes, 4):
+        raise ValueError("a count reaches beyond its array")
+    if into is not None:
+        color = np.array(into["color"], dtype=np.float32, order="C").reshape(height, width, 4)
+        walked = None if not want_walked else np.array(into["lights_walked"], dtype=np.uint32, order="C").reshape(height, width)
+    else:
+        color = np.full((height, width, 4), fill, np.uint32).view(np.float32)
+        walked = np.full((height, width), fill, np.uint32) if want_walked else None
+    stats = np.zeros(1, L.SHADE_STATS) if want_stats else None
+    p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    j = _lib.FragmentsShade()
+    j.visibility, j.world_pos, j.normal, j.material, j.materials, j.lights = p(vis), p(wp), p(nrm), p(mat), p(mats), p(lts)
+    j.cluster_offset_image, j.light_index_buffer, j.color, j.lights_walked, j.stats = p(img), p(lib_), p(color), p(walked), p(stats)
+    j.material_count, j.light_count, j.index_capacity = material_count, light_count, index_capacity
+    _lib.fill_fragments_shade(j, (cx, cy, cz), tile_size_px, z_scale, z_bias, luminance_cutoff, z_near, view_pos, render_mode, width,
+                              height, clear, form)
+    status = C.c_int32(0)
+    _check(lib().orbit_host_fragments_shade(C.byref(j), C.byref(status)))
+    return dict(color=color, lights_walked=walked, stats=None if stats is None else stats[0], status=status.value)
+
+
+def host_shade_log2(x):
+    """The host restatement of the canonical log2 (csrc/shade_common.h shade_log2c) of a float32 -> np.float32."""
+    fn = lib().orbit_host_shade_log2
+    fn.restype, fn.argtypes = C.c_float, [C.c_float]
+    return np.float32(fn(float(x)))
+
+
+def host_shade_slice(z_near, d, z_scale, z_bias):
+    """L2's slice of a depth d: uint(fma(log2c(z_near / d), z_scale, z_bias)) as the host mirror takes it."""
+    fn = lib().orbit_host_shade_slice
+    fn.restype, fn.argtypes = C.c_uint32, [C.c_float] * 4
+    return int(fn(float(z_near), float(d), float(z_scale), float(z_bias)))
