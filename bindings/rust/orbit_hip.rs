@@ -256,6 +256,34 @@ pub struct OrbitFragmentsShade {
     pub render_mode: u32, pub width: u32, pub height: u32, pub flags: u32,
 }
 
+/// One row of ShadowDataBuffer (288 B, DEVICE; types.glsl:29-33 in std430): four column-major light_projection_matrices,
+/// their shadow_map_world_sizes, and shadow_map_indices into orbit_fragments_shade_shadowed's shadow_maps array (the
+/// caller maps its bindless indices onto it)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitShadowData {
+    pub light_projection_matrices: [[f32; 16]; 4], pub shadow_map_world_sizes: [f32; 4], pub shadow_map_indices: [u32; 4],
+}
+
+/// The counters orbit_fragments_shade_shadowed adds (16 B, DEVICE, cleared by the call), over written pixels
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitShadowStats {
+    pub shadowed_pixels: u32, pub no_cascade_pixels: u32, pub early_out_pixels: u32, pub shadow_evaluations: u32,
+}
+
+/// orbit_fragments_shade_shadowed's argument block (232 B, HOST): an OrbitFragmentsShade, then the shadow rows
+/// (shadow_count of them, 16-B aligned), the maps (shadow_map_count squares of shadow_resolution^2 f32, reversed z, as
+/// orbit_raster_depth leaves them under a cascade's matrix with ORBIT_RASTER_CLEAR), the optional outputs shadow_factor,
+/// cascade and shadow_stats (may be null), shadow_index_base = MAX_SHADOW_COMMANDS * frame_index, and ShadowSettings'
+/// blocker_search_radius, normal_bias_scale and oriented_bias (as shadow_renderer.rs:129 sends it: negated)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitFragmentsShadeShadowed {
+    pub shade: OrbitFragmentsShade,
+    pub shadows: *const OrbitShadowData, pub shadow_maps: *const f32,
+    pub shadow_factor: *mut f32, pub cascade: *mut u32, pub shadow_stats: *mut OrbitShadowStats,
+    pub shadow_count: u32, pub shadow_index_base: u32, pub shadow_map_count: u32, pub shadow_resolution: u32,
+    pub blocker_search_radius: f32, pub normal_bias_scale: f32, pub oriented_bias: f32, pub _pad: u32,
+}
+
 /// orbit_visibility_resolve's argument block (48 B, HOST): DEVICE pointers; each output may be null, not all
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct OrbitVisibilityResolve {
@@ -480,6 +508,8 @@ extern "C" {
     /// forward.frag's clustered lighting of every visible pixel (L1-L9): the texture-free part of render_mode 0, and
     /// render_mode 8, from the fragments call's planes and the cluster chain's light lists.
     pub fn orbit_fragments_shade(ctx: *mut OrbitCtx, job: *const OrbitFragmentsShade, stream: *mut c_void) -> i32;
+    /// The same with forward.frag's cascaded PCSS shadow term on the shadowed directional lights (H1-H10).
+    pub fn orbit_fragments_shade_shadowed(ctx: *mut OrbitCtx, job: *const OrbitFragmentsShadeShadowed, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

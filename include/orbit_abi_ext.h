@@ -235,10 +235,10 @@ int32_t orbit_ctx_set_raster_grid(OrbitCtx *ctx, uint32_t max_workgroups);
  * prepared call follows it too.  0, the default, restores the sized grid.  The outputs do not depend on the grid; the
  * shard launch and every other launch are not touched. */
 int32_t orbit_ctx_set_fused_grid(OrbitCtx *ctx, uint32_t max_workgroups);
-/* Tests: the strided launches of the visibility buffer's five readers — orbit_visibility_resolve's clear and its tile
+/* Tests: the strided launches of the visibility buffer's six readers — orbit_visibility_resolve's clear and its tile
  * walk, orbit_visibility_compact's clear and its mark, orbit_visibility_surface's clear and its tile walk (and
  * orbit_visibility_surface_drawn's), orbit_surface_fragments' clear and its tile walk, orbit_fragments_shade's clear and
- * its tile walk — take at most
+ * its tile walk, orbit_fragments_shade_shadowed's clear and its tile walk — take at most
  * `max_workgroups` workgroups (of four waves; a wave takes its 8 x 8 tiles one after another, so under a cap of c wave g
  * takes tiles g, g + 4c, ... of even a small target).  Read when the call is enqueued: a captured launch carries its
  * grid.  0, the default, restores num_cus * 8.  The outputs do not depend on the grid; the compaction's scan, totals and
@@ -1690,6 +1690,144 @@ ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShade, flags) == 156, "flags @156");
 
 /* forward.frag's clustered lighting of every visible pixel; see above */
 int32_t orbit_fragments_shade(OrbitCtx *ctx, const OrbitFragmentsShade *job, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* Clustered lighting with cascaded PCSS shadows.                           */
+/* orbit_fragments_shade_shadowed is orbit_fragments_shade with L5's        */
+/* directional branch served: a directional light whose shadow_data_index   */
+/* is not 0xFFFFFFFF is multiplied by forward.frag's shadow term (:81-184,  */
+/* :406-459): cascade selection, normal and oriented bias, the 12-tap       */
+/* blocker search and the 32 x 4-tap percentage-closer filter over float    */
+/* depth maps the caller drew (orbit_raster_depth under each cascade's      */
+/* light_projection_matrix with ORBIT_RASTER_CLEAR: reversed z).  ONE       */
+/* definition for the device and the host mirror                            */
+/* (orbit_host_fragments_shade_shadowed, csrc/shadow_common.h); the two     */
+/* agree on every byte.  The job starts with an OrbitFragmentsShade: same   */
+/* meaning, same checks.  Arithmetic as in L: fp32, every operation rounded */
+/* on its own, never contracted, IEEE '/', GLSL max / clamp, matrix x       */
+/* vector as R2's left-to-right rounded sums ((m0 * x + m4 * y) + m8 * z) + */
+/* m12 * w.  L1-L4, L6-L9 and L5's point and sky branches hold unchanged.   */
+/*  H1 which lights.  A directional light with shadow_data_index = s !=     */
+/*     0xFFFFFFFF is a SHADOWED light; its row is r = s - shadow_index_base */
+/*     (u32 arithmetic).  r >= shadow_count makes the pixel STALE           */
+/*     (ORBIT_E_RANGE, not written); nothing is read before it is known to  */
+/*     be in range.  A shadowed light no longer counts the pixel in         */
+/*     unserved_pixels; sky still does.                                     */
+/*  H2 cascade selection (:414-421, check_ndc_bounds).  For i = 0..3: c =   */
+/*     M_i x world_pos[p] (all four floats as they arrive), q = c / c.w     */
+/*     over all four components; q is inside iff q.x >= -1, q.y >= -1, q.z  */
+/*     >= 0, q.w >= 0 and every component <= 1 (NaN fails).  The first i    */
+/*     inside wins.  None: shadow = 1, cascade = 4, the pixel counts in     */
+/*     no_cascade_pixels.                                                   */
+/*  H3 map = shadow_map_indices[cascade]; map >= shadow_map_count makes the */
+/*     pixel STALE.  texel = 1.0f / (float)shadow_resolution.               */
+/*  H4 bias (:426-435).  ndl = dot(N, direction); nos = clamp(1 - ndl, 0,   */
+/*     1); off_c = ((texel * normal_bias_scale) * nos) * N_c; ob = ndl > 0  */
+/*     ? -oriented_bias : oriented_bias; sp_c = (wp_c + off_c) + ob *       */
+/*     direction_c.  oriented_bias is taken as given: the reference sends   */
+/*     it negated (shadow_renderer.rs:129).                                 */
+/*  H5 coordinates (:135-137, :437-442).  c = M_cascade x (sp, 1); x = c.x  */
+/*     / c.w, y = (c.y / c.w) * -1, z = c.z / c.w; u = (x + 1) * 0.5, v =   */
+/*     (y + 1) * 0.5; inv_ws = 1 / world_size[cascade]; light_uv =          */
+/*     inner_radius * inv_ws.                                               */
+/*  H6 noise and rotation (functions.glsl:109-112, :140-143).  The seed is  */
+/*     the pixel centre (sx, sy) = (x + 0.5, y + 0.5); fract(a) = a -       */
+/*     floorf(a); ign = fract(52.9829189f * fract(sx * 0.06711056f + sy *   */
+/*     0.00583715f)); theta = (ign * 2) * PI (L6's PI); (s, c) = (sinc,     */
+/*     cosc)(theta): k = (int)(theta * 0.636619772f + 0.5f); r = (theta - k */
+/*     * 1.5703125f) - k * 4.83826794897e-4f; w = r * r; sin_r = ((((       */
+/*     -1.9515295891e-4f * w + 8.3321608736e-3f) * w) + -1.6666654611e-1f)  */
+/*     * w) * r + r; cos_r = ((((2.443315711809948e-5f * w +                */
+/*     -1.388731625493765e-3f) * w) + 4.166664568298827e-2f) * w) * w + (1  */
+/*     - 0.5f * w); (s, c) by k & 3: 0 (sin_r, cos_r), 1 (cos_r, -sin_r), 2 */
+/*     (-sin_r, -cos_r), 3 (-cos_r, sin_r).  GLSL LEAVES sin AND cos        */
+/*     PRECISION TO THE DRIVER: THIS ROUTINE IS THIS PROJECT'S CHOICE.  rot */
+/*     . o = (c * o.x + (-s) * o.y, s * o.x + c * o.y); o_i =               */
+/*     poisson_offsets[i] (forward.frag:14-79) as floats, i < 32.           */
+/*  H7 blocker search (penumbra_poisson; NEAREST, clamp to edge).  rad =    */
+/*     blocker_search_radius * inv_ws; for i < 12: suv = uv + ((rot . o_i)  */
+/*     * rad) * inv_ws (the second inv_ws is the reference's); the texel is */
+/*     (clamp((int)floorf(suv.x * res), 0, res - 1), the same of suv.y),    */
+/*     the conversion saturating, NaN -> 0; t > z: avg = avg + (1 - t),     */
+/*     count++.  count == 0: shadow = 1; count == 12: shadow = 0; both      */
+/*     count in early_out_pixels.  Otherwise avg = avg / (float)count.      */
+/*  H8 filter (:153-170; clamp to edge, GREATER_OR_EQUAL, textureGather).   */
+/*     pen = (((1 - z) - avg) / avg) * light_uv; fr = max(pen * inv_ws,     */
+/*     texel); for i < 32: sp = uv + (rot . o_i) * fr; fx = sp.x * res -    */
+/*     0.5; i0 = floorf(fx), i1 = i0 + 1, both converted (saturating, NaN   */
+/*     -> 0) and clamped to [0, res - 1]; sp.y alike; each of the four      */
+/*     texels is lit iff z >= t (NaN fails).  shadow = (float)lit / 128.0f: */
+/*     the GLSL's float sum, every partial sum an integer below 2^24.  THE  */
+/*     SUB-TEXEL PRECISION OF A GATHER IS THE IMPLEMENTATION'S IN VULKAN:   */
+/*     fp32 AS WRITTEN IS THIS PROJECT'S CHOICE.                            */
+/*  H9 light_sum_c = light_sum_c + (L6_c * shadow) for EVERY directional    */
+/*     light (x * 1.0f is x: with no shadowed light in any list color,      */
+/*     lights_walked and the base stats equal orbit_fragments_shade's byte  */
+/*     for byte).  render_mode 8: H1 still range-checks s (the light's type */
+/*     and shadow_data_index are read), nothing else of H is evaluated,     */
+/*     shadow_factor and cascade take their defaults and the four shadow    */
+/*     counters stay 0.                                                     */
+/*  H10 shadow_factor[p] = the shadow of the FIRST shadowed light of the    */
+/*     pixel's walk, 1.0f if none (non-finite leaves as +0 under L8);       */
+/*     cascade[p] = that light's cascade 0..3, 4 when none holds the pixel, */
+/*     0xFFFFFFFF with no shadowed light.  Both are written for written     */
+/*     pixels only; ORBIT_SHADE_CLEAR fills them with 1.0f and 0xFFFFFFFF.  */
+/*     OrbitShadowStats, cleared by the call, over written pixels:          */
+/*     shadowed_pixels evaluated H2 at least once; no_cascade_pixels /      */
+/*     early_out_pixels had at least one evaluation end so;                 */
+/*     shadow_evaluations = the sum of shadowed lights walked.  Every       */
+/*     output depends on its own pixel only.                                */
+/* shadow_count == 0 is valid: every shadowed light makes its pixel STALE.  */
+/* OUT OF SCOPE: the reference's D16_UNORM quantisation of the maps and the */
+/* rasteriser's slope-scaled depth bias (shadow_renderer.rs:414-416) — the  */
+/* maps are whatever floats the caller drew —, render_mode 1 (the cascade   */
+/* debug view: the cascade plane carries it), textures and sky.             */
+/*   ORBIT_E_INVALID  (message prefix fragments_shade_shadowed:) everything */
+/*                    orbit_fragments_shade rejects; shadow_count > 0 with  */
+/*                    shadows or shadow_maps NULL, shadows not 16-B         */
+/*                    aligned, shadow_resolution 0 or above                 */
+/*                    ORBIT_RASTER_MAX_DIM, or shadow_map_count * res^2 >   */
+/*                    2^31 floats; a buffer not 4-B aligned; an output      */
+/*                    pointer equal to an input pointer.                    */
+/* Kernel launches only: no allocation, no scratch, no host wait; a graph   */
+/* captures the call on a fresh context's first call.                       */
+/* ------------------------------------------------------------------------ */
+typedef struct OrbitShadowData { /* DEVICE, 288 B: types.glsl:29-33 in std430 */
+    float light_projection_matrices[4][16]; /* column-major */
+    float shadow_map_world_sizes[4];
+    uint32_t shadow_map_indices[4]; /* into shadow_maps: the caller maps its bindless indices onto that array */
+} OrbitShadowData;
+ORBIT_STATIC_ASSERT(sizeof(OrbitShadowData) == 288, "ShadowData is 288 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitShadowData, shadow_map_world_sizes) == 256, "shadow_map_world_sizes @256");
+ORBIT_STATIC_ASSERT(offsetof(OrbitShadowData, shadow_map_indices) == 272, "shadow_map_indices @272");
+typedef struct OrbitShadowStats { /* DEVICE, 16 B, cleared by the call (H10) */
+    uint32_t shadowed_pixels, no_cascade_pixels, early_out_pixels, shadow_evaluations;
+} OrbitShadowStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitShadowStats) == 16, "ShadowStats is 16 B");
+typedef struct OrbitFragmentsShadeShadowed { /* HOST block, 232 B; every pointer a DEVICE pointer */
+    OrbitFragmentsShade shade;      /* as orbit_fragments_shade takes it */
+    const OrbitShadowData *shadows; /* shadow_count rows of 288 B, 16-B aligned */
+    const float *shadow_maps;       /* shadow_map_count maps of res * res floats: map k at float k * res * res, row pitch res */
+    float *shadow_factor;           /* NULL, or 1 float per pixel */
+    uint32_t *cascade;              /* NULL, or 1 word per pixel */
+    OrbitShadowStats *shadow_stats; /* NULL, or the counters */
+    uint32_t shadow_count;
+    uint32_t shadow_index_base; /* MAX_SHADOW_COMMANDS * frame_index, as orbit_scene_update takes it */
+    uint32_t shadow_map_count, shadow_resolution;
+    float blocker_search_radius, normal_bias_scale, oriented_bias; /* ShadowSettings, types.glsl:35-40 */
+    uint32_t _pad;
+} OrbitFragmentsShadeShadowed;
+ORBIT_STATIC_ASSERT(sizeof(OrbitFragmentsShadeShadowed) == 232, "FragmentsShadeShadowed is 232 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeShadowed, shadows) == 160, "shadows @160");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeShadowed, shadow_factor) == 176, "shadow_factor @176");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeShadowed, shadow_stats) == 192, "shadow_stats @192");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeShadowed, shadow_count) == 200, "shadow_count @200");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeShadowed, shadow_resolution) == 212, "shadow_resolution @212");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeShadowed, blocker_search_radius) == 216, "blocker_search_radius @216");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeShadowed, oriented_bias) == 224, "oriented_bias @224");
+
+/* forward.frag's clustered lighting with cascaded PCSS shadows of every visible pixel; see above */
+int32_t orbit_fragments_shade_shadowed(OrbitCtx *ctx, const OrbitFragmentsShadeShadowed *job, void *stream);
 
 #ifdef __cplusplus
 }

@@ -185,6 +185,21 @@ def fill_fragments_shade(j, cluster_count, tile_size_px, z_scale, z_bias, lumina
     j.flags = (SHADE_CLEAR if clear else 0) | (form if isinstance(form, int) else forms[form])  # an int: raw flag bits
 
 
+class FragmentsShadeShadowed(C.Structure):  # OrbitFragmentsShadeShadowed (232 B)
+    _fields_ = [("shade", FragmentsShade), ("shadows", C.c_void_p), ("shadow_maps", C.c_void_p), ("shadow_factor", C.c_void_p),
+                ("cascade", C.c_void_p), ("shadow_stats", C.c_void_p), ("shadow_count", C.c_uint32), ("shadow_index_base", C.c_uint32),
+                ("shadow_map_count", C.c_uint32), ("shadow_resolution", C.c_uint32), ("blocker_search_radius", C.c_float),
+                ("normal_bias_scale", C.c_float), ("oriented_bias", C.c_float), ("_pad", C.c_uint32)]
+
+
+def fill_shadow_fields(j, shadow_count, shadow_index_base, shadow_map_count, shadow_resolution, blocker_search_radius, normal_bias_scale,
+                       oriented_bias):
+    """The by-value shadow fields of an OrbitFragmentsShadeShadowed; oriented_bias as the reference sends it (negated)."""
+    j.shadow_count, j.shadow_index_base = int(shadow_count), int(shadow_index_base)
+    j.shadow_map_count, j.shadow_resolution = int(shadow_map_count), int(shadow_resolution)
+    j.blocker_search_radius, j.normal_bias_scale, j.oriented_bias = float(blocker_search_radius), float(normal_bias_scale), float(oriented_bias)
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -292,6 +307,7 @@ SYMBOLS = {
     "orbit_visibility_surface_drawn": (C.c_int32, [C.c_void_p, C.POINTER(VisibilitySurface), C.c_uint32, C.c_void_p]),
     "orbit_surface_fragments": (C.c_int32, [C.c_void_p, C.POINTER(SurfaceFragments), C.c_void_p]),
     "orbit_fragments_shade": (C.c_int32, [C.c_void_p, C.POINTER(FragmentsShade), C.c_void_p]),
+    "orbit_fragments_shade_shadowed": (C.c_int32, [C.c_void_p, C.POINTER(FragmentsShadeShadowed), C.c_void_p]),
 }
 
 _lib = None

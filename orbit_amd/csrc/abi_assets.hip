@@ -6,7 +6,8 @@
 // orbit_visibility_surface, its barycentrics, differences and ids per pixel (visibility_surface.hip), with
 // orbit_visibility_surface_drawn, the same for a buffer drawn with the raster flags (visibility_surface_drawn.hip), and
 // orbit_surface_fragments, the fragment shader's inputs per pixel from those and the vertex attributes
-// (surface_fragments.hip), and orbit_fragments_shade, the clustered lighting of those pixels (fragments_shade.hip).
+// (surface_fragments.hip), and orbit_fragments_shade, the clustered lighting of those pixels (fragments_shade.hip), with
+// orbit_fragments_shade_shadowed, the same with cascaded shadows served (fragments_shade_shadowed.hip).
 #include "abi_internal.h"
 
 namespace {
@@ -294,44 +295,84 @@ int32_t orbit_surface_fragments(OrbitCtx *ctx, const OrbitSurfaceFragments *job,
     return ORBIT_OK;
 }
 
-// A clearing launch (stats, and with ORBIT_SHADE_CLEAR color and lights_walked) and the shading launch
-// (fragments_shade.hip).  No allocation, no scratch, no host sync: capturable on the first call.  As its siblings, the
-// job is checked before the context is looked at, each error with a message of its own.
-int32_t orbit_fragments_shade(OrbitCtx *ctx, const OrbitFragmentsShade *job, void *stream) {
-    if (!job) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: job is NULL");
-    const OrbitFragmentsShade &j = *job;
+// The checks of an OrbitFragmentsShade, for orbit_fragments_shade and for orbit_fragments_shade_shadowed, which starts with
+// one: each error with a message of its own behind the caller's prefix `who`
+static int32_t check_fragments_shade(OrbitCtx *ctx, const char *who, const OrbitFragmentsShade &j) {
     const uint32_t known = ORBIT_SHADE_CLEAR | ORBIT_SHADE_FORCE_PER_LANE | ORBIT_SHADE_FORCE_STAGED;
-    if (j.flags & ~known) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: flags %#x", j.flags);
+    if (j.flags & ~known) return fail(ctx, ORBIT_E_INVALID, "%s: flags %#x", who, j.flags);
     if ((j.flags & ORBIT_SHADE_FORCE_PER_LANE) && (j.flags & ORBIT_SHADE_FORCE_STAGED))
-        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: ORBIT_SHADE_FORCE_PER_LANE and ORBIT_SHADE_FORCE_STAGED together");
-    if (j.render_mode != 0u && j.render_mode != 8u) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: render_mode %u (0 or 8)", j.render_mode);
+        return fail(ctx, ORBIT_E_INVALID, "%s: ORBIT_SHADE_FORCE_PER_LANE and ORBIT_SHADE_FORCE_STAGED together", who);
+    if (j.render_mode != 0u && j.render_mode != 8u) return fail(ctx, ORBIT_E_INVALID, "%s: render_mode %u (0 or 8)", who, j.render_mode);
     if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
-        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+        return fail(ctx, ORBIT_E_INVALID, "%s: target %u x %u (1..%u each)", who, j.width, j.height, ORBIT_RASTER_MAX_DIM);
     if (j.cluster_count[0] == 0 || j.cluster_count[1] == 0 || j.cluster_count[2] == 0 || j.tile_size_px == 0)
-        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: cluster_count %u x %u x %u, tile_size_px %u (none may be 0)", j.cluster_count[0],
+        return fail(ctx, ORBIT_E_INVALID, "%s: cluster_count %u x %u x %u, tile_size_px %u (none may be 0)", who, j.cluster_count[0],
                     j.cluster_count[1], j.cluster_count[2], j.tile_size_px);
-    if (j.cluster_count[2] > 32u) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: cluster_count[2] %u > 32", j.cluster_count[2]);
+    if (j.cluster_count[2] > 32u) return fail(ctx, ORBIT_E_INVALID, "%s: cluster_count[2] %u > 32", who, j.cluster_count[2]);
     if ((uint64_t)j.cluster_count[0] * j.cluster_count[1] > (1ull << 31) / j.cluster_count[2])
-        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: %u x %u x %u clusters > 2^31", j.cluster_count[0], j.cluster_count[1], j.cluster_count[2]);
+        return fail(ctx, ORBIT_E_INVALID, "%s: %u x %u x %u clusters > 2^31", who, j.cluster_count[0], j.cluster_count[1], j.cluster_count[2]);
     if ((j.flags & ORBIT_SHADE_FORCE_STAGED) && j.tile_size_px % 8u != 0u)
-        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: ORBIT_SHADE_FORCE_STAGED needs tile_size_px %u %% 8 == 0", j.tile_size_px);
+        return fail(ctx, ORBIT_E_INVALID, "%s: ORBIT_SHADE_FORCE_STAGED needs tile_size_px %u %% 8 == 0", who, j.tile_size_px);
     if (!j.visibility || !j.world_pos || !j.normal || !j.material || !j.materials || !j.lights || !j.cluster_offset_image ||
         !j.light_index_buffer || !j.color)
-        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: NULL buffer");
+        return fail(ctx, ORBIT_E_INVALID, "%s: NULL buffer", who);
     const void *const inputs[8] = {j.visibility, j.world_pos, j.normal, j.material, j.materials, j.lights, j.cluster_offset_image, j.light_index_buffer};
     const void *const outputs[3] = {j.color, j.lights_walked, j.stats};
     uintptr_t low_bits = 0;
     for (const void *in : inputs) low_bits |= (uintptr_t)in;
     for (const void *out : outputs) low_bits |= (uintptr_t)out;
     if ((((uintptr_t)j.visibility | (uintptr_t)j.cluster_offset_image) & 7u) || (((uintptr_t)j.materials | (uintptr_t)j.lights) & 15u) || (low_bits & 3u))
-        return fail(ctx, ORBIT_E_INVALID, "fragments_shade: visibility and cluster_offset_image must be 8-B aligned, materials and lights 16-B aligned, every other buffer 4-B aligned");
+        return fail(ctx, ORBIT_E_INVALID, "%s: visibility and cluster_offset_image must be 8-B aligned, materials and lights 16-B aligned, every other buffer 4-B aligned", who);
     for (const void *out : outputs)
         for (const void *in : inputs)
-            if (out && out == in) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: an output is an input (%p)", out);
+            if (out && out == in) return fail(ctx, ORBIT_E_INVALID, "%s: an output is an input (%p)", who, out);
+    return ORBIT_OK;
+}
+
+// A clearing launch (stats, and with ORBIT_SHADE_CLEAR color and lights_walked) and the shading launch
+// (fragments_shade.hip).  No allocation, no scratch, no host sync: capturable on the first call.  As its siblings, the
+// job is checked before the context is looked at, each error with a message of its own.
+int32_t orbit_fragments_shade(OrbitCtx *ctx, const OrbitFragmentsShade *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "fragments_shade: job is NULL");
+    const OrbitFragmentsShade &j = *job;
+    const int32_t checked = check_fragments_shade(ctx, "fragments_shade", j);
+    if (checked != ORBIT_OK) return checked;
     if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "fragments_shade: ctx is NULL");
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_fragments_shade(j, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch fragments_shade");
+    return ORBIT_OK;
+}
+
+// The same two launches with the shadow term served (fragments_shade_shadowed.hip): the base job's checks under this
+// call's prefix, then the shadow fields'.
+int32_t orbit_fragments_shade_shadowed(OrbitCtx *ctx, const OrbitFragmentsShadeShadowed *job, void *stream) {
+    const char *who = "fragments_shade_shadowed";
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "%s: job is NULL", who);
+    const OrbitFragmentsShadeShadowed &j = *job;
+    const OrbitFragmentsShade &b = j.shade;
+    const int32_t checked = check_fragments_shade(ctx, who, b);
+    if (checked != ORBIT_OK) return checked;
+    if (j.shadow_count > 0u) {
+        if (!j.shadows || !j.shadow_maps) return fail(ctx, ORBIT_E_INVALID, "%s: shadow_count %u with shadows or shadow_maps NULL", who, j.shadow_count);
+        if ((uintptr_t)j.shadows & 15u) return fail(ctx, ORBIT_E_INVALID, "%s: shadows must be 16-B aligned", who);
+        if (j.shadow_resolution == 0u || j.shadow_resolution > ORBIT_RASTER_MAX_DIM)
+            return fail(ctx, ORBIT_E_INVALID, "%s: shadow_resolution %u (1..%u)", who, j.shadow_resolution, ORBIT_RASTER_MAX_DIM);
+        if ((uint64_t)j.shadow_map_count * j.shadow_resolution * j.shadow_resolution > (1ull << 31))
+            return fail(ctx, ORBIT_E_INVALID, "%s: %u maps of %u x %u floats > 2^31", who, j.shadow_map_count, j.shadow_resolution, j.shadow_resolution);
+    }
+    const void *const inputs[10] = {b.visibility, b.world_pos, b.normal, b.material, b.materials, b.lights, b.cluster_offset_image,
+                                    b.light_index_buffer, j.shadows, j.shadow_maps};
+    const void *const outputs[6] = {b.color, b.lights_walked, b.stats, j.shadow_factor, j.cascade, j.shadow_stats};
+    if (((uintptr_t)j.shadow_maps | (uintptr_t)j.shadow_factor | (uintptr_t)j.cascade | (uintptr_t)j.shadow_stats) & 3u)
+        return fail(ctx, ORBIT_E_INVALID, "%s: shadow_maps, shadow_factor, cascade and shadow_stats must be 4-B aligned", who);
+    for (const void *out : outputs)
+        for (const void *in : inputs)
+            if (out && out == in) return fail(ctx, ORBIT_E_INVALID, "%s: an output is an input (%p)", who, out);
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "%s: ctx is NULL", who);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_fragments_shade_shadowed(j, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch fragments_shade_shadowed");
     return ORBIT_OK;
 }
 

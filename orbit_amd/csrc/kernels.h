@@ -455,6 +455,11 @@ hipError_t launch_surface_fragments(const OrbitSurfaceFragments &job, uint32_t n
 // cluster's light list per lane or staged through LDS (tile_size_px % 8 == 0, the default there)
 hipError_t launch_fragments_shade(const OrbitFragmentsShade &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
                                   hipStream_t s);
+// fragments_shade_shadowed.hip: orbit_fragments_shade_shadowed — `job` validated by the entry point.  The same two
+// launches with H1-H10 served: the clear also fills shadow_factor and cascade and clears shadow_stats; the walk, in the
+// form the same rule chooses, evaluates cascade selection, blocker search and filter per lane
+hipError_t launch_fragments_shade_shadowed(const OrbitFragmentsShadeShadowed &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
+                                           hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

@@ -137,8 +137,10 @@ ORBIT_RASTER_FN void shade_pixel_begin(const OrbitFragmentsShade &j, const Orbit
     px.ndv4 = 4.0f * px.ndv;
 }
 
-// L5 and L6 of one light of the walk
-ORBIT_RASTER_FN void shade_pixel_light(const ShadeLight &l, float luminance_cutoff, ShadePixel &px) {
+// L5 and L6 of one light of the walk -> the light has a term, the L6_c it adds.  SHADOWS_SERVED (shadow_common.h): a
+// shadowed directional light does not mark the pixel unserved
+template <bool SHADOWS_SERVED = false>
+ORBIT_RASTER_FN bool shade_light_term(const ShadeLight &l, float luminance_cutoff, ShadePixel &px, float *term) {
     float Ld[3], att;
     if (l.type == kLightPoint) {
         for (int i = 0; i < 3; i++) Ld[i] = l.position[i] - px.wp[i];
@@ -150,10 +152,10 @@ ORBIT_RASTER_FN void shade_pixel_light(const ShadeLight &l, float luminance_cuto
     } else if (l.type == kLightDirectional) {
         for (int i = 0; i < 3; i++) Ld[i] = l.direction[i];
         att = 1.0f;
-        if (l.shadow != kNone) px.unserved = true;
+        if (!SHADOWS_SERVED && l.shadow != kNone) px.unserved = true;
     } else {
         if (l.type == kLightSky) px.unserved = true;
-        return;
+        return false;
     }
     float H[3];
     for (int i = 0; i < 3; i++) H[i] = px.V[i] + Ld[i];
@@ -170,8 +172,14 @@ ORBIT_RASTER_FN void shade_pixel_light(const ShadeLight &l, float luminance_cuto
         const float F = px.f0[i] + px.one_minus_f0[i] * p5;
         const float spec = (DG * F) / spec_den;
         const float kD = (1.0f - F) * px.one_minus_metallic;
-        px.sum[i] = px.sum[i] + ((((kD * px.albedo[i]) / kShadePi) + spec) * (l.lc[i] * att)) * ndl;
+        term[i] = ((((kD * px.albedo[i]) / kShadePi) + spec) * (l.lc[i] * att)) * ndl;
     }
+    return true;
+}
+ORBIT_RASTER_FN void shade_pixel_light(const ShadeLight &l, float luminance_cutoff, ShadePixel &px) {
+    float term[3];
+    if (!shade_light_term(l, luminance_cutoff, px, term)) return;
+    for (int i = 0; i < 3; i++) px.sum[i] = px.sum[i] + term[i];
 }
 
 // L7 and L8 of mode 0 -> the pixel was degenerate

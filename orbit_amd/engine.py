@@ -526,6 +526,37 @@ class Engine:
                                   width, height, clear, form)
         _lib.check(self._lib.orbit_fragments_shade(self._ctx, C.byref(j), _stream(stream)), self._ctx)
 
+    # -- the same with cascaded PCSS shadows served (orbit_fragments_shade_shadowed)
+    def fragments_shade_shadowed(self, visibility, width, height, world_pos, normal, material, materials, material_count, lights,
+                                 light_count, cluster_offset_image, light_index_buffer, index_capacity, cluster_count, tile_size_px,
+                                 z_scale, z_bias, luminance_cutoff, z_near, view_pos, color, shadows, shadow_count, shadow_maps,
+                                 shadow_map_count, shadow_resolution, blocker_search_radius, normal_bias_scale, oriented_bias,
+                                 shadow_index_base=0, shadow_factor=None, cascade=None, shadow_stats=None, lights_walked=None,
+                                 stats=None, render_mode=0, clear=False, form=None, stream=None):
+        """fragments_shade with the reference's shadow term: a directional light whose shadow_data_index is not 0xFFFFFFFF
+        takes row shadow_data_index - shadow_index_base of `shadows` (288-B rows, layouts.SHADOW_DATA) and is multiplied
+        by forward.frag's cascaded PCSS factor, read from `shadow_maps`: shadow_map_count float32 maps of
+        shadow_resolution^2 (reversed z, as raster_depth leaves them with clear=True; orbit_amd.raster.shadow_atlas draws
+        them), which a row's shadow_map_indices index.  blocker_search_radius, normal_bias_scale, oriented_bias: the
+        reference's ShadowSettings, oriented_bias as it sends it (negated).  shadow_factor (1 float per pixel), cascade (1
+        u32 per pixel: 0..3, 4 = no cascade, 0xFFFFFFFF = no shadowed light) and shadow_stats (16 bytes,
+        layouts.SHADOW_STATS) may be None; clear=True fills the two planes with 1.0 and 0xFFFFFFFF.  A shadow row or map
+        index out of range makes the pixel stale (ORBIT_E_RANGE).  Byte-equal to
+        orbit_amd.raster.host_fragments_shade_shadowed.  Enqueued on `stream`."""
+        js = _lib.FragmentsShadeShadowed()
+        j = js.shade
+        j.visibility, j.world_pos, j.normal, j.material = _ptr(visibility), _ptr(world_pos), _ptr(normal), _ptr(material)
+        j.materials, j.lights, j.cluster_offset_image = _ptr(materials), _ptr(lights), _ptr(cluster_offset_image)
+        j.light_index_buffer, j.color, j.lights_walked, j.stats = _ptr(light_index_buffer), _ptr(color), _ptr(lights_walked), _ptr(stats)
+        j.material_count, j.light_count, j.index_capacity = int(material_count), int(light_count), int(index_capacity)
+        _lib.fill_fragments_shade(j, cluster_count, tile_size_px, z_scale, z_bias, luminance_cutoff, z_near, view_pos, render_mode,
+                                  width, height, clear, form)
+        js.shadows, js.shadow_maps, js.shadow_factor = _ptr(shadows), _ptr(shadow_maps), _ptr(shadow_factor)
+        js.cascade, js.shadow_stats = _ptr(cascade), _ptr(shadow_stats)
+        _lib.fill_shadow_fields(js, shadow_count, shadow_index_base, shadow_map_count, shadow_resolution, blocker_search_radius,
+                                normal_bias_scale, oriented_bias)
+        _lib.check(self._lib.orbit_fragments_shade_shadowed(self._ctx, C.byref(js), _stream(stream)), self._ctx)
+
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                    entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,
@@ -852,7 +883,8 @@ class Engine:
 
     def set_visibility_grid(self, max_workgroups):
         """orbit_ctx_set_visibility_grid: at most that many workgroups for the strided launches of visibility_resolve,
-        visibility_compact (clear and mark), visibility_surface, surface_fragments and fragments_shade, read when the call is
+        visibility_compact (clear and mark), visibility_surface, surface_fragments, fragments_shade and
+        fragments_shade_shadowed, read when the call is
         enqueued (0 = num_cus * 8; tests)."""
         _lib.check(self._lib.orbit_ctx_set_visibility_grid(self._ctx, int(max_workgroups)), self._ctx)
 

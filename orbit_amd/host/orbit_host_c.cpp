@@ -13,6 +13,7 @@
 #include "orbit_scene.hpp"
 #include "../csrc/block_pretest.h"
 #include "../csrc/shade_common.h"
+#include "../csrc/shadow_common.h"
 
 using namespace orbit;
 using namespace orbit::passes;
@@ -631,6 +632,17 @@ int32_t orbit_host_fragments_shade(const OrbitFragmentsShade *job, int32_t *stat
         if (!job) throw Panic("fragments_shade: job is NULL");
         raster::fragments_shade(*job, status);
     });
+}
+
+int32_t orbit_host_fragments_shade_shadowed(const OrbitFragmentsShadeShadowed *job, int32_t *status) {
+    return guarded([&] {
+        if (!job) throw Panic("fragments_shade_shadowed: job is NULL");
+        raster::fragments_shade_shadowed(*job, status);
+    });
+}
+
+void orbit_host_shadow_rotation(uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float *theta, float *sine, float *cosine) {
+    raster::shadow_rotation(x0, y0, width, height, theta, sine, cosine);
 }
 
 // canonical log2 and slice of shade_common.h, for tests

@@ -264,6 +264,12 @@ int32_t orbit_host_surface_fragments(const OrbitSurfaceFragments *job, int32_t *
  * and stats hold the device's bytes.  *status (may be NULL): ORBIT_E_RANGE if a pixel was stale, else ORBIT_OK.
  * ORBIT_HOST_PANIC for what the device answers with ORBIT_E_INVALID (alignment and aliasing aside). */
 int32_t orbit_host_fragments_shade(const OrbitFragmentsShade *job, int32_t *status);
+/* the reference of orbit_fragments_shade_shadowed (H1-H10): the device call's block with HOST pointers in it, as
+ * orbit_host_fragments_shade; shadow_factor, cascade and shadow_stats hold the device's bytes too. */
+int32_t orbit_host_fragments_shade_shadowed(const OrbitFragmentsShadeShadowed *job, int32_t *status);
+/* tests: H6 of the pixels (x0 + x, y0 + y), x < width, y < height, row-major into three arrays of width * height floats:
+ * theta and csrc/shadow_common.h's sine and cosine of it */
+void orbit_host_shadow_rotation(uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float *theta, float *sine, float *cosine);
 /* tests: the host restatement of the canonical log2 (held to the oracle's) and L2's slice of a depth d */
 float orbit_host_shade_log2(float x);
 uint32_t orbit_host_shade_slice(float z_near, float d, float z_scale, float z_bias);

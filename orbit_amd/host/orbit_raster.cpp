@@ -1,12 +1,14 @@
 // orbit_raster.cpp — see orbit_raster.hpp.
 #include "orbit_raster.hpp"
 
+#include <algorithm>
 #include <cstring>
 
 #include "../csrc/raster_common.h"
 #include "../csrc/surface_common.h"
 #include "../csrc/fragment_common.h"
 #include "../csrc/shade_common.h"
+#include "../csrc/shadow_common.h"
 #include "orbit_host.hpp"
 
 namespace orbit {
@@ -440,7 +442,8 @@ void surface_fragments(const OrbitSurfaceFragments &j, int32_t *status) {
     if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
 }
 
-void fragments_shade(const OrbitFragmentsShade &j, int32_t *status) {
+// what both shade mirrors throw for the base job
+static void check_fragments_shade(const OrbitFragmentsShade &j) {
     const uint32_t known = ORBIT_SHADE_CLEAR | ORBIT_SHADE_FORCE_PER_LANE | ORBIT_SHADE_FORCE_STAGED;
     if (j.flags & ~known) throw Panic("fragments_shade: unknown flags");
     if ((j.flags & ORBIT_SHADE_FORCE_PER_LANE) && (j.flags & ORBIT_SHADE_FORCE_STAGED)) throw Panic("fragments_shade: both forms forced");
@@ -455,6 +458,10 @@ void fragments_shade(const OrbitFragmentsShade &j, int32_t *status) {
     if (!j.visibility || !j.world_pos || !j.normal || !j.material || !j.materials || !j.lights || !j.cluster_offset_image ||
         !j.light_index_buffer || !j.color)
         throw Panic("fragments_shade: NULL argument");
+}
+
+void fragments_shade(const OrbitFragmentsShade &j, int32_t *status) {
+    check_fragments_shade(j);
     const size_t pixels = (size_t)j.width * j.height;
     if (j.flags & ORBIT_SHADE_CLEAR) { // L9
         std::memset(j.color, 0, pixels * 16);
@@ -483,6 +490,65 @@ void fragments_shade(const OrbitFragmentsShade &j, int32_t *status) {
     }
     if (j.stats) *j.stats = st;
     if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
+}
+
+void fragments_shade_shadowed(const OrbitFragmentsShadeShadowed &j, int32_t *status) {
+    const OrbitFragmentsShade &b = j.shade;
+    check_fragments_shade(b);
+    if (j.shadow_count > 0u) {
+        if (!j.shadows || !j.shadow_maps) throw Panic("fragments_shade_shadowed: shadow_count > 0 with shadows or shadow_maps NULL");
+        if (j.shadow_resolution == 0u || j.shadow_resolution > ORBIT_RASTER_MAX_DIM) throw Panic("fragments_shade_shadowed: shadow_resolution");
+        if ((uint64_t)j.shadow_map_count * j.shadow_resolution * j.shadow_resolution > (1ull << 31))
+            throw Panic("fragments_shade_shadowed: shadow maps > 2^31 floats");
+    }
+    const size_t pixels = (size_t)b.width * b.height;
+    if (b.flags & ORBIT_SHADE_CLEAR) { // L9, H10
+        std::memset(b.color, 0, pixels * 16);
+        if (b.lights_walked) std::memset(b.lights_walked, 0, pixels * 4);
+        if (j.shadow_factor) std::fill(j.shadow_factor, j.shadow_factor + pixels, 1.0f);
+        if (j.cascade) std::fill(j.cascade, j.cascade + pixels, kNone);
+    }
+    OrbitShadeStats st{};
+    OrbitShadowStats sh{};
+    for (size_t p = 0; p < pixels; p++) {
+        const uint64_t word = b.visibility[p];
+        if (word == 0) continue;
+        st.covered_pixels++;
+        const uint32_t x = (uint32_t)(p % b.width), y = (uint32_t)(p / b.width);
+        const uint32_t slice = shade_slice_canonical(b.z_near, bits_float((int32_t)(uint32_t)(word >> 32)), b.z_scale, b.z_bias); // L2
+        float color[4];
+        uint32_t n, marks;
+        ShadowPixel sp;
+        const uint32_t verdict = shadow_shade_pixel(j, x, y, p, slice, color, n, marks, sp);
+        if (verdict == kShadeUnshaded) st.unshaded_pixels++;
+        if (verdict == kShadeStale) st.stale_pixels++;
+        if (verdict != kShadeWritten) continue;
+        st.written_pixels++;
+        if (marks & kShadeOutside) st.outside_pixels++;
+        if (marks & kShadeDegenerate) st.degenerate_pixels++;
+        if (marks & kShadeTextured) st.textured_pixels++;
+        if (marks & kShadeUnserved) st.unserved_pixels++;
+        if (sp.marks & kShadowEvaluated) sh.shadowed_pixels++;
+        if (sp.marks & kShadowOutOfCascades) sh.no_cascade_pixels++;
+        if (sp.marks & kShadowEarlyOut) sh.early_out_pixels++;
+        sh.shadow_evaluations += sp.evaluations;
+        std::memcpy(b.color + 4 * p, color, 16);
+        if (b.lights_walked) b.lights_walked[p] = n;
+        if (j.shadow_factor) j.shadow_factor[p] = sp.factor;
+        if (j.cascade) j.cascade[p] = sp.cascade;
+    }
+    if (b.stats) *b.stats = st;
+    if (j.shadow_stats) *j.shadow_stats = sh;
+    if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
+}
+
+void shadow_rotation(uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float *theta, float *sine, float *cosine) {
+    for (uint32_t y = 0; y < height; y++)
+        for (uint32_t x = 0; x < width; x++) {
+            const size_t i = (size_t)y * width + x;
+            theta[i] = shadow_theta(x0 + x, y0 + y);
+            shadow_sincos(theta[i], sine[i], cosine[i]);
+        }
 }
 
 } // namespace raster

@@ -67,5 +67,11 @@ void surface_fragments(const OrbitSurfaceFragments &job, int32_t *status);
 // for ORBIT_E_INVALID (alignment and aliasing aside).
 void fragments_shade(const OrbitFragmentsShade &job, int32_t *status);
 
+// orbit_fragments_shade_shadowed (H1-H10 on L1-L9, §4.26) on host buffers, as fragments_shade: the obvious loop over the
+// pixels, each through ../csrc/shadow_common.h.  Throws Panic for ORBIT_E_INVALID (alignment and aliasing aside).
+void fragments_shade_shadowed(const OrbitFragmentsShadeShadowed &job, int32_t *status);
+// H6 of the pixels (x0 + x, y0 + y), x < width, y < height, row-major: theta and the project's sine and cosine of it
+void shadow_rotation(uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float *theta, float *sine, float *cosine);
+
 } // namespace raster
 } // namespace orbit

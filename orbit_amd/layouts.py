@@ -75,6 +75,11 @@ SURFACE_FRAGMENT_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "writt
 # OrbitShadeStats: the counters of orbit_fragments_shade
 SHADE_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "written_pixels", "unshaded_pixels", "stale_pixels", "outside_pixels",
                                              "degenerate_pixels", "textured_pixels", "unserved_pixels")])
+# OrbitShadowStats: the counters orbit_fragments_shade_shadowed adds
+SHADOW_STATS = np.dtype([(n, "<u4") for n in ("shadowed_pixels", "no_cascade_pixels", "early_out_pixels", "shadow_evaluations")])
+# OrbitShadowData, types.glsl:29-33 in std430 (288 B): the matrices column-major
+SHADOW_DATA = np.dtype([("light_projection_matrices", "<f4", (4, 16)), ("shadow_map_world_sizes", "<f4", (4,)),
+                        ("shadow_map_indices", "<u4", (4,))])
 # types.glsl:64-73, src/assets/mesh.rs:14-20: the reference's MeshVertex, 32 B (normal and tangent as snorm8)
 MESH_VERTEX = np.dtype([("position", "<f4", (3,)), ("normal", "i1", (4,)), ("uv", "<f4", (2,)), ("tangent", "i1", (4,)),
                         ("_padding", "<u4")])

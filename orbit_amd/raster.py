@@ -6,7 +6,9 @@ list of such a buffer, the reference of ``Engine.visibility_compact``, and of ``
 barycentrics and ids per pixel of such a buffer, the reference of ``Engine.visibility_surface``, and of
 ``orbit_surface_fragments``, the fragment shader's inputs per pixel from those, the reference of
 ``Engine.surface_fragments``, and of ``orbit_fragments_shade``, the clustered lighting of those pixels, the reference of
-``Engine.fragments_shade``.  Python adds nothing; host only."""
+``Engine.fragments_shade``, and of ``orbit_fragments_shade_shadowed``, the same with cascaded shadows, the reference of
+``Engine.fragments_shade_shadowed``, with the two helpers that draw the cascades' maps into one atlas (``host_shadow_atlas``
+on the host, ``shadow_atlas`` through an Engine).  Python adds nothing."""
 import ctypes as C
 
 import numpy as np
@@ -294,6 +296,108 @@ def host_fragments_shade(visibility, world_pos, normal, material, materials, lig
     status = C.c_int32(0)
     _check(lib().orbit_host_fragments_shade(C.byref(j), C.byref(status)))
     return dict(color=color, lights_walked=walked, stats=None if stats is None else stats[0], status=status.value)
+
+
+def host_fragments_shade_shadowed(visibility, world_pos, normal, material, materials, lights, cluster_offset_image, light_index_buffer,
+                                  cluster_count, tile_size_px, z_scale, z_bias, luminance_cutoff, z_near, view_pos, shadows, shadow_maps,
+                                  shadow_resolution, blocker_search_radius, normal_bias_scale, oriented_bias, shadow_index_base=0,
+                                  shadow_count=None, shadow_map_count=None, render_mode=0, clear=True, into=None, form=None,
+                                  material_count=None, light_count=None, index_capacity=None, fill=0, want_walked=True, want_stats=True,
+                                  want_factor=True, want_cascade=True, want_shadow_stats=True):
+    """orbit_host_fragments_shade_shadowed: host_fragments_shade's arguments, then np[layouts.SHADOW_DATA] rows (or None),
+    the maps as float32 (map k at float k * res * res; or None) and the ShadowSettings -> host_fragments_shade's dict with
+    shadow_factor (height, width) np.float32, cascade (height, width) np.uint32 and shadow_stats:
+    np[layouts.SHADOW_STATS] scalar row, each None if not wanted.  With `into` the two planes are taken from it; otherwise
+    they start filled with the u32 `fill`.  The counts default to what the arrays hold."""
+    vis = np.ascontiguousarray(visibility, dtype=np.uint64)
+    height, width = vis.shape
+    wp = np.ascontiguousarray(world_pos, dtype=np.float32).reshape(height, width, 4)
+    nrm = np.ascontiguousarray(normal, dtype=np.float32).reshape(height, width, 3)
+    mat = np.ascontiguousarray(material, dtype=np.uint32).reshape(height, width)
+    mats = np.ascontiguousarray(materials).view(np.uint8).reshape(-1)
+    lts = np.ascontiguousarray(lights).view(np.uint8).reshape(-1)
+    img = np.ascontiguousarray(cluster_offset_image).view(np.uint32).reshape(-1)
+    lib_ = np.ascontiguousarray(light_index_buffer).view(np.uint8).reshape(-1)
+    rows = None if shadows is None else np.ascontiguousarray(shadows).view(np.uint8).reshape(-1)
+    maps = None if shadow_maps is None else np.ascontiguousarray(shadow_maps, dtype=np.float32).reshape(-1)
+    cx, cy, cz = (int(c) for c in cluster_count)
+    if img.size < 2 * cx * cy * cz:
+        raise ValueError("cluster_count reaches beyond the offset image")
+    material_count = mats.nbytes // 80 if material_count is None else int(material_count)
+    light_count = lts.nbytes // 64 if light_count is None else int(light_count)
+    index_capacity = max(lib_.nbytes - 4, 0) // 4 if index_capacity is None else int(index_capacity)
+    res = int(shadow_resolution)
+    shadow_count = (0 if rows is None else rows.nbytes // 288) if shadow_count is None else int(shadow_count)
+    shadow_map_count = (0 if maps is None or res == 0 else maps.size // (res * res)) if shadow_map_count is None else int(shadow_map_count)
+    if material_count * 80 > mats.nbytes or light_count * 64 > lts.nbytes or 4 + 4 * index_capacity > max(lib_.nbytes, 4):
+        raise ValueError("a count reaches beyond its array")
+    if shadow_count * 288 > (0 if rows is None else rows.nbytes) or shadow_map_count * res * res > (0 if maps is None else maps.size):
+        raise ValueError("a shadow count reaches beyond its array")
+    if into is not None:
+        color = np.array(into["color"], dtype=np.float32, order="C").reshape(height, width, 4)
+        walked = None if not want_walked else np.array(into["lights_walked"], dtype=np.uint32, order="C").reshape(height, width)
+        factor = None if not want_factor else np.array(into["shadow_factor"], dtype=np.float32, order="C").reshape(height, width)
+        cascade = None if not want_cascade else np.array(into["cascade"], dtype=np.uint32, order="C").reshape(height, width)
+    else:
+        color = np.full((height, width, 4), fill, np.uint32).view(np.float32)
+        walked = np.full((height, width), fill, np.uint32) if want_walked else None
+        factor = np.full((height, width), fill, np.uint32).view(np.float32) if want_factor else None
+        cascade = np.full((height, width), fill, np.uint32) if want_cascade else None
+    stats = np.zeros(1, L.SHADE_STATS) if want_stats else None
+    shadow_stats = np.zeros(1, L.SHADOW_STATS) if want_shadow_stats else None
+    p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    js = _lib.FragmentsShadeShadowed()
+    j = js.shade
+    j.visibility, j.world_pos, j.normal, j.material, j.materials, j.lights = p(vis), p(wp), p(nrm), p(mat), p(mats), p(lts)
+    j.cluster_offset_image, j.light_index_buffer, j.color, j.lights_walked, j.stats = p(img), p(lib_), p(color), p(walked), p(stats)
+    j.material_count, j.light_count, j.index_capacity = material_count, light_count, index_capacity
+    _lib.fill_fragments_shade(j, (cx, cy, cz), tile_size_px, z_scale, z_bias, luminance_cutoff, z_near, view_pos, render_mode, width,
+                              height, clear, form)
+    js.shadows, js.shadow_maps, js.shadow_factor, js.cascade, js.shadow_stats = p(rows), p(maps), p(factor), p(cascade), p(shadow_stats)
+    _lib.fill_shadow_fields(js, shadow_count, shadow_index_base, shadow_map_count, res, blocker_search_radius, normal_bias_scale, oriented_bias)
+    status = C.c_int32(0)
+    _check(lib().orbit_host_fragments_shade_shadowed(C.byref(js), C.byref(status)))
+    return dict(color=color, lights_walked=walked, stats=None if stats is None else stats[0], status=status.value, shadow_factor=factor,
+                cascade=cascade, shadow_stats=None if shadow_stats is None else shadow_stats[0])
+
+
+def host_shadow_rotation(x0, y0, width, height):
+    """H6 of the pixels (x0 + x, y0 + y), x < width, y < height -> (theta, sine, cosine), each (height, width) np.float32:
+    the mirror's noise angle and csrc/shadow_common.h's sine and cosine of it."""
+    out = [np.empty((height, width), np.float32) for _ in range(3)]
+    fn = lib().orbit_host_shadow_rotation
+    fn.restype, fn.argtypes = None, [C.c_uint32] * 4 + [C.c_void_p] * 3
+    fn(int(x0), int(y0), int(width), int(height), *(a.ctypes.data for a in out))
+    return tuple(out)
+
+
+def shadow_rows(matrices, world_sizes, map_indices=(0, 1, 2, 3)):
+    """One np[layouts.SHADOW_DATA] row from four column-major 16-float matrices, four world sizes and four map indices."""
+    row = np.zeros(1, L.SHADOW_DATA)
+    row["light_projection_matrices"][0] = np.asarray(matrices, np.float32).reshape(4, 16)
+    row["shadow_map_world_sizes"][0], row["shadow_map_indices"][0] = world_sizes, map_indices
+    return row
+
+
+def host_shadow_atlas(draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, matrices, resolution, **kw):
+    """The cascades' maps on the host: one host_raster_depth call per matrix (column-major 16 floats) with the clear, into
+    one (len(matrices), resolution, resolution) np.float32 atlas — what Engine.shadow_atlas leaves on the device."""
+    atlas = np.zeros((len(matrices), resolution, resolution), np.float32)
+    for k, m in enumerate(matrices):
+        atlas[k] = host_raster_depth(draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, m, resolution,
+                                     resolution, **kw)[0]
+    return atlas
+
+
+def shadow_atlas(engine, atlas, draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, entity_count, matrices,
+                 resolution, **kw):
+    """The cascades' maps on the device: one Engine.raster_depth call per matrix (column-major 16 floats) with the clear,
+    map k into atlas[k] of the (len(matrices), resolution, resolution) float32 device tensor `atlas` — the shadow_maps of
+    Engine.fragments_shade_shadowed, shadow_map_indices[c] = k.  No kernel of its own; kw: raster_depth's keywords."""
+    for k, m in enumerate(matrices):
+        engine.raster_depth(draw_commands, max_commands, meshlet_data, vertices, vertex_count, entity_data, entity_count, m, atlas[k],
+                            resolution, resolution, clear=True, **kw)
+    return atlas
 
 
 def host_shade_log2(x):
