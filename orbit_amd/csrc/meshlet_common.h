@@ -578,7 +578,11 @@ __device__ __forceinline__ float4 setup_load_mat(const MeshletCullParams &p, con
 // meshlets [meshlet_offset, meshlet_offset + 32) (kernels.h MeshletStreamView).
 __device__ __forceinline__ uint32_t setup_load_cls(const MeshletCullParams &p, const uint4 &rec, int lane) {
     const uint32_t col = lane & 3;
-    const uint32_t *plane = (col & 2u) ? p.ms.cls1 : p.ms.cls0;
+    // Both pointers are read into values first.  `(col & 2u) ? p.ms.cls1 : p.ms.cls0` selects between two lvalues of the
+    // by-reference kernel argument, that is between two ADDRESSES in the kernel-argument segment, and the pointer then
+    // comes through a per-lane vector load: in order behind every load in flight, so the wait for it drains them all.
+    const uint32_t *const plane0 = p.ms.cls0, *const plane1 = p.ms.cls1;
+    const uint32_t *plane = (col & 2u) ? plane1 : plane0;
     const uint32_t *src = (rec.z != 0u && p.ms.covers(rec.y)) ? plane + (rec.y >> 5) + (col & 1u)
                                                               : reinterpret_cast<const uint32_t *>(p.zero_page);
     return *src;

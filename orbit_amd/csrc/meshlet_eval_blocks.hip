@@ -337,34 +337,46 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
         uint32_t cls2;
         BoundRegs bnd2;
         uint4 rec3;
+        // The setup loads of the tile after the next: they depend only on rec2, which landed a tile ago.
+#define BK_SETUP_LOADS()                                                                                               \
+    mat2 = setup_load_mat(p, rec2, lane);                                                                              \
+    cls2 = setup_load_cls(p, rec2, lane);                                                                              \
+    bnd2 = blk_load_bound(p, blk, rec2);                                                                               \
+    rec3 = setup_load_rec(p, w3, w3 < ntiles, nrec, lane);
 #define BK_FLUSH() \
     while (rs.count >= kBkFlush) blk_flush(p, L, planes, ring, SR, lane, rs, kBkFlush);
         if (whole) {
-            // An all-sparse tile: its eight cone words are in q.  Everything the wave will wait for next goes out
-            // first — the next tile's loads and the setup loads of the tile after it — then the eight rows run from
-            // registers with no load between them.
+            // An all-sparse tile: its eight cone words are in q.  The setup loads go out FIRST: a wait the compiler attaches
+            // to their address arithmetic then covers nothing fresh, where behind the next tile's loads the same wait
+            // makes those land (vector loads return in order) — a full memory round trip at the top of every tile.  They
+            // are consumed behind the rows (setup_write_cls, setup_write, blk_setup below).  Then the next tile's loads,
+            // then the eight rows from registers with no load between them.  Each arm of `if (nxt_whole)` has its own
+            // straight-line copy of the rows: the compiler's vmcnt counts are per path, and behind a merge of an arm with
+            // eight loads in flight and one with four the first row would wait for the smaller count — half of the loads
+            // just issued.  In the steady arm (an all-sparse tile behind an all-sparse tile) nothing waits for them.
+#define BK_SPARSE_ROWS()                                                                                               \
+    blk_row_eval<0>(L, B, ring, lane, q.v[0], rs);                                                                     \
+    blk_row_eval<1>(L, B, ring, lane, q.v[1], rs);                                                                     \
+    BK_FLUSH()                                                                                                         \
+    blk_row_eval<2>(L, B, ring, lane, q.v[2], rs);                                                                     \
+    blk_row_eval<3>(L, B, ring, lane, q.v[3], rs);                                                                     \
+    BK_FLUSH()                                                                                                         \
+    blk_row_eval<4>(L, B, ring, lane, q.v[4], rs);                                                                     \
+    blk_row_eval<5>(L, B, ring, lane, q.v[5], rs);                                                                     \
+    blk_row_eval<6>(L, B, ring, lane, q.v[6], rs);                                                                     \
+    blk_row_eval<7>(L, B, ring, lane, q.v[7], rs);
+            BK_SETUP_LOADS()
             PipeRegs tn;
             if (nxt_whole) {
                 blk_tile_load(Ln, lane, tn.v, SR);
                 tn.v[8] = tn.v[9] = 0u;
+                BK_SPARSE_ROWS()
             } else {
                 blk_row_load<0>(p, Ln, row_is_sparse(Ln, 0), lane, tn.v, SR);
                 blk_row_load<1>(p, Ln, row_is_sparse(Ln, 1), lane, tn.v + 5, SR);
+                BK_SPARSE_ROWS()
             }
-            mat2 = setup_load_mat(p, rec2, lane);
-            cls2 = setup_load_cls(p, rec2, lane);
-            bnd2 = blk_load_bound(p, blk, rec2);
-            rec3 = setup_load_rec(p, w3, w3 < ntiles, nrec, lane);
-            blk_row_eval<0>(L, B, ring, lane, q.v[0], rs);
-            blk_row_eval<1>(L, B, ring, lane, q.v[1], rs);
-            BK_FLUSH()
-            blk_row_eval<2>(L, B, ring, lane, q.v[2], rs);
-            blk_row_eval<3>(L, B, ring, lane, q.v[3], rs);
-            BK_FLUSH()
-            blk_row_eval<4>(L, B, ring, lane, q.v[4], rs);
-            blk_row_eval<5>(L, B, ring, lane, q.v[5], rs);
-            blk_row_eval<6>(L, B, ring, lane, q.v[6], rs);
-            blk_row_eval<7>(L, B, ring, lane, q.v[7], rs);
+#undef BK_SPARSE_ROWS
             q = tn;
         } else {
             // A tile with a dense row: row by row, two in flight, as before.  The next tile's loads go out where the
@@ -382,10 +394,7 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
             BK_ROW(3, qb)
             blk_row_load<5>(p, L, row_is_sparse(L, 5), lane, qb, SR);
             BK_FLUSH()
-            mat2 = setup_load_mat(p, rec2, lane);
-            cls2 = setup_load_cls(p, rec2, lane);
-            bnd2 = blk_load_bound(p, blk, rec2);
-            rec3 = setup_load_rec(p, w3, w3 < ntiles, nrec, lane);
+            BK_SETUP_LOADS() // (where the row registers allow: behind this tile's own row loads, never behind the next tile's)
             BK_ROW(4, qa)
             blk_row_load<6>(p, L, row_is_sparse(L, 6), lane, qa, SR);
             BK_ROW(5, qb)
@@ -402,6 +411,7 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
 #undef BK_ROW
         }
 #undef BK_FLUSH
+#undef BK_SETUP_LOADS
         whole = nxt_whole;
         setup_write_cls(lds[wave][(it + 2) % 3], cls_sel, rec2, cls2, lane);
         setup_write(p, lds[wave][(it + 2) % 3], rec2, mat2, lane);
