@@ -284,6 +284,50 @@ pub struct OrbitFragmentsShadeShadowed {
     pub blocker_search_radius: f32, pub normal_bias_scale: f32, pub oriented_bias: f32, pub _pad: u32,
 }
 
+/// orbit_bloom_layout's result (88 B, HOST): max_levels is read (1..6, 0 = 6); level k is level_width[k] x level_height[k]
+/// packed texels starting at texel level_offset[k] of mips (bloom.rs:60-80: level 0 is the full size, at most six levels)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitBloomLayout {
+    pub max_levels: u32, pub levels: u32, pub total_texels: u32, pub _pad: u32,
+    pub level_width: [u32; 6], pub level_height: [u32; 6], pub level_offset: [u32; 6],
+}
+
+/// The counters of orbit_bloom (16 B, DEVICE, cleared by the call)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitBloomStats {
+    pub levels: u32, pub texels_written: u32, pub nonfinite_inputs: u32, pub clamped_texels: u32,
+}
+
+pub const ORBIT_BLOOM_FORCE_PER_LEVEL: u32 = 1;
+pub const ORBIT_BLOOM_FORCE_DIRECT: u32 = 4;
+pub const ORBIT_POST_BGRA: u32 = 1;
+
+/// orbit_bloom's argument block (56 B, HOST): the shade calls' colour plane (4 f32 per pixel, 16-B aligned), the packed
+/// B10G11R11 mip chain in OrbitBloomLayout's layout (total_texels u32), the optional counters, and BloomSettings'
+/// threshold, soft_threshold and filter_radius (bloom.rs:12-17); compute_bloom (bloom.rs:54-174) by rules B1-B9
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitBloom {
+    pub color: *const f32, pub mips: *mut u32, pub stats: *mut OrbitBloomStats,
+    pub width: u32, pub height: u32,
+    pub threshold: f32, pub soft_threshold: f32, pub filter_radius: f32,
+    pub max_levels: u32, pub flags: u32, pub _pad: u32,
+}
+
+/// The counters of orbit_post_process (16 B, DEVICE, cleared by the call)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitPostStats {
+    pub pixels: u32, pub nonfinite_pixels: u32, pub bloom_pixels: u32, pub _pad: u32,
+}
+
+/// orbit_post_process's argument block (64 B, HOST): colour, level 0 of the bloom chain (or null), the outputs ldr (4 f32
+/// per pixel) and rgba8 (4 bytes per pixel; at least one of the two), the optional counters, and the push constants of
+/// post_process.frag:47-56 that are served: exposure, bloom_intensity, render_mode (0 or 8); rules T1-T5
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitPostProcess {
+    pub color: *const f32, pub bloom: *const u32, pub ldr: *mut f32, pub rgba8: *mut u8, pub stats: *mut OrbitPostStats,
+    pub exposure: f32, pub bloom_intensity: f32, pub render_mode: u32, pub width: u32, pub height: u32, pub flags: u32,
+}
+
 /// orbit_visibility_resolve's argument block (48 B, HOST): DEVICE pointers; each output may be null, not all
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct OrbitVisibilityResolve {
@@ -510,6 +554,12 @@ extern "C" {
     pub fn orbit_fragments_shade(ctx: *mut OrbitCtx, job: *const OrbitFragmentsShade, stream: *mut c_void) -> i32;
     /// The same with forward.frag's cascaded PCSS shadow term on the shadowed directional lights (H1-H10).
     pub fn orbit_fragments_shade_shadowed(ctx: *mut OrbitCtx, job: *const OrbitFragmentsShadeShadowed, stream: *mut c_void) -> i32;
+    /// The shape of the bloom chain of a width x height target (host only; out.max_levels is read).
+    pub fn orbit_bloom_layout(width: u32, height: u32, out: *mut OrbitBloomLayout) -> i32;
+    /// compute_bloom of the colour plane the shade calls leave (B1-B9): afterwards level 0 of mips is the bloom image.
+    pub fn orbit_bloom(ctx: *mut OrbitCtx, job: *const OrbitBloom, stream: *mut c_void) -> i32;
+    /// post_process.frag of that plane and the bloom image (T1-T5): the ACES fit and the swapchain's sRGB bytes.
+    pub fn orbit_post_process(ctx: *mut OrbitCtx, job: *const OrbitPostProcess, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

@@ -1829,6 +1829,198 @@ ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeShadowed, oriented_bias) == 224,
 /* forward.frag's clustered lighting with cascaded PCSS shadows of every visible pixel; see above */
 int32_t orbit_fragments_shade_shadowed(OrbitCtx *ctx, const OrbitFragmentsShadeShadowed *job, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* orbit_bloom and orbit_post_process: from the shade calls' linear HDR     */
+/* `color` plane (4 floats per pixel) to the shown image, as the reference  */
+/* goes from its colour target to the swapchain: compute_bloom              */
+/* (src/passes/bloom.rs, shaders/bloom/bloom_downsample.comp,               */
+/* bloom_upsample.comp) and render_post_process (shaders/post_process.frag).*/
+/* ONE definition for the device and the host mirror (orbit_host_bloom,     */
+/* orbit_host_post_process; csrc/post_common.h); the two agree on every     */
+/* byte.  Arithmetic as in L: fp32, every operation rounded on its own,     */
+/* never contracted, IEEE '/', GLSL max / clamp.                            */
+/*  B1 the chain (bloom.rs:96-171).  levels = min(max(1, floor(log2(max(w,  */
+/*     h))) + 1), 6, max_levels); level k is max(w >> k, 1) x max(h >> k,   */
+/*     1) texels (level 0 is the full size, bloom.rs:60-80) and starts at   */
+/*     the texel count of the levels before it (orbit_bloom_layout).  Level */
+/*     0 is downsampled from color, level k from level k - 1; then level    */
+/*     k is upsampled into level k - 1 for k = levels - 1 .. 1.  With one   */
+/*     level there is no upsample.  Afterwards level 0 holds the bloom      */
+/*     image orbit_post_process reads.                                      */
+/*  B2 the threshold vector (bloom.rs:106-111), on the host, in float: knee */
+/*     = threshold * soft_threshold; tf = (threshold, threshold - knee, 2 * */
+/*     knee, 0.25 / (knee + 0.00001)).                                      */
+/*  B3 the sampler model of LinearClamp (image.rs:467, device.rs:1316-1320) */
+/*     at (u, v) of a src_w x src_h level: s = u * float(src_w) - 0.5f; i0  */
+/*     = floor(s), f = s - i0; i0 and i0 + 1 are clamped to [0, src_w - 1]  */
+/*     (saturating: +-inf clamp, NaN -> 0); v alike; per channel texel =    */
+/*     (t00 * (1 - fx) + t10 * fx) * (1 - fy) + (t01 * (1 - fx) + t11 * fx) */
+/*     * fy.  HARDWARE FILTERS WITH FIXED-POINT WEIGHTS: fp32 AS WRITTEN IS */
+/*     THIS PROJECT'S CANONICAL CHOICE, as the reduce-min sampler model is  */
+/*     for the pyramid.  Taps of level 0 do NOT collapse to one texel: (x + */
+/*     0.5 + d) * (1 / W) * W - 0.5 is not an integer in fp32 for most W,   */
+/*     so every tap is the full four-texel expression.                      */
+/*  B4 the downsample (bloom_downsample.comp:40-89).  uv = ((float(pixel) + */
+/*     0.5f) + d) * (1.0f / float(size)) with the DESTINATION size; the 13  */
+/*     taps x, y0..y3, z0..z7 and the five groups as the shader has them:   */
+/*     g0 = (y0 + y1 + y2 + y3) * 0.125, g1 = (z0 + z0 + z3 + x) * 0.03125  */
+/*     (:70 — the binary is the statement), g2 = (z1 + z2 + z4 + x) *       */
+/*     0.03125, g3 = (z3 + z5 + z6 + x) * 0.03125, g4 = (z4 + z6 + z7 + x)  */
+/*     * 0.03125; result = g0 + g1 + g2 + g3 + g4.  Sums run left to right, */
+/*     as the binary's output confirms (tests/golden/spirv_bloom.npz).      */
+/*  B5 level 0 only (:20-35, :75-87).  g_k = g_k * karis(g_k), karis(c) = 1 */
+/*     / (1 + ((s.r * 0.2126f + s.g * 0.7152f) + s.b * 0.0722f) * 0.25f), s */
+/*     = powc(c, 0.45454547f); powc(x, y) = exp2c(y * log2c(x)), 0 for x <= */
+/*     0; log2c is L2's; exp2c(x): k = floor(x + 0.5f), r = x - k, p = the  */
+/*     degree-7 Taylor polynomial of 2^r by Horner (c_n = ln(2)^n / n!      */
+/*     rounded to float), the result 2^k * p; x >= 128 -> +inf, x < -126 -> */
+/*     0.  Then prefilter: m = max(r, max(g, b)); soft = clamp(m - tf.y, 0, */
+/*     tf.z); soft = (soft * soft) * tf.w; result = result * (max(m - tf.x, */
+/*     soft) / max(m, 0.00001f)).  GLSL LEAVES pow's PRECISION TO THE       */
+/*     DRIVER: THIS ROUTINE IS THIS PROJECT'S CHOICE, as p5 in L6 and H6's  */
+/*     sine and cosine.  MEASURED: the largest relative error of powc(x, 1  */
+/*     / 2.2) against float64 over [2^-20, 65504] is 6.65e-7; 3.95 % of the */
+/*     packed texels of the hand-built cases differ from the GLSL in        */
+/*     float64 packed the same way.                       */
+/*  B6 the upsample (bloom_upsample.comp:19-44).  uv = float(pixel) * (1.0f */
+/*     / float(size)) + offset, WITHOUT the half pixel, as the shader has   */
+/*     it, with the destination's size; r = filter_radius in uv units; the  */
+/*     nine taps x (0, 0), y0 (r, 0), y1 (0, r), y2 (-r, 0), y3 (0, -r), z0 */
+/*     (r, r), z1 (-r, -r), z2 (-r, r), z3 (r, -r) of the source level by   */
+/*     B3; result = (x * 0.25 + (y0 + y1 + y2 + y3) * 0.125) + (z0 + z1 +   */
+/*     z2 + z3) * 0.0625; dst = pack(unpack(dst) + result).                 */
+/*  B7 the storage is B10G11R11_UFLOAT_PACK32: R in bits 0-10 and G in bits */
+/*     11-21 (5 + 6 bits each), B in bits 22-31 (5 + 5 bits), bias 15; the  */
+/*     smallest step is 2^-20 for R and G, 2^-19 for B.  Encode: x <= 0 ->  */
+/*     0; the rest is truncated toward zero; at or above the largest finite */
+/*     value (65024 for R and G, 64512 for B) -> that value, and            */
+/*     clamped_texels counts the texel.  Decode is exact.  TRUNCATION IS    */
+/*     THE DIRECT3D CONVERSION RULE, WHICH COLOUR BACK ENDS IMPLEMENT;      */
+/*     VULKAN LEAVES THE ROUNDING OPEN; NOBODY HAS MEASURED WHAT A DRIVER   */
+/*     UNDER THE REFERENCE DOES.  Every level is stored through this        */
+/*     encoding, between levels too, whatever the launch form.              */
+/*  B8 non-finite values.  A color component that is NaN or +-inf reads as  */
+/*     +0.0f in every tap; nonfinite_inputs counts such pixels (r, g or b)  */
+/*     once each, as the centre tap of level 0.  A component that is not    */
+/*     finite before encoding is stored as 0.  No non-finite bytes are ever */
+/*     written.                                                             */
+/*  B9 stats (may be NULL) is cleared by the call: levels; texels_written = */
+/*     every store, of the downsamples and of the upsamples;                */
+/*     nonfinite_inputs; clamped_texels over every store.  Every output     */
+/*     texel depends on its inputs only: independent of scheduling and of   */
+/*     the launch form.                                                     */
+/* Launch form: one launch per level, 2 * levels - 1 in all, behind one     */
+/* that clears the counters (ORBIT_BLOOM_FORCE_PER_LEVEL names it; it is    */
+/* the only form built and the default).  A workgroup stages the source     */
+/* texels its tile can touch in LDS, decoded, when they fit, and reads      */
+/* global memory otherwise (a large filter_radius); ORBIT_BLOOM_FORCE_DIRECT*/
+/* takes the second way everywhere: equal bytes.                            */
+/* OUT OF SCOPE: hdr_resolve.frag (no MSAA in a visibility buffer; its      */
+/* one-sample case writes vec4(1.0)); the skybox behind uncovered pixels    */
+/* (they show whatever color holds); SSAO, the sky light and textures;      */
+/* render mode 7 and the depth-pyramid overlay; the fixed-point weights of  */
+/* a hardware sampler.                                                      */
+/*   ORBIT_E_INVALID  (message prefix bloom:) color or mips NULL, color not */
+/*                    16-B or mips or stats not 4-B aligned; width or       */
+/*                    height 0 or above ORBIT_RASTER_MAX_DIM; max_levels 0  */
+/*                    or above 6; threshold, soft_threshold or              */
+/*                    filter_radius negative or not finite; unknown flags;  */
+/*                    mips equal to color.                                  */
+/* Kernel launches only: no allocation, no scratch, no host wait; a graph   */
+/* captures the call on a fresh context's first call.                       */
+/*                                                                          */
+/* orbit_post_process (post_process.frag) per pixel p:                      */
+/*  T1 hdr = color[p].rgb: the blit's texture(image, in_uv) at a 1 : 1      */
+/*     full-screen triangle is the texel itself; in_uv is the rasteriser's  */
+/*     to interpolate, so the rule is a fetch.  render_mode == 0 and bloom  */
+/*     != NULL: hdr += unpack(bloom[p]) * bloom_intensity (:59-64).         */
+/*  T2 render_mode 8 takes the same path without bloom: the shader's `if    */
+/*     (render_mode == 8)` assignment (:66) is overwritten by the else      */
+/*     branch below it (:78-82).  Any other render_mode is ORBIT_E_INVALID  */
+/*     (mode 7 and the depth-pyramid overlay are out of scope).             */
+/*  T3 mapped = aces_hill(hdr * exposure) (:8-34): the two mat3 x vec3      */
+/*     products column-major as R2's left-to-right rounded sums (m[0] * x + */
+/*     m[3] * y) + m[6] * z; the fit a / b as written; then clamped to [0,  */
+/*     1], NaN to 0.  ldr[p] = (mapped, 1.0f).                              */
+/*  T4 rgba8[p] is the sRGB encoding a B8G8R8A8_SRGB attachment applies: c  */
+/*     < 0.0031308f ? c * 12.92f : 1.055f * powc(c, 0.41666666f) - 0.055f;  */
+/*     the byte is uint8(c * 255.0f + 0.5f); alpha 255; bytes in R, G, B, A */
+/*     order, with ORBIT_POST_BGRA in the swapchain's B, G, R, A.  THE      */
+/*     CONVERSION'S LAST BIT IS THE IMPLEMENTATION'S IN VULKAN: THIS IS THE */
+/*     PROJECT'S CHOICE.  MEASURED: powc(x, 1 / 2.4) over [0.0031308, 1] is */
+/*     within 2.71e-7 of float64; 3.9e-6 of the hand-built cases' bytes     */
+/*     differ from the GLSL in float64, by 1.                               */
+/*  T5 a non-finite hdr component, as fetched or after the bloom term,      */
+/*     reads as +0.0f and the pixel counts in nonfinite_pixels.  stats (may */
+/*     be NULL) is cleared by the call: pixels, nonfinite_pixels,           */
+/*     bloom_pixels (pixels with a bloom term that is not 0).               */
+/*   ORBIT_E_INVALID  (message prefix post_process:) color NULL; ldr and    */
+/*                    rgba8 both NULL; color or ldr not 16-B, bloom, rgba8  */
+/*                    or stats not 4-B aligned; width or height 0 or above  */
+/*                    ORBIT_RASTER_MAX_DIM; render_mode not 0 or 8;         */
+/*                    exposure or bloom_intensity not finite; unknown       */
+/*                    flags; an output equal to an input or to the other.   */
+/* One launch behind a clearing one; capturable on the first call.          */
+/* ------------------------------------------------------------------------ */
+#define ORBIT_BLOOM_MAX_LEVELS 6u       /* bloom.rs:9 */
+#define ORBIT_BLOOM_FORCE_PER_LEVEL 1u  /* flags: one launch per level (the only form built) */
+#define ORBIT_BLOOM_FORCE_DIRECT 4u     /* flags: every tap reads global memory, no LDS staging */
+#define ORBIT_POST_BGRA 1u              /* flags: rgba8 in B, G, R, A order */
+typedef struct OrbitBloomLayout { /* HOST, 88 B */
+    uint32_t max_levels; /* IN: 1..6, 0 = 6 */
+    uint32_t levels, total_texels, _pad;
+    uint32_t level_width[ORBIT_BLOOM_MAX_LEVELS], level_height[ORBIT_BLOOM_MAX_LEVELS], level_offset[ORBIT_BLOOM_MAX_LEVELS]; /* 0 beyond levels */
+} OrbitBloomLayout;
+ORBIT_STATIC_ASSERT(sizeof(OrbitBloomLayout) == 88, "BloomLayout is 88 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitBloomLayout, level_width) == 16, "level_width @16");
+ORBIT_STATIC_ASSERT(offsetof(OrbitBloomLayout, level_offset) == 64, "level_offset @64");
+typedef struct OrbitBloomStats { /* DEVICE, 16 B, cleared by the call (B9) */
+    uint32_t levels, texels_written, nonfinite_inputs, clamped_texels;
+} OrbitBloomStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitBloomStats) == 16, "BloomStats is 16 B");
+typedef struct OrbitBloom { /* HOST block, 56 B; every pointer a DEVICE pointer */
+    const float *color;     /* width * height * 4 floats, 16-B aligned */
+    uint32_t *mips;         /* OrbitBloomLayout.total_texels words */
+    OrbitBloomStats *stats; /* NULL, or the counters */
+    uint32_t width, height;
+    float threshold, soft_threshold, filter_radius; /* BloomSettings, bloom.rs:12-17 */
+    uint32_t max_levels;                            /* 1..6 */
+    uint32_t flags, _pad;
+} OrbitBloom;
+ORBIT_STATIC_ASSERT(sizeof(OrbitBloom) == 56, "Bloom is 56 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitBloom, stats) == 16, "stats @16");
+ORBIT_STATIC_ASSERT(offsetof(OrbitBloom, width) == 24, "width @24");
+ORBIT_STATIC_ASSERT(offsetof(OrbitBloom, threshold) == 32, "threshold @32");
+ORBIT_STATIC_ASSERT(offsetof(OrbitBloom, max_levels) == 44, "max_levels @44");
+ORBIT_STATIC_ASSERT(offsetof(OrbitBloom, flags) == 48, "flags @48");
+typedef struct OrbitPostStats { /* DEVICE, 16 B, cleared by the call (T5) */
+    uint32_t pixels, nonfinite_pixels, bloom_pixels, _pad;
+} OrbitPostStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitPostStats) == 16, "PostStats is 16 B");
+typedef struct OrbitPostProcess { /* HOST block, 64 B; every pointer a DEVICE pointer */
+    const float *color;    /* width * height * 4 floats, 16-B aligned */
+    const uint32_t *bloom; /* NULL, or level 0 of orbit_bloom's mips */
+    float *ldr;            /* NULL, or 4 floats per pixel, 16-B aligned */
+    uint8_t *rgba8;        /* NULL, or 4 bytes per pixel, 4-B aligned */
+    OrbitPostStats *stats; /* NULL, or the counters */
+    float exposure, bloom_intensity;
+    uint32_t render_mode; /* 0 or 8 */
+    uint32_t width, height, flags;
+} OrbitPostProcess;
+ORBIT_STATIC_ASSERT(sizeof(OrbitPostProcess) == 64, "PostProcess is 64 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitPostProcess, stats) == 32, "stats @32");
+ORBIT_STATIC_ASSERT(offsetof(OrbitPostProcess, exposure) == 40, "exposure @40");
+ORBIT_STATIC_ASSERT(offsetof(OrbitPostProcess, render_mode) == 48, "render_mode @48");
+ORBIT_STATIC_ASSERT(offsetof(OrbitPostProcess, flags) == 60, "flags @60");
+
+/* B1's shape of a width x height target (host only; out->max_levels is read: 1..6, 0 = 6).  ORBIT_E_INVALID for a NULL
+ * out, width or height 0 or above ORBIT_RASTER_MAX_DIM, max_levels above 6. */
+int32_t orbit_bloom_layout(uint32_t width, uint32_t height, OrbitBloomLayout *out);
+/* the reference's bloom chain of a colour plane into packed mips; see above */
+int32_t orbit_bloom(OrbitCtx *ctx, const OrbitBloom *job, void *stream);
+/* the reference's tone mapping and sRGB encoding of a colour plane; see above */
+int32_t orbit_post_process(OrbitCtx *ctx, const OrbitPostProcess *job, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,44 @@ def fill_shadow_fields(j, shadow_count, shadow_index_base, shadow_map_count, sha
     j.blocker_search_radius, j.normal_bias_scale, j.oriented_bias = float(blocker_search_radius), float(normal_bias_scale), float(oriented_bias)
 
 
+BLOOM_MAX_LEVELS = 6                                # ORBIT_BLOOM_MAX_LEVELS
+BLOOM_FORCE_PER_LEVEL, BLOOM_FORCE_DIRECT = 1, 4    # ORBIT_BLOOM_FORCE_PER_LEVEL, ORBIT_BLOOM_FORCE_DIRECT (2 is no flag)
+POST_BGRA = 1                                       # ORBIT_POST_BGRA
+
+
+class BloomLayout(C.Structure):  # OrbitBloomLayout (88 B)
+    _fields_ = [("max_levels", C.c_uint32), ("levels", C.c_uint32), ("total_texels", C.c_uint32), ("_pad", C.c_uint32),
+                ("level_width", C.c_uint32 * BLOOM_MAX_LEVELS), ("level_height", C.c_uint32 * BLOOM_MAX_LEVELS),
+                ("level_offset", C.c_uint32 * BLOOM_MAX_LEVELS)]
+
+
+class Bloom(C.Structure):  # OrbitBloom (56 B)
+    _fields_ = [("color", C.c_void_p), ("mips", C.c_void_p), ("stats", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("threshold", C.c_float), ("soft_threshold", C.c_float), ("filter_radius", C.c_float), ("max_levels", C.c_uint32),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class PostProcess(C.Structure):  # OrbitPostProcess (64 B)
+    _fields_ = [("color", C.c_void_p), ("bloom", C.c_void_p), ("ldr", C.c_void_p), ("rgba8", C.c_void_p), ("stats", C.c_void_p),
+                ("exposure", C.c_float), ("bloom_intensity", C.c_float), ("render_mode", C.c_uint32), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def fill_bloom(j, width, height, threshold, soft_threshold, filter_radius, max_levels, form):
+    """The by-value fields of an OrbitBloom; form: None (the library chooses), "per_level", "direct" or raw flag bits."""
+    j.width, j.height, j.max_levels = int(width), int(height), int(max_levels)
+    j.threshold, j.soft_threshold, j.filter_radius = float(threshold), float(soft_threshold), float(filter_radius)
+    forms = {None: 0, "per_level": BLOOM_FORCE_PER_LEVEL, "direct": BLOOM_FORCE_DIRECT}
+    j.flags = form if isinstance(form, int) else forms[form]
+
+
+def fill_post_process(j, width, height, exposure, bloom_intensity, render_mode, bgra):
+    """The by-value fields of an OrbitPostProcess; bgra: True, False or raw flag bits."""
+    j.width, j.height, j.render_mode = int(width), int(height), int(render_mode)
+    j.exposure, j.bloom_intensity = float(exposure), float(bloom_intensity)
+    j.flags = POST_BGRA if bgra is True else int(bgra)
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -308,6 +346,9 @@ SYMBOLS = {
     "orbit_surface_fragments": (C.c_int32, [C.c_void_p, C.POINTER(SurfaceFragments), C.c_void_p]),
     "orbit_fragments_shade": (C.c_int32, [C.c_void_p, C.POINTER(FragmentsShade), C.c_void_p]),
     "orbit_fragments_shade_shadowed": (C.c_int32, [C.c_void_p, C.POINTER(FragmentsShadeShadowed), C.c_void_p]),
+    "orbit_bloom_layout": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(BloomLayout)]),
+    "orbit_bloom": (C.c_int32, [C.c_void_p, C.POINTER(Bloom), C.c_void_p]),
+    "orbit_post_process": (C.c_int32, [C.c_void_p, C.POINTER(PostProcess), C.c_void_p]),
 }
 
 _lib = None

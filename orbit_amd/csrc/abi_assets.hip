@@ -7,8 +7,10 @@
 // orbit_visibility_surface_drawn, the same for a buffer drawn with the raster flags (visibility_surface_drawn.hip), and
 // orbit_surface_fragments, the fragment shader's inputs per pixel from those and the vertex attributes
 // (surface_fragments.hip), and orbit_fragments_shade, the clustered lighting of those pixels (fragments_shade.hip), with
-// orbit_fragments_shade_shadowed, the same with cascaded shadows served (fragments_shade_shadowed.hip).
+// orbit_fragments_shade_shadowed, the same with cascaded shadows served (fragments_shade_shadowed.hip), and what follows
+// the colour plane they leave: orbit_bloom with orbit_bloom_layout and orbit_post_process (bloom.hip).
 #include "abi_internal.h"
+#include "post_common.h" // bloom_layout
 
 namespace {
 
@@ -373,6 +375,69 @@ int32_t orbit_fragments_shade_shadowed(OrbitCtx *ctx, const OrbitFragmentsShadeS
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_fragments_shade_shadowed(j, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch fragments_shade_shadowed");
+    return ORBIT_OK;
+}
+
+// B1's shape: host only, no context
+int32_t orbit_bloom_layout(uint32_t width, uint32_t height, OrbitBloomLayout *out) {
+    if (!out) return fail(nullptr, ORBIT_E_INVALID, "bloom_layout: out is NULL");
+    if (width == 0 || height == 0 || width > ORBIT_RASTER_MAX_DIM || height > ORBIT_RASTER_MAX_DIM)
+        return fail(nullptr, ORBIT_E_INVALID, "bloom_layout: target %u x %u (1..%u each)", width, height, ORBIT_RASTER_MAX_DIM);
+    if (out->max_levels > ORBIT_BLOOM_MAX_LEVELS) return fail(nullptr, ORBIT_E_INVALID, "bloom_layout: max_levels %u (1..%u, 0 = %u)", out->max_levels, ORBIT_BLOOM_MAX_LEVELS, ORBIT_BLOOM_MAX_LEVELS);
+    orbit::raster::bloom_layout(width, height, out->max_levels ? out->max_levels : ORBIT_BLOOM_MAX_LEVELS, *out);
+    return ORBIT_OK;
+}
+
+// One launch that starts the counters and one per level of the chain (bloom.hip).  No allocation, no scratch, no host
+// sync: capturable on the first call.  As its siblings, the job is checked before the context is looked at.
+int32_t orbit_bloom(OrbitCtx *ctx, const OrbitBloom *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "bloom: job is NULL");
+    const OrbitBloom &j = *job;
+    if (j.flags & ~(ORBIT_BLOOM_FORCE_PER_LEVEL | ORBIT_BLOOM_FORCE_DIRECT)) return fail(ctx, ORBIT_E_INVALID, "bloom: flags %#x", j.flags);
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "bloom: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if (j.max_levels == 0 || j.max_levels > ORBIT_BLOOM_MAX_LEVELS) return fail(ctx, ORBIT_E_INVALID, "bloom: max_levels %u (1..%u)", j.max_levels, ORBIT_BLOOM_MAX_LEVELS);
+    for (const float v : {j.threshold, j.soft_threshold, j.filter_radius})
+        if (!(v >= 0.0f && v < INFINITY))
+            return fail(ctx, ORBIT_E_INVALID, "bloom: threshold %g, soft_threshold %g, filter_radius %g (finite, not negative)", j.threshold, j.soft_threshold, j.filter_radius);
+    if (!j.color || !j.mips) return fail(ctx, ORBIT_E_INVALID, "bloom: NULL buffer");
+    if (((uintptr_t)j.color & 15u) || (((uintptr_t)j.mips | (uintptr_t)j.stats) & 3u))
+        return fail(ctx, ORBIT_E_INVALID, "bloom: color must be 16-B aligned, mips and stats 4-B aligned");
+    if ((const void *)j.mips == (const void *)j.color || (j.stats && ((const void *)j.stats == (const void *)j.color || (const void *)j.stats == (const void *)j.mips)))
+        return fail(ctx, ORBIT_E_INVALID, "bloom: an output is an input or the other output (%p)", (const void *)j.mips);
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "bloom: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_bloom(j, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch bloom");
+    return ORBIT_OK;
+}
+
+// A launch that starts the counters and one pass over the pixels (bloom.hip); as orbit_bloom otherwise.
+int32_t orbit_post_process(OrbitCtx *ctx, const OrbitPostProcess *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "post_process: job is NULL");
+    const OrbitPostProcess &j = *job;
+    if (j.flags & ~ORBIT_POST_BGRA) return fail(ctx, ORBIT_E_INVALID, "post_process: flags %#x", j.flags);
+    if (j.render_mode != 0u && j.render_mode != 8u) return fail(ctx, ORBIT_E_INVALID, "post_process: render_mode %u (0 or 8)", j.render_mode);
+    if (j.width == 0 || j.height == 0 || j.width > ORBIT_RASTER_MAX_DIM || j.height > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "post_process: target %u x %u (1..%u each)", j.width, j.height, ORBIT_RASTER_MAX_DIM);
+    if (!(fabsf(j.exposure) < INFINITY) || !(fabsf(j.bloom_intensity) < INFINITY))
+        return fail(ctx, ORBIT_E_INVALID, "post_process: exposure %g, bloom_intensity %g (finite)", j.exposure, j.bloom_intensity);
+    if (!j.color) return fail(ctx, ORBIT_E_INVALID, "post_process: color is NULL");
+    if (!j.ldr && !j.rgba8) return fail(ctx, ORBIT_E_INVALID, "post_process: ldr and rgba8 are both NULL");
+    if ((((uintptr_t)j.color | (uintptr_t)j.ldr) & 15u) || (((uintptr_t)j.bloom | (uintptr_t)j.rgba8 | (uintptr_t)j.stats) & 3u))
+        return fail(ctx, ORBIT_E_INVALID, "post_process: color and ldr must be 16-B aligned, bloom, rgba8 and stats 4-B aligned");
+    const void *const inputs[2] = {j.color, j.bloom};
+    const void *const outputs[3] = {j.ldr, j.rgba8, j.stats};
+    for (int a = 0; a < 3; a++) {
+        for (const void *in : inputs)
+            if (outputs[a] && outputs[a] == in) return fail(ctx, ORBIT_E_INVALID, "post_process: an output is an input (%p)", in);
+        for (int b = a + 1; b < 3; b++)
+            if (outputs[a] && outputs[a] == outputs[b]) return fail(ctx, ORBIT_E_INVALID, "post_process: two outputs are one buffer (%p)", outputs[a]);
+    }
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "post_process: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_post_process(j, ctx->num_cus, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch post_process");
     return ORBIT_OK;
 }
 

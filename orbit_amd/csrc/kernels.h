@@ -460,6 +460,12 @@ hipError_t launch_fragments_shade(const OrbitFragmentsShade &job, uint32_t num_c
 // form the same rule chooses, evaluates cascade selection, blocker search and filter per lane
 hipError_t launch_fragments_shade_shadowed(const OrbitFragmentsShadeShadowed &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
                                            hipStream_t s);
+// bloom.hip: orbit_bloom — `job` validated by the entry point.  One launch starts the counters, then one launch per level
+// of the chain (2 * levels - 1), a workgroup per 16 x 16 destination tile staging its source box in LDS when it fits
+hipError_t launch_bloom(const OrbitBloom &job, hipStream_t s);
+// bloom.hip: orbit_post_process — `job` validated by the entry point.  One launch starts the counters, the next makes one
+// pass over the pixels, a thread per pixel
+hipError_t launch_post_process(const OrbitPostProcess &job, uint32_t num_cus, hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

@@ -557,6 +557,34 @@ class Engine:
                                 normal_bias_scale, oriented_bias)
         _lib.check(self._lib.orbit_fragments_shade_shadowed(self._ctx, C.byref(js), _stream(stream)), self._ctx)
 
+    # -- the reference's bloom chain of a colour plane (orbit_bloom)
+    def bloom(self, color, width, height, mips, threshold=0.0, soft_threshold=0.0, filter_radius=0.003, max_levels=6,
+              stats=None, form=None, stream=None):
+        """From `color` (4 floats per pixel, as the shade calls leave it) to `mips`: one packed B10G11R11 u32 per texel of
+        the reference's bloom chain in orbit_amd.post.bloom_layout's layout (level 0 first, full size) — the 13-tap
+        downsample with the Karis average and the soft threshold on level 0, then the 3 x 3 tent upsample, each level added
+        into the one above.  Afterwards level 0 is the image post_process reads.  threshold, soft_threshold,
+        filter_radius: the reference's BloomSettings (these are its defaults).  stats (16 bytes, layouts.BLOOM_STATS,
+        cleared by the call) may be None.  form: None, "per_level" (the only launch form built, and the default) or
+        "direct" (no LDS staging): equal bytes.  Byte-equal to orbit_amd.post.host_bloom.  Enqueued on `stream`."""
+        j = _lib.Bloom()
+        j.color, j.mips, j.stats = _ptr(color), _ptr(mips), _ptr(stats)
+        _lib.fill_bloom(j, width, height, threshold, soft_threshold, filter_radius, max_levels, form)
+        _lib.check(self._lib.orbit_bloom(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
+    # -- the reference's tone mapping and sRGB encoding of a colour plane (orbit_post_process)
+    def post_process(self, color, width, height, bloom=None, ldr=None, rgba8=None, exposure=1.0, bloom_intensity=0.025,
+                     render_mode=0, bgra=False, stats=None, stream=None):
+        """From `color` (4 floats per pixel) and, with render_mode 0, `bloom` (None, or level 0 of bloom's mips) to `ldr`
+        (4 floats per pixel: the ACES fit of (color + bloom * bloom_intensity) * exposure, clamped, alpha 1) and / or
+        `rgba8` (4 bytes per pixel: its sRGB encoding, R, G, B, A, or B, G, R, A with bgra=True); at least one of the
+        two.  render_mode 8 ignores bloom.  stats (16 bytes, layouts.POST_STATS, cleared by the call) may be None.
+        Byte-equal to orbit_amd.post.host_post_process.  Enqueued on `stream`."""
+        j = _lib.PostProcess()
+        j.color, j.bloom, j.ldr, j.rgba8, j.stats = _ptr(color), _ptr(bloom), _ptr(ldr), _ptr(rgba8), _ptr(stats)
+        _lib.fill_post_process(j, width, height, exposure, bloom_intensity, render_mode, bgra)
+        _lib.check(self._lib.orbit_post_process(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                    entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,

@@ -10,6 +10,7 @@
 #include "orbit_assets.hpp"
 #include "orbit_gltf.hpp"
 #include "orbit_raster.hpp"
+#include "orbit_post.hpp"
 #include "orbit_scene.hpp"
 #include "../csrc/block_pretest.h"
 #include "../csrc/shade_common.h"
@@ -640,6 +641,33 @@ int32_t orbit_host_fragments_shade_shadowed(const OrbitFragmentsShadeShadowed *j
         raster::fragments_shade_shadowed(*job, status);
     });
 }
+
+int32_t orbit_host_bloom(const OrbitBloom *job) {
+    return guarded([&] {
+        if (!job) throw Panic("bloom: job is NULL");
+        raster::bloom(*job);
+    });
+}
+
+int32_t orbit_host_post_process(const OrbitPostProcess *job) {
+    return guarded([&] {
+        if (!job) throw Panic("post_process: job is NULL");
+        raster::post_process(*job);
+    });
+}
+
+// the pieces of csrc/post_common.h, for tests
+void orbit_host_bloom_downsample_floats(const float *src, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, uint32_t level0,
+                                        const float *threshold_filter, float *dst) {
+    raster::bloom_downsample_floats(src, src_w, src_h, dst_w, dst_h, level0 != 0u, threshold_filter, dst);
+}
+void orbit_host_bloom_upsample_floats(const float *src, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, float filter_radius,
+                                      float *dst) {
+    raster::bloom_upsample_floats(src, src_w, src_h, dst_w, dst_h, filter_radius, dst);
+}
+void orbit_host_bloom_pack(const float *rgb, uint64_t n, uint32_t *words, uint8_t *clamped) { raster::bloom_pack_texels(rgb, n, words, clamped); }
+void orbit_host_bloom_unpack(const uint32_t *words, uint64_t n, float *rgb) { raster::bloom_unpack_texels(words, n, rgb); }
+void orbit_host_powc(const float *x, uint64_t n, float y, float *out) { raster::powc_array(x, n, y, out); }
 
 void orbit_host_shadow_rotation(uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float *theta, float *sine, float *cosine) {
     raster::shadow_rotation(x0, y0, width, height, theta, sine, cosine);

@@ -267,6 +267,21 @@ int32_t orbit_host_fragments_shade(const OrbitFragmentsShade *job, int32_t *stat
 /* the reference of orbit_fragments_shade_shadowed (H1-H10): the device call's block with HOST pointers in it, as
  * orbit_host_fragments_shade; shadow_factor, cascade and shadow_stats hold the device's bytes too. */
 int32_t orbit_host_fragments_shade_shadowed(const OrbitFragmentsShadeShadowed *job, int32_t *status);
+/* the reference of orbit_bloom (B1-B9): the device call's block with HOST pointers in it; mips and stats hold the
+ * device's bytes.  ORBIT_HOST_PANIC for what the device answers with ORBIT_E_INVALID. */
+int32_t orbit_host_bloom(const OrbitBloom *job);
+/* the reference of orbit_post_process (T1-T5): as above; ldr, rgba8 and stats hold the device's bytes. */
+int32_t orbit_host_post_process(const OrbitPostProcess *job);
+/* tests: one downsample (B3-B5) / one upsample's added term (B6) on three floats per texel, nothing packed;
+ * threshold_filter: B2's four floats (read with level0 != 0) */
+void orbit_host_bloom_downsample_floats(const float *src, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, uint32_t level0,
+                                        const float *threshold_filter, float *dst);
+void orbit_host_bloom_upsample_floats(const float *src, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, float filter_radius,
+                                      float *dst);
+/* tests: B7 of n texels (clamped may be NULL: 1 per texel that counts in clamped_texels), and powc of B5 / T4 */
+void orbit_host_bloom_pack(const float *rgb, uint64_t n, uint32_t *words, uint8_t *clamped);
+void orbit_host_bloom_unpack(const uint32_t *words, uint64_t n, float *rgb);
+void orbit_host_powc(const float *x, uint64_t n, float y, float *out);
 /* tests: H6 of the pixels (x0 + x, y0 + y), x < width, y < height, row-major into three arrays of width * height floats:
  * theta and csrc/shadow_common.h's sine and cosine of it */
 void orbit_host_shadow_rotation(uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float *theta, float *sine, float *cosine);

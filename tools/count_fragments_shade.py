@@ -74,8 +74,8 @@ def surface_lights(world_pos, visibility, n=N_LIGHTS, seed=3, spread=1.0, intens
     return l
 
 
-def host_frame(oracle):
-    """The whole frame on the host -> dict: scene, rows, frame (visibility, draw1, draw2, view_proj, cam), planes (the
+def host_frame(oracle, width=None, height=None):
+    """The whole frame on the host (width x height: tools/count_surface_fragments.py's 320 x 180 by default) -> dict: scene, rows, frame (visibility, draw1, draw2, view_proj, cam), planes (the
     fragments call's outputs), depth, lights, push, info, cluster_count, z_scale, z_bias, index_buffer, image, view_pos,
     index_capacity, and `args`: the positional arguments of raster.host_fragments_shade"""
     import raster_scene as rs
@@ -85,7 +85,7 @@ def host_frame(oracle):
     outside = frag._tool("count_visible_surface")
     scene = rs.glb_scene(frag.INSTANCES)
     rows = frag.scene_rows(scene)
-    w, h = frag.WIDTH, frag.HEIGHT
+    w, h = width or frag.WIDTH, height or frag.HEIGHT
     frame = frag._tool("count_surface_drawn").flagged_frames(scene, oracle, [rs.camera(w, h, p) for p in outside.CAMERAS], w, h)[1]
     planes, total = frag.fragments_of(frag.frame_cases(scene, rows, frame))
     assert total["stale_pixels"] == total["unshaded_pixels"] == 0

@@ -63,14 +63,14 @@ def cascades_of(cam, q, resolution, position, aspect):
             for k in range(4)]
 
 
-def host_frame(oracle, resolution=RESOLUTION, shadow_index_base=2048):
+def host_frame(oracle, resolution=RESOLUTION, shadow_index_base=2048, width=None, height=None):
     """tools/count_fragments_shade.py's frame with one sun, its cascades and their maps -> that dict with lights, image,
     index_buffer, index_capacity and info replaced, and casters (every opaque meshlet's command), cascades, shadow_rows, atlas,
     settings, shadow_index_base, `args` / `kw`: the arguments of raster.host_fragments_shade_shadowed"""
     from orbit_amd import raster
 
     base = _tool("count_fragments_shade")
-    f = base.host_frame(oracle)
+    f = base.host_frame(oracle, width, height)
     scene, cam, cc = f["scene"], f["frame"]["cam"], f["cluster_count"]
     q = np.asarray(SUN_Q, np.float64)
     q = tuple(float(v) for v in q / np.linalg.norm(q))

@@ -1,0 +1,116 @@
+"""A frame of the glTF test scene as a picture: tools/count_fragments_shade_shadowed.py's frame (100
+instances, 320 x 180, 200 point lights and a sun with four 256^2 cascades) shaded, bloomed and tone-mapped — shade -> bloom
+-> post process -> a binary PPM.
+  on the CPU (default)  through the host mirrors (orbit_host_fragments_shade_shadowed, orbit_host_bloom,
+                        orbit_host_post_process); prints the counters and writes --out, which also keeps the accuracy figures
+                        tests/test_post_chain_cpu.py holds (powc against float64, the share of packed texels and rgba8
+                        bytes that differ from the GLSL in float64)
+  --device              the three calls on the GPU from the same planes, compared byte for byte with the mirrors' picture;
+                        exit code 1 if a byte differs.  Writes the device's picture; --out is not touched.
+Uncovered pixels show what the colour plane holds there (0: black); the skybox is out of scope.
+Usage: python tools/render_frame.py [--device] [--picture frame.ppm] [--exposure 4.0] [--out profiles/post_chain_cpu.json]
+"""
+import argparse
+import importlib.util
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+
+def _tool(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def host_picture(f, exposure):
+    """the frame through the three mirrors -> (shaded, bloom, post process) dicts"""
+    from orbit_amd import post, raster
+
+    shaded = raster.host_fragments_shade_shadowed(*f["args"], **f["kw"])
+    bloom = post.host_bloom(shaded["color"], **{k: post.DEFAULTS[k] for k in ("threshold", "soft_threshold", "filter_radius")})
+    out = post.host_post_process(shaded["color"], bloom["mips"], exposure=exposure, bloom_intensity=post.DEFAULTS["bloom_intensity"])
+    return shaded, bloom, out
+
+
+def device_picture(f, tool, exposure):
+    """the same three calls on the GPU -> (color, mips, ldr, rgba8, bloom stats, post stats) as host arrays"""
+    import torch
+
+    from orbit_amd import post
+    from orbit_amd.engine import Engine
+
+    base = tool._tool("count_fragments_shade")
+    w, h, cc, s = f["width"], f["height"], f["cluster_count"], f["settings"]
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).cuda()  # noqa: E731
+    vis, wp, nrm, mat, mats, lights, image, index_buffer = f["args"][:8]
+    d = [up(x) for x in (vis, wp, nrm, mat, mats, lights, image, index_buffer, f["shadow_rows"], f["atlas"])]
+    lay = post.bloom_layout(w, h)
+    color, ldr = (torch.zeros(4 * w * h, dtype=torch.float32, device="cuda") for _ in range(2))
+    mips = torch.zeros(lay["total_texels"], dtype=torch.int32, device="cuda")
+    rgba8 = torch.zeros(4 * w * h, dtype=torch.uint8, device="cuda")
+    bstats, pstats = (torch.zeros(4, dtype=torch.int32, device="cuda") for _ in range(2))
+    eng = Engine(0, max_entities=1024, max_dispatches=1024, max_draws=1024)
+    eng.fragments_shade_shadowed(d[0], w, h, d[1], d[2], d[3], d[4], len(mats), d[5], len(lights), d[6], d[7], f["index_capacity"], cc, base.TILE,
+                                 f["z_scale"], f["z_bias"], base.CUTOFF, f["frame"]["cam"].z_near, f["view_pos"], color, d[8], 1, d[9], 4,
+                                 f["atlas"].shape[-1], s["blocker_search_radius"], s["normal_bias_scale"], s["oriented_bias"],
+                                 shadow_index_base=f["shadow_index_base"], clear=True)
+    eng.bloom(color, w, h, mips, stats=bstats, **{k: post.DEFAULTS[k] for k in ("threshold", "soft_threshold", "filter_radius")})
+    eng.post_process(color, w, h, bloom=mips, ldr=ldr, rgba8=rgba8, stats=pstats, exposure=exposure, bloom_intensity=post.DEFAULTS["bloom_intensity"])
+    torch.cuda.synchronize()
+    eng.status()
+    out = [t.cpu().numpy() for t in (color, mips, ldr, rgba8, bstats, pstats)]
+    eng.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--device", action="store_true")
+    ap.add_argument("--picture", default="frame.ppm")
+    ap.add_argument("--exposure", type=float, default=4.0)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "post_chain_cpu.json"))
+    args = ap.parse_args()
+    from oracle import oracle
+    from orbit_amd import post
+    from orbit_amd import layouts as L
+
+    oracle.build()
+    tool = _tool("count_fragments_shade_shadowed")
+    f = tool.host_frame(oracle)
+    w, h = f["width"], f["height"]
+    shaded, bloom, out = host_picture(f, args.exposure)
+    if args.device:
+        color, mips, ldr, rgba8, bstats, pstats = device_picture(f, tool, args.exposure)
+        equal = dict(color=color.tobytes() == shaded["color"].tobytes(), mips=mips.tobytes() == bloom["mips"].tobytes(),
+                     ldr=ldr.tobytes() == out["ldr"].tobytes(), rgba8=rgba8.tobytes() == out["rgba8"].tobytes(),
+                     bloom_stats=bstats.tobytes() == bloom["stats"].tobytes(), post_stats=pstats.tobytes() == out["stats"].tobytes())
+        post.write_ppm(args.picture, rgba8.reshape(h, w, 4))
+        print(json.dumps(dict(width=w, height=h, picture=os.path.basename(args.picture), device_equals_host=equal)))
+        return 0 if all(equal.values()) else 1
+    import test_post_chain_cpu as held  # the figures the CPU tests hold, measured the same way
+
+    post.write_ppm(args.picture, out["rgba8"])
+    rgb = out["rgba8"][..., :3]
+    line = {"scene": "tools/make_test_glb.py, 100 instances, seed 7; 200 point lights and a sun with four 256^2 cascades", "width": w, "height": h,
+            "exposure": args.exposure, **post.DEFAULTS, "picture": os.path.basename(args.picture),
+            **{k: int(shaded["stats"][k]) for k in ("covered_pixels", "written_pixels")}, **{k: int(bloom["stats"][k]) for k in L.BLOOM_STATS.names},
+            **{k: int(out["stats"][k]) for k in ("pixels", "nonfinite_pixels", "bloom_pixels")},
+            "distinct_rgb_values": int(len(np.unique(rgb.reshape(-1, 3), axis=0))), "mean_byte": round(float(rgb.mean()), 2),
+            **held.measure_powc(), **held.measure_shares(),
+            "against": "the GLSL in float64 with a true pow, levels stored through B7 (tests/post_chain_ref.py), over tests/post_chain_cases.py"}
+    text = json.dumps(line)
+    print(text)
+    with open(args.out, "w") as fh:
+        fh.write(text + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
