@@ -328,6 +328,27 @@ pub struct OrbitPostProcess {
     pub exposure: f32, pub bloom_intensity: f32, pub render_mode: u32, pub width: u32, pub height: u32, pub flags: u32,
 }
 
+/// The counters of orbit_ssao (24 B, DEVICE, 8-B aligned, cleared by the call)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitSsaoStats {
+    pub pixels: u32, pub nonfinite_pixels: u32, pub unoccluded_pixels: u32, pub _pad: u32,
+    pub samples_in_range: u64,
+}
+
+/// orbit_ssao's argument block (224 B, HOST): the depth plane (f32, reverse-z), SsaoRenderer's noise (R8G8_SNORM) and
+/// samples (R8G8B8A8_UNORM) textures as bytes, the outputs raw and blurred (R8, ssao_w x ssao_h; ssao.rs:99-127) and
+/// ao_pixel (f32 per screen pixel: forward.frag:336-337's sample), the optional counters, and GpuSSAOInfo's matrices,
+/// sizes and settings (ssao.rs:50-67); rules A1-A9
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitSsao {
+    pub depth: *const f32, pub noise: *const i8, pub samples: *const u8,
+    pub raw: *mut u8, pub blurred: *mut u8, pub ao_pixel: *mut f32, pub stats: *mut OrbitSsaoStats,
+    pub projection: [f32; 16], pub inverse_projection: [f32; 16],
+    pub screen_w: u32, pub screen_h: u32, pub ssao_w: u32, pub ssao_h: u32,
+    pub noise_size: u32, pub samples_size: u32, pub sample_count: u32,
+    pub min_radius: f32, pub max_radius: f32, pub flags: u32,
+}
+
 /// orbit_visibility_resolve's argument block (48 B, HOST): DEVICE pointers; each output may be null, not all
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct OrbitVisibilityResolve {
@@ -560,6 +581,8 @@ extern "C" {
     pub fn orbit_bloom(ctx: *mut OrbitCtx, job: *const OrbitBloom, stream: *mut c_void) -> i32;
     /// post_process.frag of that plane and the bloom image (T1-T5): the ACES fit and the swapchain's sRGB bytes.
     pub fn orbit_post_process(ctx: *mut OrbitCtx, job: *const OrbitPostProcess, stream: *mut c_void) -> i32;
+    /// compute_ssao of the depth plane (A1-A9): raw, its blur, and what forward.frag reads of the blur per pixel.
+    pub fn orbit_ssao(ctx: *mut OrbitCtx, job: *const OrbitSsao, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

@@ -1917,7 +1917,7 @@ int32_t orbit_fragments_shade_shadowed(OrbitCtx *ctx, const OrbitFragmentsShadeS
 /* takes the second way everywhere: equal bytes.                            */
 /* OUT OF SCOPE: hdr_resolve.frag (no MSAA in a visibility buffer; its      */
 /* one-sample case writes vec4(1.0)); the skybox behind uncovered pixels    */
-/* (they show whatever color holds); SSAO, the sky light and textures;      */
+/* (they show whatever color holds); the sky light and textures;            */
 /* render mode 7 and the depth-pyramid overlay; the fixed-point weights of  */
 /* a hardware sampler.                                                      */
 /*   ORBIT_E_INVALID  (message prefix bloom:) color or mips NULL, color not */
@@ -2020,6 +2020,152 @@ int32_t orbit_bloom_layout(uint32_t width, uint32_t height, OrbitBloomLayout *ou
 int32_t orbit_bloom(OrbitCtx *ctx, const OrbitBloom *job, void *stream);
 /* the reference's tone mapping and sRGB encoding of a colour plane; see above */
 int32_t orbit_post_process(OrbitCtx *ctx, const OrbitPostProcess *job, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* orbit_ssao: the reference's screen-space ambient occlusion between its   */
+/* depth prepass and its forward pass (app.rs:1151-1169;                    */
+/* src/passes/ssao.rs, shaders/ssao/ssao.comp, shaders/ssao/ssao_blur.comp) */
+/* and what forward.frag:335-338 reads of it per pixel.  It reads the depth */
+/* plane orbit_raster_depth / orbit_visibility_resolve leave (floats,       */
+/* reverse-z, 0 = uncovered) and the caller's two small tables.  ONE        */
+/* definition for the device and the host mirror (orbit_host_ssao;          */
+/* csrc/ssao_common.h); the two agree on every byte.  Arithmetic as in L /  */
+/* B: fp32, every operation rounded on its own, never contracted, IEEE '/'  */
+/* and sqrtf, GLSL max / clamp as x < y ? y : x; matrix x vector is R2's    */
+/* left-to-right sums, dot is L's, normalize is F3's v / sqrtf(dot); cross, */
+/* mix (a * (1 - t) + b * t) and smoothstep (t = clamp((x - e0) / (e1 -     */
+/* e0), 0, 1); (t * t) * (3 - 2 * t)) are the GLSL specification's          */
+/* formulas.                                                                */
+/*  A1 positions (ssao.comp:51-71).  For a texel (px, py) of the ssao_w x   */
+/*     ssao_h grid uv = (float(pixel) + 0.5f) * (1.0f / float(res)); depth  */
+/*     = B3's LinearClamp sample of the full-size depth plane at uv;        */
+/*     position = inverse_projection x (uv.x * 2 - 1, (1 - uv.y) * 2 - 1,   */
+/*     depth, 1), xyz / w.  THE SHADER HOLDS pixel AS uvec2 (the binary     */
+/*     converts it with OpConvertUToF in front of the + 0.5): the left      */
+/*     neighbour of column 0 and the upper neighbour of row 0 are pixel     */
+/*     0xFFFFFFFF, which converts to 2^32; its uv clamps to the far edge    */
+/*     and its x / y are enormous.  THIS IS THE REFERENCE'S BEHAVIOUR AND   */
+/*     IS KEPT: it decides the normal of column 0 and row 0.  Texels at or  */
+/*     beyond res are positions like any other and write nothing.           */
+/*  A2 the normal (:78-115).  With the centre p0 and the right, left, down, */
+/*     up neighbours: horizontal = |right.z - p0.z| < |left.z - p0.z| ?     */
+/*     right : left, vertical = |down.z - p0.z| < |up.z - p0.z| ? down : up */
+/*     (a tie takes left / up); (p1, p2) = (right, up), (down, right), (up, */
+/*     left) or (left, down) as the shader's four branches have them;       */
+/*     normal = normalize(cross(p2 - p0, p1 - p0)).                         */
+/*  A3 noise (:120-127), NearestRepeat: u = float(gid) / float(noise_size)  */
+/*     per axis of the SSAO pixel gid; the texel is floor(u *               */
+/*     float(noise_size)) wrapped into [0, noise_size); a snorm8 byte b     */
+/*     reads as max(b / 127.0f, -1).  random_vec = normalize((n.x, n.y,     */
+/*     0)); tangent = normalize(random_vec - normal * dot(random_vec,       */
+/*     normal)); bitangent = cross(normal, tangent).  A (0, 0) noise texel  */
+/*     makes them NaN, as in the shader; then every sample's proj is NaN    */
+/*     and fails A5's range test, nothing is added and THE BYTE IS 255, NOT */
+/*     0: the pixel does not count in nonfinite_pixels.                     */
+/*  A4 per sample i (:134-141), independent of the pixel: fi = float(i) /   */
+/*     float(sample_count); the 1-D NearestRepeat texel floor(fi *          */
+/*     float(samples_size)) mod samples_size, as unorm8 / 255.0f, of which  */
+/*     only .z is used; hammersley_2d as written (the bit reversal,         */
+/*     float(bits) * 2.3283064365386963e-10f); hemispherepoint_uniform(fi,  */
+/*     rdi): phi = (rdi * 2) * PI, cosTheta = 1 - fi, sinTheta = sqrtf(1 -  */
+/*     cosTheta * cosTheta), (cos(phi) * sinTheta, sin(phi) * sinTheta,     */
+/*     cosTheta) with H6's sine and cosine, whose domain [0, 2 pi] covers   */
+/*     phi; radius = mix(min_radius, max_radius, z * z).                    */
+/*  A5 the test (:140-154).  cone = (tangent * h.x + bitangent * h.y) +     */
+/*     normal * h.z; sample_point = p0 - cone * radius; proj = projection x */
+/*     (sample_point, 1); xyz /= w; xy = xy * (0.5, -0.5) + 0.5.  A sample  */
+/*     is in range iff all three components equal their clamp to [0, 1]     */
+/*     (NaN fails).  In-range samples read sample_depth by B3 at proj.xy;   */
+/*     sample_depth_lin = 0.01f / sample_depth (the literal is the          */
+/*     shader's, not the camera's near plane); range_check = smoothstep(0,  */
+/*     1, min_radius / abs(sample_depth_lin - proj.w)); occlusion +=        */
+/*     (sample_depth >= proj.z ? 1 : 0) * range_check, in sample order.     */
+/*  A6 the store.  occlusion = 1 - occlusion / float(sample_count); the R8  */
+/*     byte is uint8(clamp(c, 0, 1) * 255.0f + 0.5f), T4's byte rule.  NaN  */
+/*     stores 0 and counts in nonfinite_pixels (it arises from range_check: */
+/*     min_radius 0 and a sample at its own surface is 0 / 0); nothing else */
+/*     non-finite can reach a byte.  VULKAN LEAVES THE CONVERSION'S LAST    */
+/*     BIT TO THE IMPLEMENTATION: THIS IS THE PROJECT'S CHOICE.             */
+/*  A7 the blur (ssao_blur.comp).  The four textureGather calls are at      */
+/*     (float(pixel) + 0.5f - off) / float(size), off = (0, 0), (2, 0), (0, */
+/*     2), (2, 2): a division, as written.  Each returns the four texels of */
+/*     B3's footprint, i0 = floor(u * W - 0.5f), i0 and i0 + 1 clamped, in  */
+/*     the order x = (i0, j1), y = (i1, j1), z = (i1, j0), w = (i0, j0);    */
+/*     texels read as byte / 255.0f.  The sums are the two levels of dot(., */
+/*     vec4(1)), left to right, then * 0.0625f, then A6's byte.  THE        */
+/*     GATHERS SIT EXACTLY ON TEXEL CENTRES, WHERE A HARDWARE FOOTPRINT IS  */
+/*     IMPLEMENTATION-DEFINED: fp32 AS WRITTEN, WITH THE floor IT YIELDS,   */
+/*     IS THIS PROJECT'S CHOICE, as B3 is.                                  */
+/*  A8 the fragment read (forward.frag:336-337).  ao_pixel[p] = B3's sample */
+/*     of blurred (byte / 255.0f) at (float(x) + 0.5f, float(y) + 0.5f) /   */
+/*     float(screen) for every screen pixel.  min with the material's ao is */
+/*     the consumer's.                                                      */
+/*  A9 stats (may be NULL) is cleared by the call: pixels = ssao_w *        */
+/*     ssao_h, nonfinite_pixels, unoccluded_pixels (raw byte 255) and the   */
+/*     64-bit samples_in_range.  Every output depends on its own pixel and  */
+/*     the inputs only: independent of scheduling and of how the kernel     */
+/*     tiles the target.                                                    */
+/* Outputs: raw (ssao.comp's R8 image), blurred (ssao_blur.comp's, which    */
+/* the frame uses), ao_pixel (A8); each may be NULL, not all; blurred needs */
+/* raw and ao_pixel needs blurred: the call has no scratch.  Launches: one  */
+/* that clears the counters, the SSAO launch (a workgroup takes a 16 x 16   */
+/* tile and stages its bordered tile of positions and A4's table in LDS),   */
+/* the blur and the fragment read, ordered by the stream.                   */
+/* OUT OF SCOPE: the sky-light term (forward.frag:404) and render mode 6    */
+/* (:561) that consume ao (cube maps, the BRDF table); the material's       */
+/* occlusion texture; a hardware sampler's fixed-point weights and gather   */
+/* footprint.                                                               */
+/*   ORBIT_E_INVALID  (message prefix ssao:) depth, noise or samples NULL;  */
+/*                    every output NULL; blurred without raw or ao_pixel    */
+/*                    without blurred; depth, ao_pixel or samples not 4-B,  */
+/*                    noise not 2-B, stats not 8-B aligned; a size 0 or     */
+/*                    above ORBIT_RASTER_MAX_DIM, ssao above screen;        */
+/*                    noise_size outside 1..64, samples_size outside        */
+/*                    1..256, sample_count outside 1..64; a radius negative */
+/*                    or not finite; flags not 0; an output equal to an     */
+/*                    input or to another output.  As in the sibling calls  */
+/*                    the check compares the pointers only: ranges that     */
+/*                    overlap without starting at one address are the       */
+/*                    caller's to avoid, and their result is undefined.     */
+/* Kernel launches only: no allocation, no scratch, no host wait; a graph   */
+/* captures the call on a fresh context's first call.                       */
+/* ------------------------------------------------------------------------ */
+#define ORBIT_SSAO_MAX_SAMPLES 64u       /* sample_count: the UI's range, ssao.rs:31 */
+#define ORBIT_SSAO_MAX_NOISE_SIZE 64u    /* noise_size */
+#define ORBIT_SSAO_MAX_SAMPLES_SIZE 256u /* samples_size */
+typedef struct OrbitSsaoStats { /* DEVICE, 24 B, 8-B aligned, cleared by the call (A9) */
+    uint32_t pixels, nonfinite_pixels, unoccluded_pixels, _pad;
+    uint64_t samples_in_range;
+} OrbitSsaoStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitSsaoStats) == 24, "SsaoStats is 24 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSsaoStats, samples_in_range) == 16, "samples_in_range @16");
+typedef struct OrbitSsao { /* HOST block, 224 B; every pointer a DEVICE pointer */
+    const float *depth;     /* screen_w * screen_h floats, reverse-z, 0 = uncovered */
+    const int8_t *noise;    /* noise_size * noise_size pairs (R8G8_SNORM), 2-B aligned */
+    const uint8_t *samples; /* samples_size * 4 bytes (R8G8B8A8_UNORM), 4-B aligned */
+    uint8_t *raw;           /* NULL, or ssao_w * ssao_h bytes */
+    uint8_t *blurred;       /* NULL, or ssao_w * ssao_h bytes; needs raw */
+    float *ao_pixel;        /* NULL, or screen_w * screen_h floats; needs blurred */
+    OrbitSsaoStats *stats;  /* NULL, or the counters */
+    float projection[16], inverse_projection[16]; /* column-major, GpuSSAOInfo's two (ssao.rs:50-53) */
+    uint32_t screen_w, screen_h;
+    uint32_t ssao_w, ssao_h; /* the screen's, or each / 2 (ssao.rs:93-97); any 1 <= ssao <= screen */
+    uint32_t noise_size, samples_size, sample_count;
+    float min_radius, max_radius; /* SsaoSettings, ssao.rs:9-25 */
+    uint32_t flags;               /* 0 */
+} OrbitSsao;
+ORBIT_STATIC_ASSERT(sizeof(OrbitSsao) == 224, "Ssao is 224 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSsao, raw) == 24, "raw @24");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSsao, stats) == 48, "stats @48");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSsao, projection) == 56, "projection @56");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSsao, inverse_projection) == 120, "inverse_projection @120");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSsao, screen_w) == 184, "screen_w @184");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSsao, noise_size) == 200, "noise_size @200");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSsao, min_radius) == 212, "min_radius @212");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSsao, flags) == 220, "flags @220");
+
+/* the reference's SSAO, its blur and forward.frag's read of it per pixel; see above */
+int32_t orbit_ssao(OrbitCtx *ctx, const OrbitSsao *job, void *stream);
 
 #ifdef __cplusplus
 }

@@ -238,6 +238,29 @@ def fill_post_process(j, width, height, exposure, bloom_intensity, render_mode, 
     j.flags = POST_BGRA if bgra is True else int(bgra)
 
 
+SSAO_MAX_SAMPLES, SSAO_MAX_NOISE_SIZE, SSAO_MAX_SAMPLES_SIZE = 64, 64, 256  # ORBIT_SSAO_MAX_*
+
+
+class Ssao(C.Structure):  # OrbitSsao (224 B)
+    _fields_ = [("depth", C.c_void_p), ("noise", C.c_void_p), ("samples", C.c_void_p), ("raw", C.c_void_p), ("blurred", C.c_void_p),
+                ("ao_pixel", C.c_void_p), ("stats", C.c_void_p), ("projection", C.c_float * 16), ("inverse_projection", C.c_float * 16),
+                ("screen_w", C.c_uint32), ("screen_h", C.c_uint32), ("ssao_w", C.c_uint32), ("ssao_h", C.c_uint32),
+                ("noise_size", C.c_uint32), ("samples_size", C.c_uint32), ("sample_count", C.c_uint32), ("min_radius", C.c_float),
+                ("max_radius", C.c_float), ("flags", C.c_uint32)]
+
+
+def fill_ssao(j, projection, inverse_projection, screen_w, screen_h, ssao_w, ssao_h, noise_size, samples_size, sample_count, min_radius,
+              max_radius, flags=0):
+    """The by-value fields of an OrbitSsao; the matrices column-major, 16 floats each."""
+    import numpy as np
+
+    j.projection = (C.c_float * 16)(*np.asarray(projection, dtype=np.float32).reshape(16))
+    j.inverse_projection = (C.c_float * 16)(*np.asarray(inverse_projection, dtype=np.float32).reshape(16))
+    j.screen_w, j.screen_h, j.ssao_w, j.ssao_h = int(screen_w), int(screen_h), int(ssao_w), int(ssao_h)
+    j.noise_size, j.samples_size, j.sample_count = int(noise_size), int(samples_size), int(sample_count)
+    j.min_radius, j.max_radius, j.flags = float(min_radius), float(max_radius), int(flags)
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -349,6 +372,7 @@ SYMBOLS = {
     "orbit_bloom_layout": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(BloomLayout)]),
     "orbit_bloom": (C.c_int32, [C.c_void_p, C.POINTER(Bloom), C.c_void_p]),
     "orbit_post_process": (C.c_int32, [C.c_void_p, C.POINTER(PostProcess), C.c_void_p]),
+    "orbit_ssao": (C.c_int32, [C.c_void_p, C.POINTER(Ssao), C.c_void_p]),
 }
 
 _lib = None

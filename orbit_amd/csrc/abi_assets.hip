@@ -8,7 +8,8 @@
 // orbit_surface_fragments, the fragment shader's inputs per pixel from those and the vertex attributes
 // (surface_fragments.hip), and orbit_fragments_shade, the clustered lighting of those pixels (fragments_shade.hip), with
 // orbit_fragments_shade_shadowed, the same with cascaded shadows served (fragments_shade_shadowed.hip), and what follows
-// the colour plane they leave: orbit_bloom with orbit_bloom_layout and orbit_post_process (bloom.hip).
+// the colour plane they leave: orbit_bloom with orbit_bloom_layout and orbit_post_process (bloom.hip), and orbit_ssao, the
+// reference's ambient occlusion of the depth plane (ssao.hip).
 #include "abi_internal.h"
 #include "post_common.h" // bloom_layout
 
@@ -438,6 +439,41 @@ int32_t orbit_post_process(OrbitCtx *ctx, const OrbitPostProcess *job, void *str
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_post_process(j, ctx->num_cus, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch post_process");
+    return ORBIT_OK;
+}
+
+// A launch that starts the counters, then the SSAO launch, the blur and the fragment read (ssao.hip); as orbit_bloom
+// otherwise.
+int32_t orbit_ssao(OrbitCtx *ctx, const OrbitSsao *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "ssao: job is NULL");
+    const OrbitSsao &j = *job;
+    if (j.flags != 0u) return fail(ctx, ORBIT_E_INVALID, "ssao: flags %#x", j.flags);
+    if (j.screen_w == 0 || j.screen_h == 0 || j.screen_w > ORBIT_RASTER_MAX_DIM || j.screen_h > ORBIT_RASTER_MAX_DIM)
+        return fail(ctx, ORBIT_E_INVALID, "ssao: screen %u x %u (1..%u each)", j.screen_w, j.screen_h, ORBIT_RASTER_MAX_DIM);
+    if (j.ssao_w == 0 || j.ssao_h == 0 || j.ssao_w > j.screen_w || j.ssao_h > j.screen_h)
+        return fail(ctx, ORBIT_E_INVALID, "ssao: ssao size %u x %u (1..%u x 1..%u, the screen)", j.ssao_w, j.ssao_h, j.screen_w, j.screen_h);
+    if (j.noise_size == 0 || j.noise_size > ORBIT_SSAO_MAX_NOISE_SIZE || j.samples_size == 0 || j.samples_size > ORBIT_SSAO_MAX_SAMPLES_SIZE)
+        return fail(ctx, ORBIT_E_INVALID, "ssao: noise_size %u (1..%u), samples_size %u (1..%u)", j.noise_size, ORBIT_SSAO_MAX_NOISE_SIZE, j.samples_size, ORBIT_SSAO_MAX_SAMPLES_SIZE);
+    if (j.sample_count == 0 || j.sample_count > ORBIT_SSAO_MAX_SAMPLES) return fail(ctx, ORBIT_E_INVALID, "ssao: sample_count %u (1..%u)", j.sample_count, ORBIT_SSAO_MAX_SAMPLES);
+    for (const float v : {j.min_radius, j.max_radius})
+        if (!(v >= 0.0f && v < INFINITY)) return fail(ctx, ORBIT_E_INVALID, "ssao: min_radius %g, max_radius %g (finite, not negative)", j.min_radius, j.max_radius);
+    if (!j.depth || !j.noise || !j.samples) return fail(ctx, ORBIT_E_INVALID, "ssao: NULL input");
+    if (!j.raw && !j.blurred && !j.ao_pixel) return fail(ctx, ORBIT_E_INVALID, "ssao: raw, blurred and ao_pixel are all NULL");
+    if ((j.blurred && !j.raw) || (j.ao_pixel && !j.blurred)) return fail(ctx, ORBIT_E_INVALID, "ssao: blurred needs raw and ao_pixel needs blurred");
+    if ((((uintptr_t)j.depth | (uintptr_t)j.ao_pixel | (uintptr_t)j.samples) & 3u) || ((uintptr_t)j.noise & 1u) || ((uintptr_t)j.stats & 7u))
+        return fail(ctx, ORBIT_E_INVALID, "ssao: depth, ao_pixel and samples must be 4-B aligned, noise 2-B, stats 8-B");
+    const void *const inputs[3] = {j.depth, j.noise, j.samples};
+    const void *const outputs[4] = {j.raw, j.blurred, j.ao_pixel, j.stats};
+    for (int a = 0; a < 4; a++) {
+        for (const void *in : inputs)
+            if (outputs[a] && outputs[a] == in) return fail(ctx, ORBIT_E_INVALID, "ssao: an output is an input (%p)", in);
+        for (int b = a + 1; b < 4; b++)
+            if (outputs[a] && outputs[a] == outputs[b]) return fail(ctx, ORBIT_E_INVALID, "ssao: two outputs are one buffer (%p)", outputs[a]);
+    }
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "ssao: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_ssao(j, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch ssao");
     return ORBIT_OK;
 }
 

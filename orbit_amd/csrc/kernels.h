@@ -466,6 +466,9 @@ hipError_t launch_bloom(const OrbitBloom &job, hipStream_t s);
 // bloom.hip: orbit_post_process — `job` validated by the entry point.  One launch starts the counters, the next makes one
 // pass over the pixels, a thread per pixel
 hipError_t launch_post_process(const OrbitPostProcess &job, uint32_t num_cus, hipStream_t s);
+// ssao.hip: orbit_ssao — `job` validated by the entry point.  One launch starts the counters, then the SSAO launch (a 16 x
+// 16 tile per workgroup), the blur and the fragment read where their outputs are wanted, ordered by the stream.
+hipError_t launch_ssao(const OrbitSsao &job, hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

@@ -27,6 +27,27 @@ ORBIT_RASTER_FN void shade_normalize(float *v) {
     for (int i = 0; i < 3; i++) v[i] = v[i] / len;
 }
 
+// H6's and A4's sine and cosine, the project's own, of theta in [0, 2 pi]: quadrant reduction in two steps, then fixed polynomials
+ORBIT_RASTER_FN void shadow_sincos(float theta, float &s, float &c) {
+    const int k = (int)(theta * 0.636619772f + 0.5f);
+    const float kf = (float)k;
+    const float r = (theta - kf * 1.5703125f) - kf * 4.83826794897e-4f;
+    const float w = r * r;
+    const float sin_r = ((((-1.9515295891e-4f * w + 8.3321608736e-3f) * w) + -1.6666654611e-1f) * w) * r + r;
+    const float cos_r = ((((2.443315711809948e-5f * w + -1.388731625493765e-3f) * w) + 4.166664568298827e-2f) * w) * w + (1.0f - 0.5f * w);
+    switch (k & 3) {
+    case 0: s = sin_r, c = cos_r; break;
+    case 1: s = cos_r, c = -sin_r; break;
+    case 2: s = -sin_r, c = -cos_r; break;
+    default: s = -cos_r, c = sin_r; break;
+    }
+}
+
+// R2's clip = M x (x, y, z, w), M column-major
+ORBIT_RASTER_FN void shadow_project(const float *M, float x, float y, float z, float w, float *c) {
+    for (int r = 0; r < 4; r++) c[r] = ((M[r] * x + M[4 + r] * y) + M[8 + r] * z) + M[12 + r] * w;
+}
+
 // uint(float): saturating, NaN -> 0 (orbit_device.h f2u_sat)
 ORBIT_RASTER_FN uint32_t shade_f2u_sat(float f) {
     if (!(f > 0.0f)) return 0u;

@@ -1,10 +1,10 @@
 // shadow_common.h — the shadow arithmetic of orbit_fragments_shade_shadowed (include/orbit_abi_ext.h H1-H10, DESIGN.md
 // §4.26), written once for the device kernels (fragments_shade_shadowed.hip) and the host mirror
-// (orbit_amd/host/orbit_raster.cpp), on top of shade_common.h's L1-L9.  The pieces: shadow_theta and shadow_sincos are
-// H6's noise and the project's own sine and cosine; shadow_eval is H2-H8 of one shadowed light at one pixel;
-// shadow_light_checked is H1's range check; shadow_pixel_light is L5 / L6 / H9 of one light of the walk;
-// shadow_shade_pixel is the whole of L1-L8 with H for a lane or a host loop that walks its own list.  Equal inputs,
-// equal functions: equal bytes.
+// (orbit_amd/host/orbit_raster.cpp), on top of shade_common.h's L1-L9.  The pieces: shadow_theta is H6's noise (its sine
+// and cosine, shadow_sincos, and R2's shadow_project live in shade_common.h, where ssao_common.h finds them too);
+// shadow_eval is H2-H8 of one shadowed light at one pixel; shadow_light_checked is H1's range check; shadow_pixel_light is
+// L5 / L6 / H9 of one light of the walk; shadow_shade_pixel is the whole of L1-L8 with H for a lane or a host loop that
+// walks its own list.  Equal inputs, equal functions: equal bytes.
 #pragma once
 #include "shade_common.h"
 
@@ -33,32 +33,11 @@ ORBIT_RASTER_FN float shadow_theta(uint32_t x, uint32_t y) {
     return (ign * 2.0f) * kShadePi;
 }
 
-// H6: the project's sine and cosine of theta in [0, 2 pi]: quadrant reduction in two steps, then fixed polynomials
-ORBIT_RASTER_FN void shadow_sincos(float theta, float &s, float &c) {
-    const int k = (int)(theta * 0.636619772f + 0.5f);
-    const float kf = (float)k;
-    const float r = (theta - kf * 1.5703125f) - kf * 4.83826794897e-4f;
-    const float w = r * r;
-    const float sin_r = ((((-1.9515295891e-4f * w + 8.3321608736e-3f) * w) + -1.6666654611e-1f) * w) * r + r;
-    const float cos_r = ((((2.443315711809948e-5f * w + -1.388731625493765e-3f) * w) + 4.166664568298827e-2f) * w) * w + (1.0f - 0.5f * w);
-    switch (k & 3) {
-    case 0: s = sin_r, c = cos_r; break;
-    case 1: s = cos_r, c = -sin_r; break;
-    case 2: s = -sin_r, c = -cos_r; break;
-    default: s = -cos_r, c = sin_r; break;
-    }
-}
-
 // clamp((int)f, 0, res - 1) of an f that is floorf's, the conversion saturating, NaN -> 0
 ORBIT_RASTER_FN uint32_t shadow_texel(float f, uint32_t res) {
     if (!(f > 0.0f)) return 0u;
     if (f >= (float)res) return res - 1u;
     return (uint32_t)f;
-}
-
-// R2's clip = M x (x, y, z, w), M column-major
-ORBIT_RASTER_FN void shadow_project(const float *M, float x, float y, float z, float w, float *c) {
-    for (int r = 0; r < 4; r++) c[r] = ((M[r] * x + M[4 + r] * y) + M[8 + r] * z) + M[12 + r] * w;
 }
 
 struct ShadowResult {

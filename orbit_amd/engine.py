@@ -585,6 +585,24 @@ class Engine:
         _lib.fill_post_process(j, width, height, exposure, bloom_intensity, render_mode, bgra)
         _lib.check(self._lib.orbit_post_process(self._ctx, C.byref(j), _stream(stream)), self._ctx)
 
+    # -- the reference's SSAO of a depth plane, its blur and forward.frag's read of it (orbit_ssao)
+    def ssao(self, depth, screen_w, screen_h, ssao_w, ssao_h, projection, inverse_projection, noise, noise_size, samples, samples_size,
+             raw=None, blurred=None, ao_pixel=None, sample_count=32, min_radius=0.1, max_radius=0.5, stats=None, flags=0, stream=None):
+        """From `depth` (screen_w * screen_h floats, reverse-z, 0 = uncovered: raster_depth's or visibility_resolve's) to
+        `raw` (ssao_w * ssao_h bytes: ssao.comp's R8 image), `blurred` (the same size: ssao_blur.comp's, which the frame
+        uses; needs raw) and `ao_pixel` (screen_w * screen_h floats: what forward.frag:336-337 samples per pixel; needs
+        blurred).  ssao_w, ssao_h: the screen's or orbit_amd.post.ssao_resolution's halves.  projection, inverse_projection:
+        the camera's, column-major.  noise (noise_size^2 int8 pairs) and samples (samples_size x 4 bytes): the reference's
+        two tables (orbit_amd.post.ssao_tables).  sample_count, min_radius, max_radius: SsaoSettings (these are its
+        defaults).  stats (24 bytes, layouts.SSAO_STATS, cleared by the call) may be None.  Byte-equal to
+        orbit_amd.post.host_ssao.  Enqueued on `stream`."""
+        j = _lib.Ssao()
+        j.depth, j.noise, j.samples, j.raw, j.blurred, j.ao_pixel, j.stats = (_ptr(depth), _ptr(noise), _ptr(samples), _ptr(raw), _ptr(blurred),
+                                                                               _ptr(ao_pixel), _ptr(stats))
+        _lib.fill_ssao(j, projection, inverse_projection, screen_w, screen_h, ssao_w, ssao_h, noise_size, samples_size, sample_count, min_radius,
+                       max_radius, flags)
+        _lib.check(self._lib.orbit_ssao(self._ctx, C.byref(j), _stream(stream)), self._ctx)
+
     # -- cull statistics: what entity_cull + meshlet_cull with these arguments would do, counted (orbit_cull_stats)
     def cull_stats(self, stats, cull_info, entity_draw_buffer, mesh_info_buffer, meshlet_dispatch_buffer, entity_buffer,
                    entity_draw_count, dispatch_capacity, meshlet_buffer, draw_commands_buffer, material_buffer,

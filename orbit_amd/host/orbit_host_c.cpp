@@ -11,6 +11,7 @@
 #include "orbit_gltf.hpp"
 #include "orbit_raster.hpp"
 #include "orbit_post.hpp"
+#include "orbit_ssao.hpp"
 #include "orbit_scene.hpp"
 #include "../csrc/block_pretest.h"
 #include "../csrc/shade_common.h"
@@ -655,6 +656,19 @@ int32_t orbit_host_post_process(const OrbitPostProcess *job) {
         raster::post_process(*job);
     });
 }
+
+int32_t orbit_host_ssao(const OrbitSsao *job, uint64_t *census) {
+    return guarded([&] {
+        if (!job) throw Panic("ssao: job is NULL");
+        raster::ssao(*job, census);
+    });
+}
+// the pieces of csrc/ssao_common.h, for tests
+void orbit_host_ssao_table(const uint8_t *samples, uint32_t samples_size, uint32_t sample_count, float min_radius, float max_radius, float *table) {
+    raster::ssao_table(samples, samples_size, sample_count, min_radius, max_radius, table);
+}
+void orbit_host_ssao_in_range(const float *proj, uint64_t n, uint8_t *out) { raster::ssao_in_range_array(proj, n, out); }
+void orbit_host_ssao_range_check(const float *args, uint64_t n, float *out) { raster::ssao_range_check_array(args, n, out); }
 
 // the pieces of csrc/post_common.h, for tests
 void orbit_host_bloom_downsample_floats(const float *src, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, uint32_t level0,

@@ -278,6 +278,17 @@ void orbit_host_bloom_downsample_floats(const float *src, uint32_t src_w, uint32
                                         const float *threshold_filter, float *dst);
 void orbit_host_bloom_upsample_floats(const float *src, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, float filter_radius,
                                       float *dst);
+/* the reference of orbit_ssao (A1-A9): the device call's block with HOST pointers in it; raw, blurred, ao_pixel and stats
+ * hold the device's bytes.  census (may be NULL): 19 counters over every pixel and sample — A2's four branches, samples in
+ * range / out of range / occluded / not occluded, range_check strictly inside (0, 1) / 0 / 1 / NaN, samples with
+ * sample_depth == proj.z, pixels with a horizontal and with a vertical tie of A2, in-range samples with a component
+ * exactly 0 and exactly 1, rejected samples with a component one step below 0 and one above 1. */
+int32_t orbit_host_ssao(const OrbitSsao *job, uint64_t *census);
+/* tests: A4's table (sample_count x 4 floats: direction, radius), A5's range test of n (x, y, z) triples and its
+ * range_check of n (min_radius, sample_depth, proj.w) triples */
+void orbit_host_ssao_table(const uint8_t *samples, uint32_t samples_size, uint32_t sample_count, float min_radius, float max_radius, float *table);
+void orbit_host_ssao_in_range(const float *proj, uint64_t n, uint8_t *out);
+void orbit_host_ssao_range_check(const float *args, uint64_t n, float *out);
 /* tests: B7 of n texels (clamped may be NULL: 1 per texel that counts in clamped_texels), and powc of B5 / T4 */
 void orbit_host_bloom_pack(const float *rgb, uint64_t n, uint32_t *words, uint8_t *clamped);
 void orbit_host_bloom_unpack(const uint32_t *words, uint64_t n, float *rgb);

@@ -80,6 +80,8 @@ SHADOW_STATS = np.dtype([(n, "<u4") for n in ("shadowed_pixels", "no_cascade_pix
 # OrbitBloomStats and OrbitPostStats: the counters of orbit_bloom and orbit_post_process
 BLOOM_STATS = np.dtype([(n, "<u4") for n in ("levels", "texels_written", "nonfinite_inputs", "clamped_texels")])
 POST_STATS = np.dtype([(n, "<u4") for n in ("pixels", "nonfinite_pixels", "bloom_pixels", "_pad")])
+# OrbitSsaoStats: the counters of orbit_ssao (24 B)
+SSAO_STATS = np.dtype([(n, "<u4") for n in ("pixels", "nonfinite_pixels", "unoccluded_pixels", "_pad")] + [("samples_in_range", "<u8")])
 # OrbitShadowData, types.glsl:29-33 in std430 (288 B): the matrices column-major
 SHADOW_DATA = np.dtype([("light_projection_matrices", "<f4", (4, 16)), ("shadow_map_world_sizes", "<f4", (4,)),
                         ("shadow_map_indices", "<u4", (4,))])

@@ -7,8 +7,11 @@ instances, 320 x 180, 200 point lights and a sun with four 256^2 cascades) shade
                         bytes that differ from the GLSL in float64)
   --device              the three calls on the GPU from the same planes, compared byte for byte with the mirrors' picture;
                         exit code 1 if a byte differs.  Writes the device's picture; --out is not touched.
+  --ao FILE             also writes the frame's blurred ambient occlusion (orbit_ssao at half resolution, SsaoSettings'
+                        defaults) as a binary PGM: the mirror's bytes, or with --device the GPU's, compared
+                        byte for byte with the mirror's (raw, blurred, ao_pixel and the counters).  Nothing else changes.
 Uncovered pixels show what the colour plane holds there (0: black); the skybox is out of scope.
-Usage: python tools/render_frame.py [--device] [--picture frame.ppm] [--exposure 4.0] [--out profiles/post_chain_cpu.json]
+Usage: python tools/render_frame.py [--device] [--picture frame.ppm] [--ao ao.pgm] [--exposure 4.0] [--out profiles/post_chain_cpu.json]
 """
 import argparse
 import importlib.util
@@ -70,10 +73,55 @@ def device_picture(f, tool, exposure):
     return out
 
 
+SSAO_TABLE_SEED = 1
+
+
+def ssao_inputs(f):
+    """the frame's depth plane, the camera's two matrices, the two tables and the half-resolution size"""
+    import scenes as sc
+    from orbit_amd import passes, post, raster
+
+    depth, _, _ = raster.host_visibility_resolve(f["frame"]["visibility"], want_command_pixels=False)
+    proj = sc.mat4_cols(f["frame"]["cam"].proj)
+    noise, samples = post.ssao_tables(SSAO_TABLE_SEED)
+    depth = np.ascontiguousarray(depth, np.float32).reshape(f["height"], f["width"])
+    return depth, proj, passes.mat4_inverse(proj), noise, samples, post.ssao_resolution(f["width"], f["height"])
+
+
+def host_ao(f):
+    from orbit_amd import post
+
+    depth, proj, inv, noise, samples, (sw, sh) = ssao_inputs(f)
+    return post.host_ssao(depth, proj, inv, noise, samples, sw, sh)
+
+
+def device_ao(f):
+    """orbit_ssao on the GPU from the same depth -> (raw, blurred, ao_pixel, stats) as host arrays"""
+    import torch
+
+    from orbit_amd.engine import Engine
+
+    depth, proj, inv, noise, samples, (sw, sh) = ssao_inputs(f)
+    w, h = f["width"], f["height"]
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).cuda()  # noqa: E731
+    d_depth, d_noise, d_samples = up(depth), up(noise), up(samples)
+    raw, blurred = (torch.zeros(sw * sh, dtype=torch.uint8, device="cuda") for _ in range(2))
+    ao = torch.zeros(w * h, dtype=torch.float32, device="cuda")
+    stats = torch.zeros(3, dtype=torch.int64, device="cuda")
+    eng = Engine(0, max_entities=1024, max_dispatches=1024, max_draws=1024)
+    eng.ssao(d_depth, w, h, sw, sh, proj, inv, d_noise, noise.shape[0], d_samples, samples.shape[0], raw=raw, blurred=blurred, ao_pixel=ao, stats=stats)
+    torch.cuda.synchronize()
+    eng.status()
+    out = [t.cpu().numpy() for t in (raw, blurred, ao, stats)]
+    eng.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--picture", default="frame.ppm")
+    ap.add_argument("--ao", default=None, metavar="FILE")
     ap.add_argument("--exposure", type=float, default=4.0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "post_chain_cpu.json"))
     args = ap.parse_args()
@@ -93,6 +141,15 @@ def main():
                      bloom_stats=bstats.tobytes() == bloom["stats"].tobytes(), post_stats=pstats.tobytes() == out["stats"].tobytes())
         post.write_ppm(args.picture, rgba8.reshape(h, w, 4))
         print(json.dumps(dict(width=w, height=h, picture=os.path.basename(args.picture), device_equals_host=equal)))
+        if args.ao:
+            want = host_ao(f)
+            raw, blurred, ao, stats = device_ao(f)
+            ao_equal = dict(raw=raw.tobytes() == want["raw"].tobytes(), blurred=blurred.tobytes() == want["blurred"].tobytes(),
+                            ao_pixel=ao.tobytes() == want["ao_pixel"].tobytes(), ssao_stats=stats.tobytes() == want["stats"].tobytes())
+            post.write_pgm(args.ao, blurred.reshape(want["blurred"].shape))
+            print(json.dumps(dict(ao=os.path.basename(args.ao), ssao=list(want["blurred"].shape[::-1]), device_equals_host=ao_equal)))
+            assert all(ao_equal.values()), ao_equal
+            equal.update(ao_equal)
         return 0 if all(equal.values()) else 1
     import test_post_chain_cpu as held  # the figures the CPU tests hold, measured the same way
 
@@ -109,6 +166,11 @@ def main():
     print(text)
     with open(args.out, "w") as fh:
         fh.write(text + "\n")
+    if args.ao:
+        got = host_ao(f)
+        post.write_pgm(args.ao, got["blurred"])
+        print(json.dumps(dict(ao=os.path.basename(args.ao), ssao=list(got["blurred"].shape[::-1]), mean_byte=round(float(got["blurred"].mean()), 2),
+                              **{k: int(got["stats"][k]) for k in L.SSAO_STATS.names if k != "_pad"})))
     return 0
 
 
