@@ -196,28 +196,47 @@ __device__ __forceinline__ void blk_row_eval(WaveTileLds &L, const BlockTileLds 
     rs.count += (uint32_t)__popcll(cand);
 }
 
-// The literal evaluation of the first n <= 64 queued candidates; lane j takes candidate j.
-__device__ __forceinline__ void blk_flush(const MeshletCullParams &p, WaveTileLds &L, const PlaneLds &P, const CandRing &ring,
-                                          const StreamRsrc &SR, int lane, RingState &rs, uint32_t n) {
+// The literal evaluation of the first n <= 64 queued candidates; lane j takes candidate j.  In two steps, so that the
+// end-of-tile flush can have its gather in flight while the slab of the tile after the next is set up: blk_flush_load
+// reads the codes and issues the gather (n = 0: every lane reads outside the resources), blk_flush_eval evaluates.
+struct FlushRegs {
+    uint32_t sp[4], c; // sphere and cone word; a lane without a candidate holds zeros
+    uint32_t rid, ml;
+    bool valid;
+};
+__device__ __forceinline__ FlushRegs blk_flush_load(const WaveTileLds &L, const CandRing &ring, const StreamRsrc &SR, int lane,
+                                                    const RingState &rs, uint32_t n) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const bool valid = (uint32_t)lane < n;
-    const uint32_t code = valid ? (uint32_t)ring.code[(rs.head + (uint32_t)lane) & (kBkRing - 1u)] : 0u;
-    const uint32_t rid = (code >> 5) & 15u, ml = code & 31u;
-    const uint4 rec = L.r[rid].rec;
-    const uint32_t rel = rec.y + ml - SR.first;
-    const uint32_t i = (valid && ml < rec.z && rel < SR.count) ? rel : kNoOffset >> 4; // (a sparse record lies inside)
+    FlushRegs f;
+    f.valid = (uint32_t)lane < n;
+    const uint32_t code = f.valid ? (uint32_t)ring.code[(rs.head + (uint32_t)lane) & (kBkRing - 1u)] : 0u;
+    f.rid = (code >> 5) & 15u, f.ml = code & 31u;
+    const uint4 rec = L.r[f.rid].rec;
+    const uint32_t rel = rec.y + f.ml - SR.first;
+    const uint32_t i = (f.valid && f.ml < rec.z && rel < SR.count) ? rel : kNoOffset >> 4; // (a sparse record lies inside)
     const auto sp = __builtin_amdgcn_raw_buffer_load_b128(SR.sphere, i << 4, 0, 0);
-    const uint32_t c = __builtin_amdgcn_raw_buffer_load_b32(SR.cone, i << 2, 0, 0);
+    f.c = __builtin_amdgcn_raw_buffer_load_b32(SR.cone, i << 2, 0, 0);
+    f.sp[0] = sp[0], f.sp[1] = sp[1], f.sp[2] = sp[2], f.sp[3] = sp[3];
+    return f;
+}
+__device__ __forceinline__ void blk_flush_eval(const MeshletCullParams &p, WaveTileLds &L, const PlaneLds &P, int lane,
+                                               const FlushRegs &f, RingState &rs, uint32_t n) {
     Sphere s;
-    // every candidate's record is affine (block_record_setup); a lane without one holds zeros
-    const uint64_t geo = eval_geometry_mask<0>(p, L, P, rid, make_uint4(sp[0], sp[1], sp[2], sp[3]), make_uint4(c, 0u, 0u, 0u), s, true);
-    const uint64_t vis = geo & ballot(valid);
-    if (lane_of(vis)) atomicOr(reinterpret_cast<uint32_t *>(L.draw_mask) + rid, 1u << ml);
+    // every candidate's record is affine (block_record_setup)
+    const uint64_t geo = eval_geometry_mask<0>(p, L, P, f.rid, make_uint4(f.sp[0], f.sp[1], f.sp[2], f.sp[3]),
+                                               make_uint4(f.c, 0u, 0u, 0u), s, true);
+    const uint64_t vis = geo & ballot(f.valid);
+    if (lane_of(vis)) atomicOr(reinterpret_cast<uint32_t *>(L.draw_mask) + f.rid, 1u << f.ml);
     rs.total += (uint32_t)__popcll(vis);
     rs.head = (rs.head + n) & (kBkRing - 1u);
     rs.count -= n;
+}
+__device__ __forceinline__ void blk_flush(const MeshletCullParams &p, WaveTileLds &L, const PlaneLds &P, const CandRing &ring,
+                                          const StreamRsrc &SR, int lane, RingState &rs, uint32_t n) {
+    const FlushRegs f = blk_flush_load(L, ring, SR, lane, rs, n);
+    blk_flush_eval(p, L, P, lane, f, rs, n);
 }
 
 __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_blocks_kernel(const MeshletCullParams p,
@@ -413,9 +432,16 @@ __global__ __launch_bounds__(kBkWaves * 64, kBkWavesPerSimd) void meshlet_eval_b
 #undef BK_FLUSH
 #undef BK_SETUP_LOADS
         whole = nxt_whole;
+        // The candidates still queued (from bench.py's camera about nine a tile, never 64): the gather of the first 64 goes
+        // out HERE and is evaluated behind the slab's setup, which neither reads nor writes what the evaluation touches
+        // (this tile's slab L and its masks) — so the gather's round trip, which nothing else hid, runs under some 150
+        // instructions of setup instead of in front of an s_waitcnt.  Issued for no candidate too: straight-line code.
+        const uint32_t n_end = min(rs.count, kBkFlush);
+        const FlushRegs fl_end = blk_flush_load(L, ring, SR, lane, rs, n_end);
         setup_write_cls(lds[wave][(it + 2) % 3], cls_sel, rec2, cls2, lane);
         setup_write(p, lds[wave][(it + 2) % 3], rec2, mat2, lane);
         blk_setup(p, lds[wave][(it + 2) % 3], blds[wave][it & 1u], planes, plane_nn, rec2, bnd2, lane); // (this tile's rows are through)
+        if (n_end > 0u) blk_flush_eval(p, L, planes, lane, fl_end, rs, n_end);
         while (rs.count > 0u) blk_flush(p, L, planes, ring, SR, lane, rs, min(rs.count, kBkFlush));
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // the mask writes of this tile
         __builtin_amdgcn_wave_barrier();
