@@ -238,7 +238,8 @@ int32_t orbit_ctx_set_fused_grid(OrbitCtx *ctx, uint32_t max_workgroups);
 /* Tests: the strided launches of the visibility buffer's six readers — orbit_visibility_resolve's clear and its tile
  * walk, orbit_visibility_compact's clear and its mark, orbit_visibility_surface's clear and its tile walk (and
  * orbit_visibility_surface_drawn's), orbit_surface_fragments' clear and its tile walk, orbit_fragments_shade's clear and
- * its tile walk, orbit_fragments_shade_shadowed's clear and its tile walk — take at most
+ * its tile walk, orbit_fragments_shade_shadowed's clear and its tile walk — and orbit_post_process' pass over the pixels
+ * (a thread per pixel, workgroup b taking pixels 256 b, 256 (b + c), ...) take at most
  * `max_workgroups` workgroups (of four waves; a wave takes its 8 x 8 tiles one after another, so under a cap of c wave g
  * takes tiles g, g + 4c, ... of even a small target).  Read when the call is enqueued: a captured launch carries its
  * grid.  0, the default, restores num_cus * 8.  The outputs do not depend on the grid; the compaction's scan, totals and

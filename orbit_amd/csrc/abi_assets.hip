@@ -437,7 +437,7 @@ int32_t orbit_post_process(OrbitCtx *ctx, const OrbitPostProcess *job, void *str
     }
     if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "post_process: ctx is NULL");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    const hipError_t e = launch_post_process(j, ctx->num_cus, (hipStream_t)stream);
+    const hipError_t e = launch_post_process(j, ctx->num_cus, ctx->visibility_grid, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch post_process");
     return ORBIT_OK;
 }

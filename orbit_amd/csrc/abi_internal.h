@@ -112,7 +112,7 @@ struct OrbitCtx {
     uint32_t block_cull_grid = 0;                       // orbit_ctx_set_block_cull_grid: workgroups at most (0 = no cap)
     uint32_t raster_grid = 0;                           // orbit_ctx_set_raster_grid: the same for every raster launch
     uint32_t fused_grid = 0;                            // orbit_ctx_set_fused_grid: the same for the one-launch cull's launches
-    uint32_t visibility_grid = 0;                       // orbit_ctx_set_visibility_grid: the same for the buffer's three readers
+    uint32_t visibility_grid = 0;                       // orbit_ctx_set_visibility_grid: the same for the buffer's readers and orbit_post_process
     char err[512] = {0};
 };
 

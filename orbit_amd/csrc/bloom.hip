@@ -233,14 +233,15 @@ hipError_t launch_bloom(const OrbitBloom &job, hipStream_t s) {
     return hipSuccess;
 }
 
-hipError_t launch_post_process(const OrbitPostProcess &job, uint32_t num_cus, hipStream_t s) {
+hipError_t launch_post_process(const OrbitPostProcess &job, uint32_t num_cus, uint32_t grid_cap, hipStream_t s) {
     const size_t pixels = (size_t)job.width * job.height; // at most 2^30
     if (job.stats) {
         hipLaunchKernelGGL(post_begin_kernel, dim3(1), dim3(1), 0, s, (uint32_t *)job.stats, (uint32_t)pixels);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    const size_t need = (pixels + kThreads - 1u) / kThreads, cap = (size_t)(num_cus ? num_cus : 64u) * 8u; // a resident grid, striding
+    const size_t need = (pixels + kThreads - 1u) / kThreads, resident = (size_t)(num_cus ? num_cus : 64u) * 8u; // a resident grid, striding
+    const size_t cap = grid_cap != 0u && grid_cap < resident ? grid_cap : resident; // orbit_ctx_set_visibility_grid
     hipLaunchKernelGGL(post_process_kernel, dim3((uint32_t)(need < cap ? need : cap)), dim3(kThreads), 0, s, job, pixels);
     return hipGetLastError();
 }

@@ -464,8 +464,9 @@ hipError_t launch_fragments_shade_shadowed(const OrbitFragmentsShadeShadowed &jo
 // of the chain (2 * levels - 1), a workgroup per 16 x 16 destination tile staging its source box in LDS when it fits
 hipError_t launch_bloom(const OrbitBloom &job, hipStream_t s);
 // bloom.hip: orbit_post_process — `job` validated by the entry point.  One launch starts the counters, the next makes one
-// pass over the pixels, a thread per pixel
-hipError_t launch_post_process(const OrbitPostProcess &job, uint32_t num_cus, hipStream_t s);
+// pass over the pixels, a thread per pixel, striding from min(need, num_cus * 8) workgroups and from `grid_cap` at most
+// where it is not 0 (orbit_ctx_set_visibility_grid); the one-thread launch is not capped
+hipError_t launch_post_process(const OrbitPostProcess &job, uint32_t num_cus, uint32_t grid_cap, hipStream_t s);
 // ssao.hip: orbit_ssao — `job` validated by the entry point.  One launch starts the counters, then the SSAO launch (a 16 x
 // 16 tile per workgroup), the blur and the fragment read where their outputs are wanted, ordered by the stream.
 hipError_t launch_ssao(const OrbitSsao &job, hipStream_t s);

@@ -930,7 +930,7 @@ class Engine:
     def set_visibility_grid(self, max_workgroups):
         """orbit_ctx_set_visibility_grid: at most that many workgroups for the strided launches of visibility_resolve,
         visibility_compact (clear and mark), visibility_surface, surface_fragments, fragments_shade and
-        fragments_shade_shadowed, read when the call is
+        fragments_shade_shadowed, and for post_process' pass over the pixels, read when the call is
         enqueued (0 = num_cus * 8; tests)."""
         _lib.check(self._lib.orbit_ctx_set_visibility_grid(self._ctx, int(max_workgroups)), self._ctx)
 

@@ -53,3 +53,69 @@ def image(kind, width, height, seed=7):
 def all_cases(targets=TARGETS):
     """[(name, color, bloom settings)]"""
     return [(f"{kind}_{w}x{h}", image(kind, w, h), SETTINGS[kind]) for (w, h) in targets for kind in IMAGES]
+
+
+# ------------------------------------------------------------------------------- orbit_post_process' trips (DESIGN.md §4.29)
+# post_process_kernel strides over the pixels from G = min(ceil(pixels / 256), cap) workgroups of 256 threads, the cap being
+# num_cus * 8 or what orbit_ctx_set_visibility_grid says: pixel p is lane p % 64 of wave (p % 256) // 64 of workgroup
+# (p // 256) % G in that workgroup's trip (p // 256) // G.  The pixel counts either side of a wave, a workgroup and one, two,
+# three and four workgroups' worth, as 1 x N planes and a few 2-D ones, under caps of 1, 2 and 3:
+POST_THREADS, POST_WAVE = 256, 64
+TRIP_COUNTS = (1, 63, 64, 65, 255, 256, 257, 300, 511, 512, 513, 769, 1025)
+TRIP_TARGETS = tuple((n, 1) for n in TRIP_COUNTS) + ((33, 31), (65, 9), (16, 33), (257, 3), (64, 5))  # 1023, 585, 528, 771, 320 pixels
+TRIP_CAPS = (1, 2, 3)
+# where the marked pixels lie: in waves 0, 1 and 3 of the first block of 256, in the three blocks behind it, in the fifth, and
+# the plane's last pixel.  A non-finite colour is counted in nonfinite_pixels, a bloom word that is not 0 in bloom_pixels
+# (T1: render_mode 0, bloom given and bloom_intensity not 0); no pixel carries both, so the two counters differ
+TRIP_NONFINITE = (0, 5, 67, 200, 256, 326, 512, 513, 768, 1024)
+TRIP_BLOOM = (1, 63, 65, 130, 255, 257, 300, 511, 514, 700, 769, 1023)
+TRIP_BLOOM_WORD = (15 << 6 | 3) | (14 << 6 | 5) << 11 | (16 << 5 | 1) << 22  # B7: about (1.05, 0.54, 2.06), exponent | mantissa per channel
+
+
+def trip_placement(pixels):
+    """-> (nonfinite pixel indices, bloom-marked pixel indices) of a plane of `pixels` pixels: the tables' entries inside
+    it and, where there is room, its last pixel (non-finite) and the one before (bloom)"""
+    bad = sorted({p for p in TRIP_NONFINITE if p < pixels} | ({pixels - 1} if pixels > 2 else set()))
+    lit = sorted({p for p in TRIP_BLOOM if p < pixels and p not in bad} | ({pixels - 2} if pixels > 2 and pixels - 2 not in bad else set()))
+    return bad, lit
+
+
+def trip_image(width, height, marked=True, seed=11):
+    """-> (color (height, width, 4) float32, bloom (height * width,) uint32, expect): HDR noise with trip_placement's
+    pixels made non-finite (NaN, +inf, -inf in turn, in channel p % 3) and their bloom words set; marked=False leaves
+    both out.  expect = dict(pixels, nonfinite_pixels, bloom_pixels) in closed form from the placement"""
+    pixels = width * height
+    rng = np.random.default_rng(seed + 1000 * width + height)
+    c = np.ones((pixels, 4), F)
+    c[:, :3] = rng.uniform(0.0, 1.0, (pixels, 3)) ** 3 * 4.0
+    bloom = np.zeros(pixels, np.uint32)
+    bad, lit = trip_placement(pixels) if marked else ([], [])
+    for i, p in enumerate(bad):
+        c[p, p % 3] = (np.nan, np.inf, -np.inf)[i % 3]
+    bloom[lit] = TRIP_BLOOM_WORD
+    return np.ascontiguousarray(c.reshape(height, width, 4)), bloom, dict(pixels=pixels, nonfinite_pixels=len(bad), bloom_pixels=len(lit))
+
+
+def trip_shape(pixels, cap, resident=2048):
+    """What the launch over `pixels` pixels looks like under a cap of `cap` workgroups (0: none) -> dict(grid, trips: per
+    workgroup, partial_wave: the last block of 256 ends inside a wave, dead_waves: whole waves of it lie behind the plane)"""
+    need = (pixels + POST_THREADS - 1) // POST_THREADS
+    grid = min(need, cap if cap else resident, resident)
+    trips = [len(range(b, need, grid)) for b in range(grid)]
+    tail = pixels - (need - 1) * POST_THREADS  # pixels of the last block, 1..256
+    return dict(grid=grid, trips=trips, partial_wave=tail % POST_WAVE != 0, dead_waves=(POST_THREADS - tail) // POST_WAVE)
+
+
+def trip_shares(marks, pixels, cap, resident=2048):
+    """Of the marked pixels `marks`: does a counter fed by them get shares from two trips of one wave, from two waves of
+    one workgroup, from two workgroups? -> set of "trips", "waves", "workgroups" """
+    grid = trip_shape(pixels, cap, resident)["grid"]
+    where = {((p // POST_THREADS) % grid, (p % POST_THREADS) // POST_WAVE, (p // POST_THREADS) // grid) for p in marks}
+    out = set()
+    if len({(b, w) for b, w, _ in where}) < len(where):
+        out.add("trips")
+    if any(len({w for b2, w, _ in where if b2 == b}) > 1 for b, _, _ in where):
+        out.add("waves")
+    if len({b for b, _, _ in where}) > 1:
+        out.add("workgroups")
+    return out
