@@ -349,6 +349,44 @@ pub struct OrbitSsao {
     pub min_radius: f32, pub max_radius: f32, pub flags: u32,
 }
 
+/// orbit_env_map_layout's answer (264 B, HOST): sizes and offsets in texels of the sky cube's full chain and the
+/// prefiltered cube's levels (8-B texels), the irradiance cube and the BRDF table (4-B texels); rule E0
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitEnvMapLayout {
+    pub sky_size: u32, pub sky_levels: u32, pub irradiance_size: u32, pub prefiltered_size: u32, pub prefiltered_levels: u32, pub brdf_size: u32,
+    pub sky_level_size: [u32; 13], pub sky_level_offset: [u32; 13],
+    pub prefiltered_level_size: [u32; 13], pub prefiltered_level_offset: [u32; 13],
+    pub sky_texels: u64, pub irradiance_texels: u64, pub prefiltered_texels: u64, pub brdf_texels: u64,
+}
+
+/// The counters of orbit_env_map (48 B, DEVICE, 8-B aligned, cleared by the call; rule E8)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitEnvMapStats {
+    pub sky_nonfinite: u64, pub irradiance_nonfinite: u64, pub prefiltered_nonfinite: u64, pub brdf_nonfinite: u64,
+    pub bad_directions: u64, pub _pad: u64,
+}
+
+/// orbit_env_map's argument block (96 B, HOST): the panorama (f32 RGBA; null: `sky` is the caller's), the four products
+/// (R16G16B16A16_SFLOAT cubes in E0's layout, the R16G16_SFLOAT table; null: not made), the optional counters, the sizes
+/// of orbit_env_map_layout and env_map_loader.rs' constants (sample_count 4096, sample_delta 0.025, brdf_sample_count
+/// 1024); rules E0-E12
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitEnvMap {
+    pub equirect: *const f32, pub sky: *mut u16, pub irradiance: *mut u16, pub prefiltered: *mut u16, pub brdf: *mut u16,
+    pub stats: *mut OrbitEnvMapStats,
+    pub equirect_w: u32, pub equirect_h: u32,
+    pub sky_size: u32, pub irradiance_size: u32, pub prefiltered_size: u32, pub prefiltered_levels: u32, pub brdf_size: u32,
+    pub sample_count: u32, pub sample_delta: f32, pub brdf_sample_count: u32, pub flags: u32, pub _pad: u32,
+}
+
+/// orbit_env_sample's argument block (56 B, HOST): a cube in E0's layout, n directions and lods, n rgb results and the
+/// optional counter of bad directions; rule E4
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitEnvSample {
+    pub cube: *const u16, pub directions: *const f32, pub lods: *const f32, pub rgb: *mut f32, pub bad_directions: *mut u64,
+    pub size: u32, pub levels: u32, pub n: u32, pub flags: u32,
+}
+
 /// orbit_visibility_resolve's argument block (48 B, HOST): DEVICE pointers; each output may be null, not all
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct OrbitVisibilityResolve {
@@ -583,6 +621,13 @@ extern "C" {
     pub fn orbit_post_process(ctx: *mut OrbitCtx, job: *const OrbitPostProcess, stream: *mut c_void) -> i32;
     /// compute_ssao of the depth plane (A1-A9): raw, its blur, and what forward.frag reads of the blur per pixel.
     pub fn orbit_ssao(ctx: *mut OrbitCtx, job: *const OrbitSsao, stream: *mut c_void) -> i32;
+    /// The shape of the sky, irradiance and prefiltered cubes and the BRDF table (host only; E0).
+    pub fn orbit_env_map_layout(sky_size: u32, irradiance_size: u32, prefiltered_size: u32, prefiltered_levels: u32, brdf_size: u32,
+                                out: *mut OrbitEnvMapLayout) -> i32;
+    /// EnvironmentMap::new and the BRDF table of forward.rs:113-205 (E0-E12): every product that is not null.
+    pub fn orbit_env_map(ctx: *mut OrbitCtx, job: *const OrbitEnvMap, stream: *mut c_void) -> i32;
+    /// textureLod of a cube in E0's layout at n directions (E4).
+    pub fn orbit_env_sample(ctx: *mut OrbitCtx, job: *const OrbitEnvSample, stream: *mut c_void) -> i32;
 }
 
 /// Turns a non-zero status into the panic the Vulkan path produced (assert!/unwrap, draw_gen.rs:247).

@@ -2168,6 +2168,216 @@ ORBIT_STATIC_ASSERT(offsetof(OrbitSsao, flags) == 220, "flags @220");
 /* the reference's SSAO, its blur and forward.frag's read of it per pixel; see above */
 int32_t orbit_ssao(OrbitCtx *ctx, const OrbitSsao *job, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* orbit_env_map: the images the reference computes once at load time for   */
+/* its sky light (src/passes/env_map_loader.rs, forward.rs:113-205): the    */
+/* sky cube with its mip chain from an equirectangular panorama, the        */
+/* irradiance cube, the prefiltered cube and the BRDF integration table.    */
+/* orbit_env_sample is the cube sampler of rule E4 made public.  ONE        */
+/* definition for the device and the host mirror (orbit_host_env_map,       */
+/* orbit_host_env_sample; csrc/env_common.h); the two agree on every byte.  */
+/* Arithmetic as in L / B / A: fp32, every operation rounded on its own, no */
+/* contraction, IEEE / and sqrtf, normalize / cross / clamp by the GLSL     */
+/* formulas, pow = B5's powc, log2 = L2's log2c.  DESIGN.md §4.30.          */
+/*                                                                          */
+/*  E0 storage.  A cube level is six faces of n x n texels of               */
+/*     R16G16B16A16_SFLOAT (8 B), face-major, faces in Vulkan's layer order */
+/*     +X -X +Y -Y +Z -Z, rows top to bottom.  Level m of a cube of size n  */
+/*     has extent max(1, n >> m); levels are concatenated, level 0 first    */
+/*     (orbit_env_map_layout).  The BRDF table is n x n texels of           */
+/*     R16G16_SFLOAT (4 B).  fp32 -> fp16 rounds to nearest, ties to even   */
+/*     (a project choice: Vulkan allows either); a finite value at or above */
+/*     65520 in magnitude stores +-65504 (E10); a non-finite value stores   */
+/*     +0 and its texel is counted (E8).  Alpha is 1.                       */
+/*  E1 texel -> direction.  cx = (2.0f * (float(px) + 0.5f)) / float(n) -   */
+/*     1.0f, cy = 1.0f - (2.0f * (float(py) + 0.5f)) / float(n), and        */
+/*     in_local_pos = transpose(V) * (cx, cy, 1) of the layer's look_at_rh  */
+/*     matrix V (the loader pushes the bare view matrix: w = 1, the draw is */
+/*     orthographic, the clip removes view z < 0 and the viewport's height  */
+/*     is negative), which is per layer                                     */
+/*       0 (-1, cy, cx)   1 (1, cy, -cx)    2 (-cx, 1, cy)                  */
+/*       3 (-cx, -1, -cy) 4 (-cx, cy, -1)   5 (cx, cy, 1)                   */
+/*     Against Vulkan's face table this is the direction rotated by 180     */
+/*     degrees about Y: the reference's behaviour, kept.                    */
+/*  E2 equirect fetch (equirectangular_cube_map.frag).  v = normalize(      */
+/*     in_local_pos); u.x = atan2c(v.z, v.x) * 0.1591f + 0.5f, u.y = 1.0f - */
+/*     (asinc(v.y) * 0.3183f + 0.5f); LinearRepeat bilinear of level 0 of   */
+/*     the caller's fp32 RGBA panorama: s = u * size - 0.5f, floor, the two */
+/*     texel indices by integer remainder on both axes, B3's weights; then  */
+/*     clamp(rgb, 0, 10000) by the GLSL formula (NaN stays NaN: E0).  The   */
+/*     panorama's own mips are not read (a project choice).                 */
+/*  E3 sky mips.  Level m + 1 texel = ((t00 + t10) + (t01 + t11)) * 0.25f   */
+/*     of the 2 x 2 block of level m read back from its stored fp16, all    */
+/*     four channels.  sky_size is a power of two in 1 .. 4096; the chain   */
+/*     is full: log2(sky_size) + 1 levels.                                  */
+/*  E4 the cube sampler.  A direction with a non-finite component or all    */
+/*     three zero returns 0 and is counted.  The face is Vulkan's: z wins   */
+/*     ties over y and x, y over x; sc, tc, ma by the specification's       */
+/*     table; s = (0.5f * sc) / |ma| + 0.5f, t alike.  Per level of extent  */
+/*     n: x = s * n - 0.5f, i0 = floor(x), f = x - i0, i1 = i0 + 1 (both in */
+/*     -1 .. n), B3's expression (t00 * (1 - fx) + t10 * fx) * (1 - fy) +   */
+/*     (t01 * (1 - fx) + t11 * fx) * fy.  Seamless: a tap outside the face  */
+/*     in one axis is the texel of the adjoining face across that edge; a   */
+/*     tap outside in both axes is ((own + across x) + across y) / 3.0f of  */
+/*     the three corner texels.  lod: NaN and negative -> 0, above levels - */
+/*     1 -> levels - 1; l = floor(lod), f = lod - l; f == 0 reads level l   */
+/*     alone, else a * (1.0f - f) + b * f of levels l and l + 1.            */
+/*  E5 irradiance (cubemap_convolution.frag) as written: the two float loop */
+/*     counters advanced by fp32 += sample_delta against 2.0f * PI and 0.5f */
+/*     * PI; sampleVec = (x * right + y * up) + z * in_local_pos, the       */
+/*     unnormalised position; irradiance += (rgb * cos(theta)) * sin(theta);*/
+/*     (PI * irradiance) * (1.0f / nrSamples).  The lod of every tap is one */
+/*     constant per call, max(0, log2c(float(sky_size) / float(             */
+/*     irradiance_size))) (a project choice).  At an odd size the texel at  */
+/*     (0, +-1, 0) has a NaN frame: every tap is a bad direction by E4, the */
+/*     texel stores 0 and bad_directions counts its taps.                   */
+/*  E6 prefilter (environmental_map_prefilter.frag, functions.glsl) as      */
+/*     written, level m of extent max(1, n >> m) at roughness float(m) /    */
+/*     float(levels - 1) (0 when levels == 1): hammersley_2d,               */
+/*     importance_sample_ggx with phi = (2.0f * PI) * Xi.x + random(        */
+/*     normal.xz) * 0.1f, random's mod(dt, 3.14f) = dt - 3.14f * floor(dt / */
+/*     3.14f) and fract(x) = x - floor(x); L = (2.0f * dot(V, H)) * H - V;  */
+/*     pdf = (D * dotNH) / (4.0f * dotVH) + 0.0001f; omegaS = 1.0f / (float(*/
+/*     sample_count) * pdf); omegaP = (4.0f * PI) / ((6.0f * dim) * dim)    */
+/*     with dim = float(sky_size); mip = roughness == 0 ? 0 : max(0.5f *    */
+/*     log2c(omegaS / omegaP) + 1.0f, 0); color / totalWeight (0 / 0 = NaN: */
+/*     E0).  Sine and cosine are H6's routine, which holds on [-pi/4, 2 pi  */
+/*     + pi/4] (phi reaches 2 pi + 0.1).                                    */
+/*  E7 BRDF table (brdf_integration.frag) as written, with its own          */
+/*     importance_sample_ggx and geometry_smith.  Texel (x, y) has in_uv =  */
+/*     ((x + 0.5f) / n, (y + 0.5f) / n): blit.vert's uv.y = 1 - y and the   */
+/*     negative viewport height cancel.  R = A, G = B.                      */
+/*  E8 stats (may be NULL) is cleared by the call: per product the texels   */
+/*     with a non-finite channel, and the bad directions of E4 over every   */
+/*     tap of the call.                                                     */
+/*  E9 ORBIT_E_INVALID (message prefix env_map: / env_sample:) for a NULL   */
+/*     job; unknown flags; no product asked for; a product's size 0 or      */
+/*     above ORBIT_ENV_MAX_SIZE; a sky size that is not a power of two;     */
+/*     prefiltered_levels 0 or above ORBIT_ENV_MAX_LEVELS; sample_count or  */
+/*     brdf_sample_count 0 or above ORBIT_ENV_MAX_SAMPLES where its product */
+/*     is made; sample_delta non-finite or below 0.005f, which covers <= 0  */
+/*     (a thread runs its texel's trips one after the other: 0.005 is 1 257 */
+/*     x 315 of them, 25 times the reference's, and bounds the launch; a    */
+/*     step below fp32's spacing at 2 pi would never end the loop);         */
+/*     irradiance or prefiltered without a sky cube; an equirect of width   */
+/*     or height 0 or above 65 536; a plane not aligned (equirect 16 B,     */
+/*     cubes and stats 8 B, table 4 B); two of the call's buffers sharing a */
+/*     byte, by the sizes the layout call gives (for the sample call: rgb   */
+/*     or the counter sharing a byte with the cube, the directions, the     */
+/*     lods or each other).  A NULL context.                                */
+/* E10 a finite value beyond fp16's range stores the largest finite fp16.   */
+/* E11 the distance of every product from the GLSL in float64 is measured,  */
+/*     not bounded (tools/count_env_map.py, profiles/env_map_cpu.json).     */
+/* E12 abs(N.z) < 0.999 compares against the fp32 literal 0.999f.           */
+/*                                                                          */
+/* Each product is optional (NULL: not made).  With equirect the sky cube   */
+/* is written and then read by the later products; with equirect NULL the   */
+/* caller's sky cube (all its levels, E0) is read.  Launches: one clears    */
+/* the counters, one per sky face set, one per sky mip, one for the         */
+/* irradiance cube, one per prefiltered level (a 256-thread workgroup takes */
+/* a 16 x 16 tile of one face; what depends on the sample alone is staged   */
+/* through LDS in chunks of 256 samples), one for the table.  No            */
+/* allocation, no host sync: capturable on the first call.                  */
+/* ------------------------------------------------------------------------ */
+#define ORBIT_ENV_MAX_SIZE 4096u     /* every cube's and the table's largest size */
+#define ORBIT_ENV_MAX_LEVELS 13u     /* log2(4096) + 1 */
+#define ORBIT_ENV_MAX_SAMPLES 65536u /* sample_count, brdf_sample_count */
+typedef struct OrbitEnvMapLayout { /* HOST, 264 B; sizes and offsets in texels */
+    uint32_t sky_size, sky_levels, irradiance_size, prefiltered_size, prefiltered_levels, brdf_size;
+    uint32_t sky_level_size[ORBIT_ENV_MAX_LEVELS], sky_level_offset[ORBIT_ENV_MAX_LEVELS]; /* 0 beyond sky_levels */
+    uint32_t prefiltered_level_size[ORBIT_ENV_MAX_LEVELS], prefiltered_level_offset[ORBIT_ENV_MAX_LEVELS];
+    uint64_t sky_texels, irradiance_texels, prefiltered_texels; /* 8-B texels */
+    uint64_t brdf_texels;                                       /* 4-B texels */
+} OrbitEnvMapLayout;
+ORBIT_STATIC_ASSERT(sizeof(OrbitEnvMapLayout) == 264, "EnvMapLayout is 264 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, sky_size) == 0, "sky_size @0");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, sky_levels) == 4, "sky_levels @4");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, irradiance_size) == 8, "irradiance_size @8");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, prefiltered_size) == 12, "prefiltered_size @12");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, prefiltered_levels) == 16, "prefiltered_levels @16");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, brdf_size) == 20, "brdf_size @20");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, sky_level_size) == 24, "sky_level_size @24");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, sky_level_offset) == 76, "sky_level_offset @76");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, prefiltered_level_size) == 128, "prefiltered_level_size @128");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, prefiltered_level_offset) == 180, "prefiltered_level_offset @180");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, sky_texels) == 232, "sky_texels @232");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, irradiance_texels) == 240, "irradiance_texels @240");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, prefiltered_texels) == 248, "prefiltered_texels @248");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapLayout, brdf_texels) == 256, "brdf_texels @256");
+typedef struct OrbitEnvMapStats { /* DEVICE, 48 B, 8-B aligned, cleared by the call (E8) */
+    uint64_t sky_nonfinite, irradiance_nonfinite, prefiltered_nonfinite, brdf_nonfinite, bad_directions, _pad;
+} OrbitEnvMapStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitEnvMapStats) == 48, "EnvMapStats is 48 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapStats, sky_nonfinite) == 0, "sky_nonfinite @0");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapStats, irradiance_nonfinite) == 8, "irradiance_nonfinite @8");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapStats, prefiltered_nonfinite) == 16, "prefiltered_nonfinite @16");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapStats, brdf_nonfinite) == 24, "brdf_nonfinite @24");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapStats, bad_directions) == 32, "bad_directions @32");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMapStats, _pad) == 40, "_pad @40");
+typedef struct OrbitEnvMap { /* HOST block, 96 B; every pointer a DEVICE pointer */
+    const float *equirect;   /* NULL (sky is the caller's), or equirect_w * equirect_h * 4 floats, 16-B aligned */
+    uint16_t *sky;           /* NULL, or OrbitEnvMapLayout.sky_texels * 4 halves: written with equirect, else read */
+    uint16_t *irradiance;    /* NULL, or irradiance_texels * 4 halves */
+    uint16_t *prefiltered;   /* NULL, or prefiltered_texels * 4 halves */
+    uint16_t *brdf;          /* NULL, or brdf_texels * 2 halves */
+    OrbitEnvMapStats *stats; /* NULL, or the counters */
+    uint32_t equirect_w, equirect_h;
+    uint32_t sky_size, irradiance_size, prefiltered_size, prefiltered_levels, brdf_size; /* the layout call's */
+    uint32_t sample_count;      /* E6; the reference: 4096 */
+    float sample_delta;         /* E5; the reference: 0.025 */
+    uint32_t brdf_sample_count; /* E7; the reference: 1024 */
+    uint32_t flags, _pad;       /* 0 */
+} OrbitEnvMap;
+ORBIT_STATIC_ASSERT(sizeof(OrbitEnvMap) == 96, "EnvMap is 96 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, equirect) == 0, "equirect @0");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, sky) == 8, "sky @8");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, irradiance) == 16, "irradiance @16");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, prefiltered) == 24, "prefiltered @24");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, brdf) == 32, "brdf @32");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, stats) == 40, "stats @40");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, equirect_w) == 48, "equirect_w @48");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, equirect_h) == 52, "equirect_h @52");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, sky_size) == 56, "sky_size @56");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, irradiance_size) == 60, "irradiance_size @60");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, prefiltered_size) == 64, "prefiltered_size @64");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, prefiltered_levels) == 68, "prefiltered_levels @68");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, brdf_size) == 72, "brdf_size @72");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, sample_count) == 76, "sample_count @76");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, sample_delta) == 80, "sample_delta @80");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, brdf_sample_count) == 84, "brdf_sample_count @84");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, flags) == 88, "flags @88");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvMap, _pad) == 92, "_pad @92");
+typedef struct OrbitEnvSample { /* HOST block, 56 B; every pointer a DEVICE pointer */
+    const uint16_t *cube;     /* a cube in E0's layout, 8-B aligned */
+    const float *directions;  /* n * 3 floats */
+    const float *lods;        /* n floats */
+    float *rgb;               /* n * 3 floats */
+    uint64_t *bad_directions; /* NULL, or one counter, cleared by the call */
+    uint32_t size, levels;    /* the cube's: level m has extent max(1, size >> m) */
+    uint32_t n, flags;        /* flags: 0 */
+} OrbitEnvSample;
+ORBIT_STATIC_ASSERT(sizeof(OrbitEnvSample) == 56, "EnvSample is 56 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvSample, cube) == 0, "cube @0");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvSample, directions) == 8, "directions @8");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvSample, lods) == 16, "lods @16");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvSample, rgb) == 24, "rgb @24");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvSample, bad_directions) == 32, "bad_directions @32");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvSample, size) == 40, "size @40");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvSample, levels) == 44, "levels @44");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvSample, n) == 48, "n @48");
+ORBIT_STATIC_ASSERT(offsetof(OrbitEnvSample, flags) == 52, "flags @52");
+
+/* E0's shape (host only).  A size of 0 leaves its product out (its fields 0).  ORBIT_E_INVALID for a NULL out, a size
+ * above ORBIT_ENV_MAX_SIZE, a sky size that is not a power of two, prefiltered_levels 0 (with a prefiltered size) or above
+ * ORBIT_ENV_MAX_LEVELS. */
+int32_t orbit_env_map_layout(uint32_t sky_size, uint32_t irradiance_size, uint32_t prefiltered_size, uint32_t prefiltered_levels,
+                             uint32_t brdf_size, OrbitEnvMapLayout *out);
+/* the sky cube, the irradiance cube, the prefiltered cube and the BRDF table; see above */
+int32_t orbit_env_map(OrbitCtx *ctx, const OrbitEnvMap *job, void *stream);
+/* E4 of n directions and lods of a cube in E0's layout (size 1 .. ORBIT_ENV_MAX_SIZE, levels 1 .. ORBIT_ENV_MAX_LEVELS);
+ * n == 0 is a call that only clears the counter */
+int32_t orbit_env_sample(OrbitCtx *ctx, const OrbitEnvSample *job, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -261,6 +261,38 @@ def fill_ssao(j, projection, inverse_projection, screen_w, screen_h, ssao_w, ssa
     j.min_radius, j.max_radius, j.flags = float(min_radius), float(max_radius), int(flags)
 
 
+ENV_MAX_SIZE, ENV_MAX_LEVELS, ENV_MAX_SAMPLES = 4096, 13, 65536  # ORBIT_ENV_MAX_*
+
+
+class EnvMapLayout(C.Structure):  # OrbitEnvMapLayout (264 B)
+    _fields_ = [("sky_size", C.c_uint32), ("sky_levels", C.c_uint32), ("irradiance_size", C.c_uint32), ("prefiltered_size", C.c_uint32),
+                ("prefiltered_levels", C.c_uint32), ("brdf_size", C.c_uint32), ("sky_level_size", C.c_uint32 * ENV_MAX_LEVELS),
+                ("sky_level_offset", C.c_uint32 * ENV_MAX_LEVELS), ("prefiltered_level_size", C.c_uint32 * ENV_MAX_LEVELS),
+                ("prefiltered_level_offset", C.c_uint32 * ENV_MAX_LEVELS), ("sky_texels", C.c_uint64), ("irradiance_texels", C.c_uint64),
+                ("prefiltered_texels", C.c_uint64), ("brdf_texels", C.c_uint64)]
+
+
+class EnvMap(C.Structure):  # OrbitEnvMap (96 B)
+    _fields_ = [("equirect", C.c_void_p), ("sky", C.c_void_p), ("irradiance", C.c_void_p), ("prefiltered", C.c_void_p), ("brdf", C.c_void_p),
+                ("stats", C.c_void_p), ("equirect_w", C.c_uint32), ("equirect_h", C.c_uint32), ("sky_size", C.c_uint32),
+                ("irradiance_size", C.c_uint32), ("prefiltered_size", C.c_uint32), ("prefiltered_levels", C.c_uint32), ("brdf_size", C.c_uint32),
+                ("sample_count", C.c_uint32), ("sample_delta", C.c_float), ("brdf_sample_count", C.c_uint32), ("flags", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+class EnvSample(C.Structure):  # OrbitEnvSample (56 B)
+    _fields_ = [("cube", C.c_void_p), ("directions", C.c_void_p), ("lods", C.c_void_p), ("rgb", C.c_void_p), ("bad_directions", C.c_void_p),
+                ("size", C.c_uint32), ("levels", C.c_uint32), ("n", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def fill_env_map(j, equirect_w, equirect_h, sky_size, irradiance_size, prefiltered_size, prefiltered_levels, brdf_size, sample_count,
+                 sample_delta, brdf_sample_count, flags=0):
+    """The by-value fields of an OrbitEnvMap."""
+    j.equirect_w, j.equirect_h, j.sky_size, j.irradiance_size = int(equirect_w), int(equirect_h), int(sky_size), int(irradiance_size)
+    j.prefiltered_size, j.prefiltered_levels, j.brdf_size = int(prefiltered_size), int(prefiltered_levels), int(brdf_size)
+    j.sample_count, j.sample_delta, j.brdf_sample_count, j.flags = int(sample_count), float(sample_delta), int(brdf_sample_count), int(flags)
+
+
 class ClusterFrame(C.Structure):  # OrbitClusterFrame
     _fields_ = [("push", C.c_void_p), ("info", C.c_void_p), ("depth", C.c_void_p), ("lights", C.c_void_p),
                 ("tile_depth_slice_mask", C.c_void_p), ("depth_bounds", C.c_void_p), ("unique_cluster_buffer", C.c_void_p),
@@ -373,6 +405,9 @@ SYMBOLS = {
     "orbit_bloom": (C.c_int32, [C.c_void_p, C.POINTER(Bloom), C.c_void_p]),
     "orbit_post_process": (C.c_int32, [C.c_void_p, C.POINTER(PostProcess), C.c_void_p]),
     "orbit_ssao": (C.c_int32, [C.c_void_p, C.POINTER(Ssao), C.c_void_p]),
+    "orbit_env_map_layout": (C.c_int32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(EnvMapLayout)]),
+    "orbit_env_map": (C.c_int32, [C.c_void_p, C.POINTER(EnvMap), C.c_void_p]),
+    "orbit_env_sample": (C.c_int32, [C.c_void_p, C.POINTER(EnvSample), C.c_void_p]),
 }
 
 _lib = None

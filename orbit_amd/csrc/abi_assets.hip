@@ -12,6 +12,7 @@
 // reference's ambient occlusion of the depth plane (ssao.hip).
 #include "abi_internal.h"
 #include "post_common.h" // bloom_layout
+#include "env_common.h"  // env_layout, env_map_check, env_sample_check
 
 namespace {
 
@@ -474,6 +475,45 @@ int32_t orbit_ssao(OrbitCtx *ctx, const OrbitSsao *job, void *stream) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_ssao(j, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch ssao");
+    return ORBIT_OK;
+}
+
+// E0's shape: host only, no context
+int32_t orbit_env_map_layout(uint32_t sky_size, uint32_t irradiance_size, uint32_t prefiltered_size, uint32_t prefiltered_levels,
+                             uint32_t brdf_size, OrbitEnvMapLayout *out) {
+    if (!out) return fail(nullptr, ORBIT_E_INVALID, "env_map_layout: out is NULL");
+    if (sky_size > ORBIT_ENV_MAX_SIZE || irradiance_size > ORBIT_ENV_MAX_SIZE || prefiltered_size > ORBIT_ENV_MAX_SIZE || brdf_size > ORBIT_ENV_MAX_SIZE)
+        return fail(nullptr, ORBIT_E_INVALID, "env_map_layout: sizes %u, %u, %u, %u (each at most %u)", sky_size, irradiance_size, prefiltered_size, brdf_size, ORBIT_ENV_MAX_SIZE);
+    if (sky_size != 0u && !orbit::raster::env_power_of_two(sky_size)) return fail(nullptr, ORBIT_E_INVALID, "env_map_layout: sky_size %u is not a power of two", sky_size);
+    if (prefiltered_size != 0u && (prefiltered_levels == 0u || prefiltered_levels > ORBIT_ENV_MAX_LEVELS))
+        return fail(nullptr, ORBIT_E_INVALID, "env_map_layout: prefiltered_levels %u (1..%u)", prefiltered_levels, ORBIT_ENV_MAX_LEVELS);
+    orbit::raster::env_layout(sky_size, irradiance_size, prefiltered_size, prefiltered_levels, brdf_size, *out);
+    return ORBIT_OK;
+}
+
+// A launch that starts the counters and the launches of the products asked for (env_map.hip).  No allocation, no scratch,
+// no host sync: capturable on the first call.  As its siblings, the job is checked before the context is looked at; the
+// checks are env_common.h's, the host mirror's too.
+int32_t orbit_env_map(OrbitCtx *ctx, const OrbitEnvMap *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "env_map: job is NULL");
+    const char *wrong = orbit::raster::env_map_check(*job);
+    if (wrong) return fail(ctx, ORBIT_E_INVALID, "env_map: %s", wrong);
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "env_map: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_env_map(*job, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch env_map");
+    return ORBIT_OK;
+}
+
+// E4 of n directions: a clearing launch and one thread per direction; as orbit_env_map otherwise.
+int32_t orbit_env_sample(OrbitCtx *ctx, const OrbitEnvSample *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "env_sample: job is NULL");
+    const char *wrong = orbit::raster::env_sample_check(*job);
+    if (wrong) return fail(ctx, ORBIT_E_INVALID, "env_sample: %s", wrong);
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "env_sample: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_env_sample(*job, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch env_sample");
     return ORBIT_OK;
 }
 

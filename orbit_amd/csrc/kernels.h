@@ -470,6 +470,12 @@ hipError_t launch_post_process(const OrbitPostProcess &job, uint32_t num_cus, ui
 // ssao.hip: orbit_ssao — `job` validated by the entry point.  One launch starts the counters, then the SSAO launch (a 16 x
 // 16 tile per workgroup), the blur and the fragment read where their outputs are wanted, ordered by the stream.
 hipError_t launch_ssao(const OrbitSsao &job, hipStream_t s);
+// env_map.hip: orbit_env_map and orbit_env_sample — `job` validated by the entry point (env_common.h env_map_check /
+// env_sample_check).  One launch starts the counters, then the equirect launch and one per sky mip, the irradiance launch,
+// one prefilter launch per level (a 16 x 16 tile of one face per workgroup) and the table launch, each for a product that
+// is asked for; the sample call is a clearing launch and one thread per direction.
+hipError_t launch_env_map(const OrbitEnvMap &job, hipStream_t s);
+hipError_t launch_env_sample(const OrbitEnvSample &job, hipStream_t s);
 // cull_stats.hip: orbit_cull_stats — the counts of entity cull `e` followed by meshlet cull `m` (S = 32; m reads the
 // Meshlet buffer, its dispatch buffer is never read) into `stats`, cleared on the stream first
 struct CullStatsParams {

@@ -11,6 +11,7 @@
 #include "orbit_gltf.hpp"
 #include "orbit_raster.hpp"
 #include "orbit_post.hpp"
+#include "orbit_env_map.hpp"
 #include "orbit_ssao.hpp"
 #include "orbit_scene.hpp"
 #include "../csrc/block_pretest.h"
@@ -663,6 +664,27 @@ int32_t orbit_host_ssao(const OrbitSsao *job, uint64_t *census) {
         raster::ssao(*job, census);
     });
 }
+int32_t orbit_host_env_map(const OrbitEnvMap *job, uint64_t *census) {
+    return guarded([&] {
+        if (!job) throw Panic("env_map: job is NULL");
+        raster::env_map(*job, census);
+    });
+}
+int32_t orbit_host_env_sample(const OrbitEnvSample *job, uint64_t *census) {
+    return guarded([&] {
+        if (!job) throw Panic("env_sample: job is NULL");
+        raster::env_sample_job(*job, census);
+    });
+}
+int32_t orbit_host_env_prefilter_texels(const OrbitEnvMap *job, uint32_t level, const uint32_t *texels, uint32_t count, uint16_t *out) {
+    return guarded([&] {
+        if (!job || !texels || !out) throw Panic("env_prefilter_texels: NULL argument");
+        raster::env_prefilter_texels(*job, level, texels, count, out);
+    });
+}
+// the pieces of csrc/env_common.h, for tests
+void orbit_host_env_direction(uint32_t face, uint32_t px, uint32_t py, uint32_t n, float *out) { raster::env_direction(face, px, py, n, out); }
+void orbit_host_env_routines(uint32_t which, const float *a, const float *b, uint64_t n, float *out) { raster::env_routines(which, a, b, n, out); }
 // the pieces of csrc/ssao_common.h, for tests
 void orbit_host_ssao_table(const uint8_t *samples, uint32_t samples_size, uint32_t sample_count, float min_radius, float max_radius, float *table) {
     raster::ssao_table(samples, samples_size, sample_count, min_radius, max_radius, table);

@@ -284,6 +284,23 @@ void orbit_host_bloom_upsample_floats(const float *src, uint32_t src_w, uint32_t
  * sample_depth == proj.z, pixels with a horizontal and with a vertical tie of A2, in-range samples with a component
  * exactly 0 and exactly 1, rejected samples with a component one step below 0 and one above 1. */
 int32_t orbit_host_ssao(const OrbitSsao *job, uint64_t *census);
+/* the reference of orbit_env_map and orbit_env_sample (E0-E12): the device calls' blocks with HOST pointers in them; every
+ * output holds the device's bytes.  census (may be NULL): ORBIT_HOST_ENV_CENSUS counters over every tap of the call — by
+ * index 0-5 the sampled directions whose major axis is each layer; 6-29 the taps outside their face in one axis, by layer
+ * * 4 + side (0 left, 1 right, 2 above, 3 below); 30-53 the taps outside in both, by layer * 4 + corner (bit 0 right, bit
+ * 1 below); 54 / 55 prefilter texels whose abs(N.z) < 0.999 is true / false; 56 prefilter samples with dotNL <= 0; 57
+ * prefilter texels at roughness 0; 58 prefilter texels with totalWeight == 0; 59 irradiance texels with a NaN frame; 60
+ * sampled directions mixed from two levels; 61-63 zero. */
+#define ORBIT_HOST_ENV_CENSUS 64
+int32_t orbit_host_env_map(const OrbitEnvMap *job, uint64_t *census);
+int32_t orbit_host_env_sample(const OrbitEnvSample *job, uint64_t *census);
+/* tools: count texels (face * n * n + py * n + px) of level `level` of the job's prefiltered cube, from the job's sky cube
+ * as it is; out: count 8-B texels.  What a full-size run is verified against where the whole mirror would take hours. */
+int32_t orbit_host_env_prefilter_texels(const OrbitEnvMap *job, uint32_t level, const uint32_t *texels, uint32_t count, uint16_t *out);
+/* tests: E1 of one texel (three floats); the routines over n values — which = 0: atan2c(a, b), 1: asinc(a), 2 / 3: the
+ * sine / cosine of H6's routine at a, 4: E0's stored half of a read back as a float (NaN where a is not finite) */
+void orbit_host_env_direction(uint32_t face, uint32_t px, uint32_t py, uint32_t n, float *out);
+void orbit_host_env_routines(uint32_t which, const float *a, const float *b, uint64_t n, float *out);
 /* tests: A4's table (sample_count x 4 floats: direction, radius), A5's range test of n (x, y, z) triples and its
  * range_check of n (min_radius, sample_depth, proj.w) triples */
 void orbit_host_ssao_table(const uint8_t *samples, uint32_t samples_size, uint32_t sample_count, float min_radius, float max_radius, float *table);

@@ -82,6 +82,9 @@ BLOOM_STATS = np.dtype([(n, "<u4") for n in ("levels", "texels_written", "nonfin
 POST_STATS = np.dtype([(n, "<u4") for n in ("pixels", "nonfinite_pixels", "bloom_pixels", "_pad")])
 # OrbitSsaoStats: the counters of orbit_ssao (24 B)
 SSAO_STATS = np.dtype([(n, "<u4") for n in ("pixels", "nonfinite_pixels", "unoccluded_pixels", "_pad")] + [("samples_in_range", "<u8")])
+# OrbitEnvMapStats: the counters of orbit_env_map (48 B)
+ENV_MAP_STATS = np.dtype([(n, "<u8") for n in ("sky_nonfinite", "irradiance_nonfinite", "prefiltered_nonfinite", "brdf_nonfinite",
+                                               "bad_directions", "_pad")])
 # OrbitShadowData, types.glsl:29-33 in std430 (288 B): the matrices column-major
 SHADOW_DATA = np.dtype([("light_projection_matrices", "<f4", (4, 16)), ("shadow_map_world_sizes", "<f4", (4,)),
                         ("shadow_map_indices", "<u4", (4,))])
