@@ -349,6 +349,29 @@ pub struct OrbitSsao {
     pub min_radius: f32, pub max_radius: f32, pub flags: u32,
 }
 
+/// The counters orbit_fragments_shade_sky adds (32 B, DEVICE, 8-B aligned, cleared by the call; rule K10): SKY lights
+/// evaluated over written pixels, written pixels with at least one, pixels the skybox wrote, E4's bad directions over every
+/// cube sample of the call
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct OrbitSkyStats {
+    pub sky_evaluations: u32, pub sky_lit_pixels: u32, pub skybox_pixels: u32, pub _pad: u32,
+    pub bad_directions: u64, pub _pad2: u64,
+}
+
+/// orbit_fragments_shade_sky's argument block (344 B, HOST): an OrbitFragmentsShadeShadowed, then the environment
+/// (irradiance, prefiltered and brdf as orbit_env_map writes them: all three or none), the sky cube (null: no skybox),
+/// the ao plane (null, or orbit_ssao's ao_pixel), the counters (may be null), the images' sizes and level counts, the
+/// skybox's constant lod and K9's ray basis (orbit_host_skybox_basis)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct OrbitFragmentsShadeSky {
+    pub shadowed: OrbitFragmentsShadeShadowed,
+    pub irradiance: *const u16, pub prefiltered: *const u16, pub brdf: *const u16, pub sky: *const u16,
+    pub ao: *const f32, pub sky_stats: *mut OrbitSkyStats,
+    pub irradiance_size: u32, pub prefiltered_size: u32, pub prefiltered_levels: u32, pub brdf_size: u32,
+    pub sky_size: u32, pub sky_levels: u32, pub skybox_lod: f32,
+    pub sky_x: [f32; 3], pub sky_y: [f32; 3], pub sky_z: [f32; 3],
+}
+
 /// orbit_env_map_layout's answer (264 B, HOST): sizes and offsets in texels of the sky cube's full chain and the
 /// prefiltered cube's levels (8-B texels), the irradiance cube and the BRDF table (4-B texels); rule E0
 #[repr(C)] #[derive(Clone, Copy)]
@@ -622,6 +645,8 @@ extern "C" {
     /// compute_ssao of the depth plane (A1-A9): raw, its blur, and what forward.frag reads of the blur per pixel.
     pub fn orbit_ssao(ctx: *mut OrbitCtx, job: *const OrbitSsao, stream: *mut c_void) -> i32;
     /// The shape of the sky, irradiance and prefiltered cubes and the BRDF table (host only; E0).
+    /// forward.frag's clustered lighting with shadows, the sky light's term and the skybox (rules K1-K10)
+    pub fn orbit_fragments_shade_sky(ctx: *mut OrbitCtx, job: *const OrbitFragmentsShadeSky, stream: *mut c_void) -> i32;
     pub fn orbit_env_map_layout(sky_size: u32, irradiance_size: u32, prefiltered_size: u32, prefiltered_levels: u32, brdf_size: u32,
                                 out: *mut OrbitEnvMapLayout) -> i32;
     /// EnvironmentMap::new and the BRDF table of forward.rs:113-205 (E0-E12): every product that is not null.

@@ -2378,6 +2378,131 @@ int32_t orbit_env_map(OrbitCtx *ctx, const OrbitEnvMap *job, void *stream);
  * n == 0 is a call that only clears the counter */
 int32_t orbit_env_sample(OrbitCtx *ctx, const OrbitEnvSample *job, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* The sky light's term and the skybox.  orbit_fragments_shade_sky is       */
+/* orbit_fragments_shade_shadowed with two additions: L5's SKY branch is    */
+/* served (forward.frag:378-405) from the images orbit_env_map writes, and  */
+/* the uncovered pixels are filled from the sky cube (skybox.vert /         */
+/* skybox.frag, forward.rs:471-472, 629-682).  ONE definition for the       */
+/* device and the host mirror (orbit_host_fragments_shade_sky,              */
+/* csrc/sky_common.h); the two agree on every byte.  The job starts with an */
+/* OrbitFragmentsShadeShadowed: same meaning, same checks.  Arithmetic as   */
+/* in L: fp32, every operation rounded on its own, never contracted, IEEE   */
+/* '/', GLSL max / min / clamp by their formulas, dot as L's left-to-right  */
+/* sum.  The irradiance cube, the prefiltered cube and the BRDF table are   */
+/* THE ENVIRONMENT: given together or not at all.  DESIGN.md §4.31.         */
+/*  K1 which lights.  With the environment given, a SKY light of a pixel's  */
+/*     walk is evaluated in list position, as often as it occurs, and no    */
+/*     longer counts the pixel in unserved_pixels.  With the environment    */
+/*     NULL it is skipped and counted exactly as by the shadowed call.  The */
+/*     light's irradiance_map_index and prefiltered_map_index are not read: */
+/*     a call has one environment, as the reference has one                 */
+/*     environment_map.                                                     */
+/*  K2 the reflection vector.  R = V - (2 * dot(N, V)) * N: GLSL            */
+/*     reflect(view_direction, normal) with the view direction as the       */
+/*     incident vector, the reference's expression, kept.  Then R.y = R.y * */
+/*     -1.                                                                  */
+/*  K3 Fresnel with roughness.  ndv0 = max(dot(N, V), 0); f0 is L6's; x =   */
+/*     clamp(1 - ndv0, 0, 1); p5 = ((x * x) * (x * x)) * x (L6's choice for */
+/*     pow(., 5)); kS_c = f0_c + (max(1 - roughness, f0_c) - f0_c) * p5;    */
+/*     kD_c = (1 - kS_c) * (1 - metallic).                                  */
+/*  K4 diffuse.  irr = E4's sample of the irradiance cube (one level) at N, */
+/*     lod 0, the seamless fold and the corner mean included; diffuse_c =   */
+/*     irr_c * base_c.                                                      */
+/*  K5 reflection.  lod = roughness * float(prefiltered_levels - 1); refl = */
+/*     E4's sample of the prefiltered cube at R and lod (E4 clamps NaN,     */
+/*     negative and too-large lods).                                        */
+/*  K6 the BRDF table.  env = table(ndv0, roughness) under the reference's  */
+/*     default LinearClamp sampler: per axis s = u * n - 0.5, i0 = floor(s),*/
+/*     f = s - i0, i1 = i0 + 1; both indices converted saturating with NaN  */
+/*     -> 0 and clamped to [0, n - 1]; B3's expression (t00 * (1 - fx) +    */
+/*     t10 * fx) * (1 - fy) + (t01 * (1 - fx) + t11 * fx) * fy on the       */
+/*     stored fp16 pair.  u = ndv0 indexes a row's texels, v = roughness    */
+/*     the rows (E7).                                                       */
+/*  K7 the term.  spec_c = refl_c * (kS_c * env.x + env.y); term_c = ((kD_c */
+/*     * diffuse_c + spec_c) * lc_c) * ao, lc = color * intensity as in L5; */
+/*     light_sum_c = light_sum_c + term_c.                                  */
+/*  K8 ambient occlusion.  ao = 1.0f with the plane NULL; otherwise min(    */
+/*     1.0f, ao[p]) by GLSL's min (y < x ? y : x: NaN gives 1): what        */
+/*     orbit_ssao writes as ao_pixel.  ao scales the sky term only, as in   */
+/*     the shader.  Occlusion textures are not served and are counted in    */
+/*     textured_pixels as before.                                           */
+/*  K9 the skybox.  With sky given and render_mode 0, a pixel whose         */
+/*     visibility word is 0 (the reference's EQUAL test against the cleared */
+/*     reverse-z depth at gl_Position.z = 0) gets color[p] = (E4's sample   */
+/*     of the sky cube at normalize(d) and skybox_lod, 1.0f), d = (cx *     */
+/*     sky_x + cy * sky_y) + sky_z per component, cx = (2 * (x + 0.5)) /    */
+/*     width - 1, cy = 1 - (2 * (y + 0.5)) / height (the sign follows the   */
+/*     negative viewport height, as in E1).  The caller derives the basis   */
+/*     from skybox_view_projection_matrix; for the reference's              */
+/*     perspective_infinite_reverse_rh camera with orientation R: sky_x = R */
+/*     e_x / P00, sky_y = R e_y / P11, sky_z = -R e_z                       */
+/*     (orbit_host_skybox_basis).  TWO PROJECT CHOICES: the ray is          */
+/*     evaluated at the pixel centre, and the lod is one constant per call  */
+/*     where the shader's implicit lod depends on the driver's derivatives  */
+/*     (E5's choice).  A bad direction (E4) stores 0 and is counted.        */
+/*     Covered pixels are never touched by K9.  With sky NULL, or in        */
+/*     render_mode 8, uncovered pixels are left as by the shadowed call.    */
+/* K10 everything else.  L8 (no non-finite bytes), L9 and H1-H10 hold       */
+/*     unchanged; every output depends on its own pixel only.  With the     */
+/*     environment NULL and sky NULL, color, lights_walked, shadow_factor,  */
+/*     cascade and all stats equal orbit_fragments_shade_shadowed's byte    */
+/*     for byte.  In render_mode 8 nothing of K is evaluated.  sky_stats,   */
+/*     cleared by the call: sky_evaluations = SKY lights evaluated over     */
+/*     written pixels; sky_lit_pixels = written pixels with at least one;   */
+/*     skybox_pixels = pixels K9 wrote; bad_directions = E4's bad           */
+/*     directions over every cube sample of the call (K4, K5 and K9; those  */
+/*     of K4 / K5 over written pixels).                                     */
+/* OUT OF SCOPE: material textures, occlusion textures included; render     */
+/* modes 1-7 and 9; MSAA and hdr_resolve; an orthographic camera's skybox;  */
+/* more than one environment per call; a hardware sampler's fixed-point     */
+/* weights; derivative-driven lod for the skybox.                           */
+/*   ORBIT_E_INVALID  (message prefix fragments_shade_sky:) everything      */
+/*                    orbit_fragments_shade_shadowed rejects; an            */
+/*                    environment given only in part; a size of 0 or above  */
+/*                    ORBIT_ENV_MAX_SIZE; prefiltered_levels or sky_levels  */
+/*                    of 0 or above ORBIT_ENV_MAX_LEVELS; a cube or         */
+/*                    sky_stats not 8-B aligned, the table or ao not 4-B    */
+/*                    aligned; a non-finite skybox_lod; an output sharing a */
+/*                    byte with an input, by the ranges the sizes give.     */
+/*                    All checked before the context is looked at, by the   */
+/*                    function the mirror uses.                             */
+/* Kernel launches only: no allocation, no scratch, no host wait; a graph   */
+/* captures the call on a fresh context's first call.                       */
+/* ------------------------------------------------------------------------ */
+typedef struct OrbitSkyStats { /* DEVICE, 32 B, 8-B aligned, cleared by the call (K10) */
+    uint32_t sky_evaluations, sky_lit_pixels, skybox_pixels, _pad;
+    uint64_t bad_directions, _pad2;
+} OrbitSkyStats;
+ORBIT_STATIC_ASSERT(sizeof(OrbitSkyStats) == 32, "SkyStats is 32 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSkyStats, skybox_pixels) == 8, "skybox_pixels @8");
+ORBIT_STATIC_ASSERT(offsetof(OrbitSkyStats, bad_directions) == 16, "bad_directions @16");
+typedef struct OrbitFragmentsShadeSky { /* HOST block, 344 B; every pointer a DEVICE pointer */
+    OrbitFragmentsShadeShadowed shadowed; /* as orbit_fragments_shade_shadowed takes it */
+    const uint16_t *irradiance;           /* NULL, or level 0 of a cube in E0's layout, 8-B aligned */
+    const uint16_t *prefiltered;          /* NULL, or prefiltered_levels levels in E0's layout, 8-B aligned */
+    const uint16_t *brdf;                 /* NULL, or brdf_size^2 R16G16_SFLOAT texels, 4-B aligned */
+    const uint16_t *sky;                  /* NULL (no skybox), or sky_levels levels in E0's layout, 8-B aligned */
+    const float *ao;                      /* NULL, or 1 float per pixel (orbit_ssao's ao_pixel) */
+    OrbitSkyStats *sky_stats;             /* NULL, or the counters */
+    uint32_t irradiance_size, prefiltered_size, prefiltered_levels, brdf_size;
+    uint32_t sky_size, sky_levels;
+    float skybox_lod;
+    float sky_x[3], sky_y[3], sky_z[3]; /* K9's ray basis */
+} OrbitFragmentsShadeSky;
+ORBIT_STATIC_ASSERT(sizeof(OrbitFragmentsShadeSky) == 344, "FragmentsShadeSky is 344 B");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeSky, irradiance) == 232, "irradiance @232");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeSky, sky) == 256, "sky @256");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeSky, sky_stats) == 272, "sky_stats @272");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeSky, irradiance_size) == 280, "irradiance_size @280");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeSky, sky_size) == 296, "sky_size @296");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeSky, skybox_lod) == 304, "skybox_lod @304");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeSky, sky_x) == 308, "sky_x @308");
+ORBIT_STATIC_ASSERT(offsetof(OrbitFragmentsShadeSky, sky_z) == 332, "sky_z @332");
+
+/* forward.frag's clustered lighting with shadows, the sky light's term and the skybox; see above */
+int32_t orbit_fragments_shade_sky(OrbitCtx *ctx, const OrbitFragmentsShadeSky *job, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

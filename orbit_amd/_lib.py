@@ -200,6 +200,25 @@ def fill_shadow_fields(j, shadow_count, shadow_index_base, shadow_map_count, sha
     j.blocker_search_radius, j.normal_bias_scale, j.oriented_bias = float(blocker_search_radius), float(normal_bias_scale), float(oriented_bias)
 
 
+class FragmentsShadeSky(C.Structure):  # OrbitFragmentsShadeSky (344 B)
+    _fields_ = [("shadowed", FragmentsShadeShadowed), ("irradiance", C.c_void_p), ("prefiltered", C.c_void_p), ("brdf", C.c_void_p),
+                ("sky", C.c_void_p), ("ao", C.c_void_p), ("sky_stats", C.c_void_p), ("irradiance_size", C.c_uint32),
+                ("prefiltered_size", C.c_uint32), ("prefiltered_levels", C.c_uint32), ("brdf_size", C.c_uint32), ("sky_size", C.c_uint32),
+                ("sky_levels", C.c_uint32), ("skybox_lod", C.c_float), ("sky_x", C.c_float * 3), ("sky_y", C.c_float * 3),
+                ("sky_z", C.c_float * 3)]
+
+
+def fill_sky_fields(j, irradiance_size=0, prefiltered_size=0, prefiltered_levels=0, brdf_size=0, sky_size=0, sky_levels=0, skybox_lod=0.0,
+                    basis=None):
+    """The by-value sky fields of an OrbitFragmentsShadeSky; basis: K9's (sky_x, sky_y, sky_z), three floats each, or None
+    (zeros)."""
+    j.irradiance_size, j.prefiltered_size, j.prefiltered_levels = int(irradiance_size), int(prefiltered_size), int(prefiltered_levels)
+    j.brdf_size, j.sky_size, j.sky_levels, j.skybox_lod = int(brdf_size), int(sky_size), int(sky_levels), float(skybox_lod)
+    if basis is not None:
+        for field, v in zip((j.sky_x, j.sky_y, j.sky_z), basis):
+            field[:] = [float(c) for c in v]
+
+
 BLOOM_MAX_LEVELS = 6                                # ORBIT_BLOOM_MAX_LEVELS
 BLOOM_FORCE_PER_LEVEL, BLOOM_FORCE_DIRECT = 1, 4    # ORBIT_BLOOM_FORCE_PER_LEVEL, ORBIT_BLOOM_FORCE_DIRECT (2 is no flag)
 POST_BGRA = 1                                       # ORBIT_POST_BGRA
@@ -401,6 +420,7 @@ SYMBOLS = {
     "orbit_surface_fragments": (C.c_int32, [C.c_void_p, C.POINTER(SurfaceFragments), C.c_void_p]),
     "orbit_fragments_shade": (C.c_int32, [C.c_void_p, C.POINTER(FragmentsShade), C.c_void_p]),
     "orbit_fragments_shade_shadowed": (C.c_int32, [C.c_void_p, C.POINTER(FragmentsShadeShadowed), C.c_void_p]),
+    "orbit_fragments_shade_sky": (C.c_int32, [C.c_void_p, C.POINTER(FragmentsShadeSky), C.c_void_p]),
     "orbit_bloom_layout": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(BloomLayout)]),
     "orbit_bloom": (C.c_int32, [C.c_void_p, C.POINTER(Bloom), C.c_void_p]),
     "orbit_post_process": (C.c_int32, [C.c_void_p, C.POINTER(PostProcess), C.c_void_p]),

@@ -28,3 +28,11 @@ def frame_cull_info(position, n_planes=5, fov_deg=90.0, aspect=16.0 / 9.0, z_nea
     planes = passes.frustum_planes_from_matrix(proj)[:n_planes]
     host_ci = passes.CullInfo(view, planes, projection, aspect_ratio=aspect, **cull_info_fields)
     return passes.cull_info_to_gpu(host_ci)
+
+
+def skybox_basis(orientation=(0.0, 0.0, 0.0, 1.0), fov_deg=90.0, aspect=16.0 / 9.0):
+    """K9's ray basis (include/orbit_abi_ext.h) of the reference's perspective camera with the unit quaternion
+    `orientation` (x, y, z, w): (sky_x, sky_y, sky_z), three float32 each, for orbit_fragments_shade_sky — sky_x = R e_x /
+    P00, sky_y = R e_y / P11, sky_z = -R e_z of skybox_view_projection_matrix = projection * inverse(from_quat(orientation))
+    (src/passes/forward.rs:471-472)."""
+    return passes.skybox_basis(orientation, float(np.deg2rad(np.float32(fov_deg))), aspect)

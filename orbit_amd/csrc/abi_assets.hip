@@ -13,6 +13,7 @@
 #include "abi_internal.h"
 #include "post_common.h" // bloom_layout
 #include "env_common.h"  // env_layout, env_map_check, env_sample_check
+#include "sky_common.h"  // sky_check
 
 namespace {
 
@@ -377,6 +378,19 @@ int32_t orbit_fragments_shade_shadowed(OrbitCtx *ctx, const OrbitFragmentsShadeS
     std::lock_guard<std::mutex> lock(ctx->mu);
     const hipError_t e = launch_fragments_shade_shadowed(j, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch fragments_shade_shadowed");
+    return ORBIT_OK;
+}
+
+// The same two launches with the sky light's term and the skybox served (fragments_shade_sky.hip).  The whole job, the
+// base job's and the shadow fields' parts included, is checked by sky_common.h's sky_check, the function the mirror uses.
+int32_t orbit_fragments_shade_sky(OrbitCtx *ctx, const OrbitFragmentsShadeSky *job, void *stream) {
+    if (!job) return fail(ctx, ORBIT_E_INVALID, "fragments_shade_sky: job is NULL");
+    const char *wrong = orbit::raster::sky_check(*job);
+    if (wrong) return fail(ctx, ORBIT_E_INVALID, "fragments_shade_sky: %s", wrong);
+    if (!ctx) return fail(nullptr, ORBIT_E_INVALID, "fragments_shade_sky: ctx is NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const hipError_t e = launch_fragments_shade_sky(*job, ctx->num_cus, ctx->visibility_grid, ctx->status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "launch fragments_shade_sky");
     return ORBIT_OK;
 }
 

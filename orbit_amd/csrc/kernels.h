@@ -460,6 +460,11 @@ hipError_t launch_fragments_shade(const OrbitFragmentsShade &job, uint32_t num_c
 // form the same rule chooses, evaluates cascade selection, blocker search and filter per lane
 hipError_t launch_fragments_shade_shadowed(const OrbitFragmentsShadeShadowed &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
                                            hipStream_t s);
+// fragments_shade_sky.hip: orbit_fragments_shade_sky — `job` validated by the entry point (sky_common.h sky_check).  The
+// same two launches with K1-K10 served: the clear also clears sky_stats; the walk, in the form the same rule chooses,
+// evaluates a SKY light from the environment's images per lane, and the lanes of uncovered pixels sample the sky cube
+// behind their tile's walk
+hipError_t launch_fragments_shade_sky(const OrbitFragmentsShadeSky &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status, hipStream_t s);
 // bloom.hip: orbit_bloom — `job` validated by the entry point.  One launch starts the counters, then one launch per level
 // of the chain (2 * levels - 1), a workgroup per 16 x 16 destination tile staging its source box in LDS when it fits
 hipError_t launch_bloom(const OrbitBloom &job, hipStream_t s);

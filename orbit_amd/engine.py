@@ -557,6 +557,42 @@ class Engine:
                                 normal_bias_scale, oriented_bias)
         _lib.check(self._lib.orbit_fragments_shade_shadowed(self._ctx, C.byref(js), _stream(stream)), self._ctx)
 
+    # -- the same with the sky light's term and the skybox served (orbit_fragments_shade_sky)
+    def fragments_shade_sky(self, visibility, width, height, world_pos, normal, material, materials, material_count, lights,
+                            light_count, cluster_offset_image, light_index_buffer, index_capacity, cluster_count, tile_size_px,
+                            z_scale, z_bias, luminance_cutoff, z_near, view_pos, color, shadows, shadow_count, shadow_maps,
+                            shadow_map_count, shadow_resolution, blocker_search_radius, normal_bias_scale, oriented_bias,
+                            irradiance=None, irradiance_size=0, prefiltered=None, prefiltered_size=0, prefiltered_levels=0, brdf=None,
+                            brdf_size=0, sky=None, sky_size=0, sky_levels=0, skybox_lod=0.0, basis=None, ao=None, sky_stats=None,
+                            shadow_index_base=0, shadow_factor=None, cascade=None, shadow_stats=None, lights_walked=None,
+                            stats=None, render_mode=0, clear=False, form=None, stream=None):
+        """fragments_shade_shadowed with the reference's sky light and skybox.  The environment — irradiance (level 0 of a
+        cube), prefiltered (prefiltered_levels levels) and brdf (the R16G16 table), as orbit_amd.env_map.device_env_map
+        writes them, given together or not at all — serves every LIGHT_TYPE_SKY light of a pixel's walk
+        (forward.frag:378-405); without it such a light is skipped and counted in unserved_pixels as before.  ao (1 float
+        per pixel, orbit_ssao's ao_pixel, or None: 1.0) scales the sky term.  sky (sky_levels levels of a cube, or None)
+        fills the pixels whose visibility word is 0 with the cube's colour along the ray of `basis` =
+        orbit_amd.camera.skybox_basis(...) at the constant lod skybox_lod (render_mode 0 only).  sky_stats (32 bytes,
+        layouts.SKY_STATS, cleared by the call) may be None.  With neither given the bytes are
+        fragments_shade_shadowed's.  Byte-equal to orbit_amd.raster.host_fragments_shade_sky.  Enqueued on `stream`."""
+        jk = _lib.FragmentsShadeSky()
+        js = jk.shadowed
+        j = js.shade
+        j.visibility, j.world_pos, j.normal, j.material = _ptr(visibility), _ptr(world_pos), _ptr(normal), _ptr(material)
+        j.materials, j.lights, j.cluster_offset_image = _ptr(materials), _ptr(lights), _ptr(cluster_offset_image)
+        j.light_index_buffer, j.color, j.lights_walked, j.stats = _ptr(light_index_buffer), _ptr(color), _ptr(lights_walked), _ptr(stats)
+        j.material_count, j.light_count, j.index_capacity = int(material_count), int(light_count), int(index_capacity)
+        _lib.fill_fragments_shade(j, cluster_count, tile_size_px, z_scale, z_bias, luminance_cutoff, z_near, view_pos, render_mode,
+                                  width, height, clear, form)
+        js.shadows, js.shadow_maps, js.shadow_factor = _ptr(shadows), _ptr(shadow_maps), _ptr(shadow_factor)
+        js.cascade, js.shadow_stats = _ptr(cascade), _ptr(shadow_stats)
+        _lib.fill_shadow_fields(js, shadow_count, shadow_index_base, shadow_map_count, shadow_resolution, blocker_search_radius,
+                                normal_bias_scale, oriented_bias)
+        jk.irradiance, jk.prefiltered, jk.brdf, jk.sky = _ptr(irradiance), _ptr(prefiltered), _ptr(brdf), _ptr(sky)
+        jk.ao, jk.sky_stats = _ptr(ao), _ptr(sky_stats)
+        _lib.fill_sky_fields(jk, irradiance_size, prefiltered_size, prefiltered_levels, brdf_size, sky_size, sky_levels, skybox_lod, basis)
+        _lib.check(self._lib.orbit_fragments_shade_sky(self._ctx, C.byref(jk), _stream(stream)), self._ctx)
+
     # -- the reference's bloom chain of a colour plane (orbit_bloom)
     def bloom(self, color, width, height, mips, threshold=0.0, soft_threshold=0.0, filter_radius=0.003, max_levels=6,
               stats=None, form=None, stream=None):

@@ -216,6 +216,15 @@ Mat4 Projection::compute_matrix(float aspect_ratio) const {
     return Mat4::orthographic_rh(-half_width, half_width, -half_height, half_height, far_clip, near_clip);
 }
 float Projection::z_far() const { return kind == Orthographic ? far_clip : INFINITY; }
+void skybox_basis(const Quat &orientation, float fov_y, float aspect, float *sky_x, float *sky_y, float *sky_z) {
+    const Mat4 rotation = math::mat4_from_quat(orientation);
+    const Mat4 projection = Mat4::perspective_infinite_reverse_rh(fov_y, aspect, 1.0f); // (P00 and P11 do not depend on z_near)
+    for (int i = 0; i < 3; i++) {
+        sky_x[i] = rotation.c[i] / projection.c[0];
+        sky_y[i] = rotation.c[4 + i] / projection.c[5];
+        sky_z[i] = -rotation.c[8 + i];
+    }
+}
 } // namespace camera
 
 // ------------------------------------------------------------------------- graphics

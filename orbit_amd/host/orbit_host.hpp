@@ -75,6 +75,10 @@ struct Projection {
     float z_near() const { return near_clip; }
     float z_far() const;
 };
+// The ray basis of orbit_fragments_shade_sky's skybox (include/orbit_abi_ext.h K9) of a perspective camera, from
+// skybox_view_projection_matrix = perspective_infinite_reverse_rh(fov_y, aspect, .) * inverse(from_quat(orientation))
+// (src/passes/forward.rs:471-472): sky_x = R e_x / P00, sky_y = R e_y / P11, sky_z = -R e_z, three floats each
+void skybox_basis(const Quat &orientation, float fov_y, float aspect, float *sky_x, float *sky_y, float *sky_z);
 } // namespace camera
 
 namespace graphics {

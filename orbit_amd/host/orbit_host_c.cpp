@@ -644,6 +644,20 @@ int32_t orbit_host_fragments_shade_shadowed(const OrbitFragmentsShadeShadowed *j
     });
 }
 
+int32_t orbit_host_fragments_shade_sky(const OrbitFragmentsShadeSky *job, int32_t *status, uint64_t *census) {
+    return guarded([&] {
+        if (!job) throw Panic("fragments_shade_sky: job is NULL");
+        raster::fragments_shade_sky(*job, status, census);
+    });
+}
+
+int32_t orbit_host_skybox_basis(const float *orientation, float fov_y, float aspect, float *sky_x, float *sky_y, float *sky_z) {
+    return guarded([&] {
+        if (!orientation || !sky_x || !sky_y || !sky_z) throw Panic("skybox_basis: NULL argument");
+        camera::skybox_basis(Quat{orientation[0], orientation[1], orientation[2], orientation[3]}, fov_y, aspect, sky_x, sky_y, sky_z);
+    });
+}
+
 int32_t orbit_host_bloom(const OrbitBloom *job) {
     return guarded([&] {
         if (!job) throw Panic("bloom: job is NULL");

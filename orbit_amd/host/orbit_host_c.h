@@ -267,6 +267,20 @@ int32_t orbit_host_fragments_shade(const OrbitFragmentsShade *job, int32_t *stat
 /* the reference of orbit_fragments_shade_shadowed (H1-H10): the device call's block with HOST pointers in it, as
  * orbit_host_fragments_shade; shadow_factor, cascade and shadow_stats hold the device's bytes too. */
 int32_t orbit_host_fragments_shade_shadowed(const OrbitFragmentsShadeShadowed *job, int32_t *status);
+/* the reference of orbit_fragments_shade_sky (K1-K10): the device call's block with HOST pointers in it, as
+ * orbit_host_fragments_shade_shadowed; sky_stats holds the device's bytes too.  ORBIT_HOST_PANIC for everything the device
+ * answers with ORBIT_E_INVALID, alignment and aliasing included: the two share one check.  census (may be NULL):
+ * ORBIT_HOST_SKY_CENSUS counters — 0-63 the cube sampler's (ORBIT_HOST_ENV_CENSUS, over K4's, K5's and K9's samples), then
+ * by index 64 / 65 SKY lights evaluated / skipped with the environment NULL; 66-70 evaluations with dot(N, V) negative, 0,
+ * 1, NaN, any other value; 71 / 72 channels whose max(1 - roughness, f0) took 1 - roughness / f0; 73 / 74 evaluations whose
+ * N / R was a bad direction; 75 / 76 / 77 table lookups with a tap clamped at 0 / at n - 1 / not clamped; 78 pixels shaded
+ * with ao NULL, 79 with ao[p] < 1, 80 with 1.0f taken; 81 / 82 skybox pixels with a good / a bad direction; 83 second and
+ * later SKY lights of one walk; 84-95 zero. */
+#define ORBIT_HOST_SKY_CENSUS 96
+int32_t orbit_host_fragments_shade_sky(const OrbitFragmentsShadeSky *job, int32_t *status, uint64_t *census);
+/* K9's ray basis of the reference's perspective_infinite_reverse_rh camera: orientation (x, y, z, w) a unit quaternion,
+ * fov_y in radians -> sky_x, sky_y, sky_z, three floats each */
+int32_t orbit_host_skybox_basis(const float *orientation, float fov_y, float aspect, float *sky_x, float *sky_y, float *sky_z);
 /* the reference of orbit_bloom (B1-B9): the device call's block with HOST pointers in it; mips and stats hold the
  * device's bytes.  ORBIT_HOST_PANIC for what the device answers with ORBIT_E_INVALID. */
 int32_t orbit_host_bloom(const OrbitBloom *job);

@@ -2,13 +2,16 @@
 #include "orbit_raster.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <string>
 
 #include "../csrc/raster_common.h"
 #include "../csrc/surface_common.h"
 #include "../csrc/fragment_common.h"
 #include "../csrc/shade_common.h"
 #include "../csrc/shadow_common.h"
+#include "../csrc/sky_common.h"
 #include "orbit_host.hpp"
 
 namespace orbit {
@@ -539,6 +542,74 @@ void fragments_shade_shadowed(const OrbitFragmentsShadeShadowed &j, int32_t *sta
     }
     if (b.stats) *b.stats = st;
     if (j.shadow_stats) *j.shadow_stats = sh;
+    if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
+}
+
+namespace {
+struct SkyCounting { // sky_common.h's and the sampler's census hook: counts into the tests' block, or nowhere
+    uint64_t *census;
+    void operator()(uint32_t index) const {
+        if (census) census[index]++;
+    }
+};
+} // namespace
+
+void fragments_shade_sky(const OrbitFragmentsShadeSky &js, int32_t *status, uint64_t *census) {
+    if (const char *wrong = sky_check(js)) throw Panic(std::string("fragments_shade_sky: ") + wrong);
+    const OrbitFragmentsShadeShadowed &j = js.shadowed;
+    const OrbitFragmentsShade &b = j.shade;
+    const SkyCounting counting{census};
+    const size_t pixels = (size_t)b.width * b.height;
+    if (b.flags & ORBIT_SHADE_CLEAR) { // L9, H10
+        std::memset(b.color, 0, pixels * 16);
+        if (b.lights_walked) std::memset(b.lights_walked, 0, pixels * 4);
+        if (j.shadow_factor) std::fill(j.shadow_factor, j.shadow_factor + pixels, 1.0f);
+        if (j.cascade) std::fill(j.cascade, j.cascade + pixels, kNone);
+    }
+    const bool box = sky_box_given(js);
+    OrbitShadeStats st{};
+    OrbitShadowStats sh{};
+    OrbitSkyStats sky{};
+    for (size_t p = 0; p < pixels; p++) {
+        const uint64_t word = b.visibility[p];
+        const uint32_t x = (uint32_t)(p % b.width), y = (uint32_t)(p / b.width);
+        float color[4];
+        if (word == 0) {
+            if (!box) continue;
+            if (!sky_box_pixel(js, x, y, color, counting)) sky.bad_directions++; // K9
+            sky.skybox_pixels++;
+            std::memcpy(b.color + 4 * p, color, 16);
+            continue;
+        }
+        st.covered_pixels++;
+        const uint32_t slice = shade_slice_canonical(b.z_near, bits_float((int32_t)(uint32_t)(word >> 32)), b.z_scale, b.z_bias); // L2
+        uint32_t n, marks;
+        ShadowPixel sp;
+        SkyPixel sk;
+        const uint32_t verdict = sky_shade_pixel<true>(js, x, y, p, slice, color, n, marks, sp, sk, counting);
+        if (verdict == kShadeUnshaded) st.unshaded_pixels++;
+        if (verdict == kShadeStale) st.stale_pixels++;
+        if (verdict != kShadeWritten) continue;
+        st.written_pixels++;
+        if (marks & kShadeOutside) st.outside_pixels++;
+        if (marks & kShadeDegenerate) st.degenerate_pixels++;
+        if (marks & kShadeTextured) st.textured_pixels++;
+        if (marks & kShadeUnserved) st.unserved_pixels++;
+        if (sp.marks & kShadowEvaluated) sh.shadowed_pixels++;
+        if (sp.marks & kShadowOutOfCascades) sh.no_cascade_pixels++;
+        if (sp.marks & kShadowEarlyOut) sh.early_out_pixels++;
+        sh.shadow_evaluations += sp.evaluations;
+        if (sk.evaluations != 0u) sky.sky_lit_pixels++;
+        sky.sky_evaluations += sk.evaluations;
+        sky.bad_directions += sk.bad;
+        std::memcpy(b.color + 4 * p, color, 16);
+        if (b.lights_walked) b.lights_walked[p] = n;
+        if (j.shadow_factor) j.shadow_factor[p] = sp.factor;
+        if (j.cascade) j.cascade[p] = sp.cascade;
+    }
+    if (b.stats) *b.stats = st;
+    if (j.shadow_stats) *j.shadow_stats = sh;
+    if (js.sky_stats) *js.sky_stats = sky;
     if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
 }
 

@@ -77,6 +77,9 @@ SHADE_STATS = np.dtype([(n, "<u4") for n in ("covered_pixels", "written_pixels",
                                              "degenerate_pixels", "textured_pixels", "unserved_pixels")])
 # OrbitShadowStats: the counters orbit_fragments_shade_shadowed adds
 SHADOW_STATS = np.dtype([(n, "<u4") for n in ("shadowed_pixels", "no_cascade_pixels", "early_out_pixels", "shadow_evaluations")])
+# OrbitSkyStats (32 B, 8-B aligned, cleared by orbit_fragments_shade_sky)
+SKY_STATS = np.dtype([("sky_evaluations", "<u4"), ("sky_lit_pixels", "<u4"), ("skybox_pixels", "<u4"), ("_pad", "<u4"),
+                      ("bad_directions", "<u8"), ("_pad2", "<u8")])
 # OrbitBloomStats and OrbitPostStats: the counters of orbit_bloom and orbit_post_process
 BLOOM_STATS = np.dtype([(n, "<u4") for n in ("levels", "texels_written", "nonfinite_inputs", "clamped_texels")])
 POST_STATS = np.dtype([(n, "<u4") for n in ("pixels", "nonfinite_pixels", "bloom_pixels", "_pad")])

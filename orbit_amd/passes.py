@@ -148,6 +148,16 @@ def mat4_inverse(m):
     return np.array(out, dtype=np.float32)
 
 
+def skybox_basis(orientation, fov_y, aspect):
+    """orbit_host_skybox_basis: K9's (sky_x, sky_y, sky_z) of orbit_fragments_shade_sky, three float32 each."""
+    q = (C.c_float * 4)(*[float(v) for v in orientation])
+    out = [(C.c_float * 3)() for _ in range(3)]
+    fn = lib().orbit_host_skybox_basis
+    fn.restype, fn.argtypes = C.c_int32, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(fn(q, float(fov_y), float(aspect), *out))
+    return tuple(np.array(o, dtype=np.float32) for o in out)
+
+
 def frustum_planes_from_matrix(m, normalize=True):
     out = ((C.c_float * 4) * 6)()
     lib().orbit_host_frustum_planes_from_matrix(_mat(m), out, 1 if normalize else 0)

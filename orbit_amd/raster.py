@@ -360,6 +360,105 @@ def host_fragments_shade_shadowed(visibility, world_pos, normal, material, mater
     return dict(color=color, lights_walked=walked, stats=None if stats is None else stats[0], status=status.value, shadow_factor=factor,
                 cascade=cascade, shadow_stats=None if shadow_stats is None else shadow_stats[0])
 
+SKY_CENSUS_SIZE = 96  # ORBIT_HOST_SKY_CENSUS
+SKY_CENSUS = dict(evaluated=64, skipped=65, ndv_negative=66, ndv_zero=67, ndv_one=68, ndv_nan=69, ndv_other=70, took_roughness=71,
+                  took_f0=72, bad_normal=73, bad_reflection=74, table_low=75, table_high=76, table_inside=77, ao_null=78,
+                  ao_below_one=79, ao_one=80, skybox=81, skybox_bad=82, second_sky_light=83)
+
+
+def host_fragments_shade_sky(visibility, world_pos, normal, material, materials, lights, cluster_offset_image, light_index_buffer,
+                             cluster_count, tile_size_px, z_scale, z_bias, luminance_cutoff, z_near, view_pos, shadows, shadow_maps,
+                             shadow_resolution, blocker_search_radius, normal_bias_scale, oriented_bias, env=None, sky=None,
+                             skybox_lod=0.0, basis=None, ao=None, shadow_index_base=0, shadow_count=None, shadow_map_count=None,
+                             render_mode=0, clear=True, into=None, form=None, material_count=None, light_count=None, index_capacity=None,
+                             fill=0, want_walked=True, want_stats=True, want_factor=True, want_cascade=True, want_shadow_stats=True,
+                             want_sky_stats=True, want_census=False, over=None, return_job=False):
+    """orbit_host_fragments_shade_sky: host_fragments_shade_shadowed's arguments, then env: None or dict(irradiance,
+    prefiltered, brdf: np.uint16 arrays in E0's layout as orbit_amd.env_map.host_env_map returns them; irradiance_size,
+    prefiltered_size, prefiltered_levels, brdf_size), sky: None or dict(cube, size, levels), K9's skybox_lod and basis
+    (orbit_amd.camera.skybox_basis), ao: None or (height, width) float32 -> host_fragments_shade_shadowed's dict with
+    sky_stats: np[layouts.SKY_STATS] scalar row and census: np.uint64 (SKY_CENSUS_SIZE,), each None if not wanted.
+    `over`: fields of the OrbitFragmentsShadeSky block set last, as they are; return_job: nothing is run, the block and the
+    arrays it points into are returned (both for the tests of the argument errors)."""
+    vis = np.ascontiguousarray(visibility, dtype=np.uint64)
+    height, width = vis.shape
+    wp = np.ascontiguousarray(world_pos, dtype=np.float32).reshape(height, width, 4)
+    nrm = np.ascontiguousarray(normal, dtype=np.float32).reshape(height, width, 3)
+    mat = np.ascontiguousarray(material, dtype=np.uint32).reshape(height, width)
+    mats = np.ascontiguousarray(materials).view(np.uint8).reshape(-1)
+    lts = np.ascontiguousarray(lights).view(np.uint8).reshape(-1)
+    img = np.ascontiguousarray(cluster_offset_image).view(np.uint32).reshape(-1)
+    lib_ = np.ascontiguousarray(light_index_buffer).view(np.uint8).reshape(-1)
+    rows = None if shadows is None else np.ascontiguousarray(shadows).view(np.uint8).reshape(-1)
+    maps = None if shadow_maps is None else np.ascontiguousarray(shadow_maps, dtype=np.float32).reshape(-1)
+    cx, cy, cz = (int(c) for c in cluster_count)
+    if img.size < 2 * cx * cy * cz:
+        raise ValueError("cluster_count reaches beyond the offset image")
+    material_count = mats.nbytes // 80 if material_count is None else int(material_count)
+    light_count = lts.nbytes // 64 if light_count is None else int(light_count)
+    index_capacity = max(lib_.nbytes - 4, 0) // 4 if index_capacity is None else int(index_capacity)
+    res = int(shadow_resolution)
+    shadow_count = (0 if rows is None else rows.nbytes // 288) if shadow_count is None else int(shadow_count)
+    shadow_map_count = (0 if maps is None or res == 0 else maps.size // (res * res)) if shadow_map_count is None else int(shadow_map_count)
+    if material_count * 80 > mats.nbytes or light_count * 64 > lts.nbytes or 4 + 4 * index_capacity > max(lib_.nbytes, 4):
+        raise ValueError("a count reaches beyond its array")
+    if shadow_count * 288 > (0 if rows is None else rows.nbytes) or shadow_map_count * res * res > (0 if maps is None else maps.size):
+        raise ValueError("a shadow count reaches beyond its array")
+    cubes = {}
+    if env is not None:
+        cubes = {k: np.ascontiguousarray(env[k], dtype=np.uint16).reshape(-1) for k in ("irradiance", "prefiltered", "brdf")}
+        n, m, levels, t = (int(env[k]) for k in ("irradiance_size", "prefiltered_size", "prefiltered_levels", "brdf_size"))
+        need = dict(irradiance=24 * n * n, prefiltered=24 * sum(max(1, m >> k) ** 2 for k in range(levels)), brdf=2 * t * t)
+        if any(cubes[k].size < need[k] for k in need):
+            raise ValueError("an environment size reaches beyond its array")
+    if sky is not None:
+        cubes["sky"] = np.ascontiguousarray(sky["cube"], dtype=np.uint16).reshape(-1)
+        if cubes["sky"].size < 24 * sum(max(1, int(sky["size"]) >> k) ** 2 for k in range(int(sky["levels"]))):
+            raise ValueError("the sky cube's size and levels reach beyond its array")
+    ao_ = None if ao is None else np.ascontiguousarray(ao, dtype=np.float32).reshape(height, width)
+    if into is not None:
+        color = np.array(into["color"], dtype=np.float32, order="C").reshape(height, width, 4)
+        walked = None if not want_walked else np.array(into["lights_walked"], dtype=np.uint32, order="C").reshape(height, width)
+        factor = None if not want_factor else np.array(into["shadow_factor"], dtype=np.float32, order="C").reshape(height, width)
+        cascade = None if not want_cascade else np.array(into["cascade"], dtype=np.uint32, order="C").reshape(height, width)
+    else:
+        color = np.full((height, width, 4), fill, np.uint32).view(np.float32)
+        walked = np.full((height, width), fill, np.uint32) if want_walked else None
+        factor = np.full((height, width), fill, np.uint32).view(np.float32) if want_factor else None
+        cascade = np.full((height, width), fill, np.uint32) if want_cascade else None
+    stats = np.zeros(1, L.SHADE_STATS) if want_stats else None
+    shadow_stats = np.zeros(1, L.SHADOW_STATS) if want_shadow_stats else None
+    sky_stats = np.zeros(1, L.SKY_STATS) if want_sky_stats else None
+    census = np.zeros(SKY_CENSUS_SIZE, np.uint64) if want_census else None
+    p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    jk = _lib.FragmentsShadeSky()
+    js = jk.shadowed
+    j = js.shade
+    j.visibility, j.world_pos, j.normal, j.material, j.materials, j.lights = p(vis), p(wp), p(nrm), p(mat), p(mats), p(lts)
+    j.cluster_offset_image, j.light_index_buffer, j.color, j.lights_walked, j.stats = p(img), p(lib_), p(color), p(walked), p(stats)
+    j.material_count, j.light_count, j.index_capacity = material_count, light_count, index_capacity
+    _lib.fill_fragments_shade(j, (cx, cy, cz), tile_size_px, z_scale, z_bias, luminance_cutoff, z_near, view_pos, render_mode, width,
+                              height, clear, form)
+    js.shadows, js.shadow_maps, js.shadow_factor, js.cascade, js.shadow_stats = p(rows), p(maps), p(factor), p(cascade), p(shadow_stats)
+    _lib.fill_shadow_fields(js, shadow_count, shadow_index_base, shadow_map_count, res, blocker_search_radius, normal_bias_scale, oriented_bias)
+    jk.irradiance, jk.prefiltered, jk.brdf, jk.sky = (p(cubes.get(k)) for k in ("irradiance", "prefiltered", "brdf", "sky"))
+    jk.ao, jk.sky_stats = p(ao_), p(sky_stats)
+    e, s = env or {}, sky or {}
+    _lib.fill_sky_fields(jk, e.get("irradiance_size", 0), e.get("prefiltered_size", 0), e.get("prefiltered_levels", 0), e.get("brdf_size", 0),
+                         s.get("size", 0), s.get("levels", 0), skybox_lod, basis)
+    for name, value in (over or {}).items():
+        target = jk if hasattr(jk, name) else js if hasattr(js, name) else j
+        setattr(target, name, value)
+    if return_job:
+        return jk, (vis, wp, nrm, mat, mats, lts, img, lib_, rows, maps, cubes, ao_, color, walked, factor, cascade, stats, shadow_stats, sky_stats)
+    status = C.c_int32(0)
+    fn = lib().orbit_host_fragments_shade_sky
+    fn.restype, fn.argtypes = C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(fn(C.byref(jk), C.byref(status), p(census)))
+    return dict(color=color, lights_walked=walked, stats=None if stats is None else stats[0], status=status.value, shadow_factor=factor,
+                cascade=cascade, shadow_stats=None if shadow_stats is None else shadow_stats[0],
+                sky_stats=None if sky_stats is None else sky_stats[0], census=census)
+
 
 def host_shadow_rotation(x0, y0, width, height):
     """H6 of the pixels (x0 + x, y0 + y), x < width, y < height -> (theta, sine, cosine), each (height, width) np.float32:
