@@ -450,9 +450,14 @@ hipError_t launch_visibility_surface_drawn(const OrbitVisibilitySurface &job, ui
 // ORBIT_FRAGMENTS_CLEAR, fills the outputs; the next reads every word once, a wave per 8 x 8 tile, a lane per pixel
 hipError_t launch_surface_fragments(const OrbitSurfaceFragments &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
                                     hipStream_t s);
+// fragments_shade.hip: the first launch of the three shade calls, under their grid cap `cap` — the stats blocks given = 0
+// and, with ORBIT_SHADE_CLEAR, `b`'s color and lights_walked = 0, shadow_factor = 1.0f, cascade = 0xFFFFFFFF.  NULL: a
+// plane not filled, a block not kept; nothing to do: no launch
+hipError_t launch_shade_clear(const OrbitFragmentsShade &b, float *shadow_factor, uint32_t *cascade, OrbitShadowStats *shadow_stats,
+                              OrbitSkyStats *sky_stats, uint32_t cap, hipStream_t s);
 // fragments_shade.hip: orbit_fragments_shade — `job` validated by the entry point.  One launch clears stats and, with
 // ORBIT_SHADE_CLEAR, color and lights_walked; the next shades, a wave per 8 x 8 tile, a lane per pixel, walking the
-// cluster's light list per lane or staged through LDS (tile_size_px % 8 == 0, the default there)
+// cluster's light list per lane or staged through LDS (tile_size_px % 8 == 0, the default there): shade_walk.h
 hipError_t launch_fragments_shade(const OrbitFragmentsShade &job, uint32_t num_cus, uint32_t grid_cap, int32_t *status,
                                   hipStream_t s);
 // fragments_shade_shadowed.hip: orbit_fragments_shade_shadowed — `job` validated by the entry point.  The same two

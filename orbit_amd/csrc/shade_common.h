@@ -2,8 +2,8 @@
 // for the device kernels (fragments_shade.hip) and the host mirror (orbit_amd/host/orbit_raster.cpp).  The pieces:
 // shade_slice_canonical is L2's integer (log2c and f2u_sat restated for the host: orbit_device.h's are device only and
 // this header does not depend on it); shade_cluster is L2's lookup; shade_light_row is what L5 / L6 read of a light;
-// shade_pixel_begin / _light / _end are L3-L8 of one pixel; shade_pixel is the whole of L1-L8 for a lane or a host loop
-// that walks its own list.  Equal inputs, equal functions: equal bytes.  What does not depend on the light is evaluated
+// shade_pixel_begin / _light / _end are L3-L8 of one pixel; shade_walk_pixel is the whole of L1-L8 for a lane or a host
+// loop that walks its own list, in the tier of any of the three shade calls (ShadeTier is this call's).  Equal inputs, equal functions: equal bytes.  What does not depend on the light is evaluated
 // once per pixel: every operation is still rounded on its own, so where it is evaluated does not change a bit.
 #pragma once
 #include "../../include/orbit_abi_ext.h"
@@ -247,40 +247,77 @@ ORBIT_RASTER_FN uint32_t shade_material_verdict(const OrbitFragmentsShade &j, ui
     return material == kNone ? kShadeUnshaded : material >= j.material_count ? kShadeStale : kShadeWritten;
 }
 
-// L1-L8 of covered pixel p = (x, y) whose slice is `slice`, walking its own list -> the verdict; kShadeWritten: color,
-// n = lights_walked, marks = kShadeOutside | kShadeDegenerate | kShadeTextured | kShadeUnserved
-ORBIT_RASTER_FN uint32_t shade_pixel(const OrbitFragmentsShade &j, uint32_t x, uint32_t y, size_t p, uint32_t slice, float *color,
-                                     uint32_t &n, uint32_t &marks) {
-    n = 0u, marks = 0u;
-    for (int i = 0; i < 4; i++) color[i] = 0.0f;
-    const uint32_t material = j.material[p];
-    const uint32_t verdict = shade_material_verdict(j, material);
-    if (verdict != kShadeWritten) return verdict;
-    const ShadeCluster c = shade_cluster(j, x, y, slice);
-    if (c.stale) return kShadeStale;
-    const uint32_t *walk = shade_indices(j) + c.offset;
-    const OrbitMaterialData m = shade_load_row(j.materials, material);
-    ShadePixel px;
-    float wp[4], nrm[3];
-    __builtin_memcpy(wp, j.world_pos + 4u * p, 16);
-    __builtin_memcpy(nrm, j.normal + 3u * p, 12);
-    shade_pixel_begin(j, m, wp, nrm, px);
-    for (uint32_t i = 0; i < c.n; i++) {
-        const uint32_t index = walk[i];
-        if (index >= j.light_count) return kShadeStale;
-        if (j.render_mode != 0u) continue;
-        ShadeLight l;
-        shade_light_row(shade_load_row(j.lights, index), l);
+// A tier is what one of the shade calls adds to the walk below: a policy type that holds no data on the device.  It names
+// its Job and how to reach the base job in it, the Extra state a pixel carries beside ShadePixel, and reset (Extra of a
+// pixel not yet begun: what an unwritten pixel counts and stores), begin (after shade_pixel_begin), light_checked (a
+// light's row may be evaluated), light (L5 / L6 of one checked light), stale (the light just added made the pixel
+// stale) and end (after shade_pixel_end).  This one is orbit_fragments_shade's: L1-L9 and nothing else.
+struct ShadeTier {
+    using Job = OrbitFragmentsShade;
+    struct Extra {};
+    ORBIT_RASTER_FN static const OrbitFragmentsShade &base(const Job &j) { return j; }
+    ORBIT_RASTER_FN static void reset(Extra &) {}
+    ORBIT_RASTER_FN void begin(const Job &, const OrbitMaterialData &, const float *, size_t, Extra &) const {}
+    ORBIT_RASTER_FN static bool light_checked(const Job &, uint32_t, uint32_t) { return true; }
+    ORBIT_RASTER_FN void light(const Job &j, const ShadeLight &l, uint32_t, uint32_t, ShadePixel &px, Extra &) const {
         shade_pixel_light(l, j.luminance_cutoff, px);
     }
-    n = c.n;
-    marks = (c.outside ? kShadeOutside : 0u) | (px.textured ? kShadeTextured : 0u);
-    if (j.render_mode == 0u) {
+    ORBIT_RASTER_FN static bool stale(const Extra &) { return false; }
+    ORBIT_RASTER_FN static void end(Extra &) {}
+};
+
+// L7 and L8 of a pixel whose walk of n lights is over -> its marks
+template <class Tier>
+ORBIT_RASTER_FN uint32_t shade_walk_end(const OrbitFragmentsShade &b, bool outside, uint32_t n, const ShadePixel &px, float *color,
+                                        typename Tier::Extra &e) {
+    uint32_t marks = (outside ? kShadeOutside : 0u) | (px.textured ? kShadeTextured : 0u);
+    if (b.render_mode == 0u) {
         if (shade_pixel_end(px, color)) marks |= kShadeDegenerate;
         if (px.unserved) marks |= kShadeUnserved;
+        Tier::end(e);
     } else {
         shade_heat(n, color);
     }
+    return marks;
+}
+
+// L1-L8 of covered pixel p = (x, y) whose slice is `slice`, walking its own list, in tier t (e reset by the caller) -> the
+// verdict; kShadeWritten: color, n = lights_walked, marks = kShadeOutside | kShadeDegenerate | kShadeTextured |
+// kShadeUnserved, and what the tier keeps in e
+template <class Tier>
+ORBIT_RASTER_FN uint32_t shade_walk_pixel(const Tier &t, const typename Tier::Job &j, uint32_t x, uint32_t y, size_t p, uint32_t slice,
+                                          float *color, uint32_t &n, uint32_t &marks, typename Tier::Extra &e) {
+    const OrbitFragmentsShade &b = Tier::base(j);
+    n = 0u, marks = 0u;
+    for (int i = 0; i < 4; i++) color[i] = 0.0f;
+    const uint32_t material = b.material[p];
+    const uint32_t verdict = shade_material_verdict(b, material);
+    if (verdict != kShadeWritten) return verdict;
+    const ShadeCluster c = shade_cluster(b, x, y, slice);
+    if (c.stale) return kShadeStale;
+    const uint32_t *walk = shade_indices(b) + c.offset;
+    const OrbitMaterialData m = shade_load_row(b.materials, material);
+    ShadePixel px;
+    float wp[4], nrm[3];
+    __builtin_memcpy(wp, b.world_pos + 4u * p, 16);
+    __builtin_memcpy(nrm, b.normal + 3u * p, 12);
+    shade_pixel_begin(b, m, wp, nrm, px);
+    t.begin(j, m, wp, p, e);
+    for (uint32_t i = 0; i < c.n; i++) {
+        const uint32_t index = walk[i];
+        if (index >= b.light_count) return kShadeStale;
+        if (b.render_mode != 0u) { // the type and the shadow index for the tier's check, nothing else of the row
+            if (!Tier::light_checked(j, b.lights[index].light_type, b.lights[index].shadow_data_index)) return kShadeStale;
+            continue;
+        }
+        ShadeLight l;
+        shade_light_row(shade_load_row(b.lights, index), l);
+        if (!Tier::light_checked(j, l.type, l.shadow)) return kShadeStale;
+        t.light(j, l, x, y, px, e);
+        if (Tier::stale(e)) return kShadeStale;
+    }
+    n = c.n;
+    marks = shade_walk_end<Tier>(b, c.outside, n, px, color, e);
     return kShadeWritten;
 }
 

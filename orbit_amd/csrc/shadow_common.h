@@ -3,8 +3,7 @@
 // (orbit_amd/host/orbit_raster.cpp), on top of shade_common.h's L1-L9.  The pieces: shadow_theta is H6's noise (its sine
 // and cosine, shadow_sincos, and R2's shadow_project live in shade_common.h, where ssao_common.h finds them too);
 // shadow_eval is H2-H8 of one shadowed light at one pixel; shadow_light_checked is H1's range check; shadow_pixel_light is
-// L5 / L6 / H9 of one light of the walk; shadow_shade_pixel is the whole of L1-L8 with H for a lane or a host loop that
-// walks its own list.  Equal inputs, equal functions: equal bytes.
+// L5 / L6 / H9 of one light of the walk; ShadowedTier hands them to shade_common.h's walk.  Equal inputs, equal functions: equal bytes.
 #pragma once
 #include "shade_common.h"
 
@@ -155,51 +154,20 @@ ORBIT_RASTER_FN void shadow_pixel_light(const OrbitFragmentsShadeShadowed &j, co
     for (int i = 0; i < 3; i++) px.sum[i] = px.sum[i] + term[i];
 }
 
-// L1-L8 with H of covered pixel p = (x, y) whose slice is `slice`, walking its own list -> the verdict, as shade_pixel's;
-// kShadeWritten: also sp's factor, cascade, evaluations and marks
-ORBIT_RASTER_FN uint32_t shadow_shade_pixel(const OrbitFragmentsShadeShadowed &j, uint32_t x, uint32_t y, size_t p, uint32_t slice, float *color,
-                                            uint32_t &n, uint32_t &marks, ShadowPixel &sp) {
-    const OrbitFragmentsShade &b = j.shade;
-    n = 0u, marks = 0u;
-    for (int i = 0; i < 4; i++) color[i] = 0.0f;
-    shadow_pixel_begin(1.0f, sp);
-    const uint32_t material = b.material[p];
-    const uint32_t verdict = shade_material_verdict(b, material);
-    if (verdict != kShadeWritten) return verdict;
-    const ShadeCluster c = shade_cluster(b, x, y, slice);
-    if (c.stale) return kShadeStale;
-    const uint32_t *walk = shade_indices(b) + c.offset;
-    const OrbitMaterialData m = shade_load_row(b.materials, material);
-    ShadePixel px;
-    float wp[4], nrm[3];
-    __builtin_memcpy(wp, b.world_pos + 4u * p, 16);
-    __builtin_memcpy(nrm, b.normal + 3u * p, 12);
-    shade_pixel_begin(b, m, wp, nrm, px);
-    sp.w = wp[3];
-    for (uint32_t i = 0; i < c.n; i++) {
-        const uint32_t index = walk[i];
-        if (index >= b.light_count) return kShadeStale;
-        if (b.render_mode != 0u) {
-            if (!shadow_light_checked(j, b.lights[index].light_type, b.lights[index].shadow_data_index)) return kShadeStale;
-            continue;
-        }
-        ShadeLight l;
-        shade_light_row(shade_load_row(b.lights, index), l);
-        if (!shadow_light_checked(j, l.type, l.shadow)) return kShadeStale;
+// orbit_fragments_shade_shadowed's tier of shade_common.h's walk
+struct ShadowedTier {
+    using Job = OrbitFragmentsShadeShadowed;
+    using Extra = ShadowPixel;
+    ORBIT_RASTER_FN static const OrbitFragmentsShade &base(const Job &j) { return j.shade; }
+    ORBIT_RASTER_FN static void reset(Extra &sp) { shadow_pixel_begin(1.0f, sp); }
+    ORBIT_RASTER_FN void begin(const Job &, const OrbitMaterialData &, const float *wp, size_t, Extra &sp) const { sp.w = wp[3]; }
+    ORBIT_RASTER_FN static bool light_checked(const Job &j, uint32_t type, uint32_t shadow) { return shadow_light_checked(j, type, shadow); }
+    ORBIT_RASTER_FN void light(const Job &j, const ShadeLight &l, uint32_t x, uint32_t y, ShadePixel &px, Extra &sp) const {
         shadow_pixel_light(j, l, x, y, px, sp);
-        if (sp.stale) return kShadeStale;
     }
-    n = c.n;
-    marks = (c.outside ? kShadeOutside : 0u) | (px.textured ? kShadeTextured : 0u);
-    if (b.render_mode == 0u) {
-        if (shade_pixel_end(px, color)) marks |= kShadeDegenerate;
-        if (px.unserved) marks |= kShadeUnserved;
-        finite_or_zero(sp.factor);
-    } else {
-        shade_heat(n, color);
-    }
-    return kShadeWritten;
-}
+    ORBIT_RASTER_FN static bool stale(const Extra &sp) { return sp.stale; }
+    ORBIT_RASTER_FN static void end(Extra &sp) { finite_or_zero(sp.factor); }
+};
 
 } // namespace raster
 } // namespace orbit

@@ -1,9 +1,9 @@
 // sky_common.h — the arithmetic of orbit_fragments_shade_sky (include/orbit_abi_ext.h K1-K10), written
 // once for the device kernels (fragments_shade_sky.hip) and the host mirror (orbit_amd/host/orbit_raster.cpp), on top of
 // shade_common.h's L1-L9, shadow_common.h's H1-H10 and env_common.h's E4, none of which it changes.  The pieces: sky_table is
-// K6; sky_pixel_begin K8; sky_light_term K2-K7 of one SKY light at one pixel; sky_pixel_light K1 in front of shadow_pixel_light; sky_shade_pixel the whole of L1-L8 with H and K for a lane or a host
-// loop that walks its own list; sky_box_pixel K9; sky_check the argument errors, for the entry point and the mirror alike.
-// fp32, every operation rounded on its own.  Equal inputs, equal functions: equal bytes.
+// K6; sky_pixel_begin K8; sky_light_term K2-K7 of one SKY light at one pixel; sky_pixel_light K1 in front of
+// shadow_pixel_light; SkyTier hands them to shade_common.h's walk; sky_box_pixel K9; sky_check the argument errors, for
+// the entry point and the mirror alike.  fp32, every operation rounded on its own.  Equal inputs, equal functions: equal bytes.
 #pragma once
 #include "shade_common.h"
 #include "shadow_common.h"
@@ -139,55 +139,33 @@ ORBIT_RASTER_FN void sky_pixel_light(const OrbitFragmentsShadeSky &j, const Shad
     for (int i = 0; i < 3; i++) px.sum[i] = px.sum[i] + term[i];
 }
 
-// L1-L8 with H and K of covered pixel p = (x, y) whose slice is `slice`, walking its own list -> the verdict, as
-// shadow_shade_pixel's; kShadeWritten: also k's evaluations and bad directions
+// orbit_fragments_shade_sky's tier of shade_common.h's walk.  ENV as sky_pixel_light's; the host mirror's instance carries
+// its census, a kernel's carries nothing
+struct SkyExtra {
+    ShadowPixel sp;
+    SkyPixel k;
+};
 template <bool ENV = true, class Census = EnvNoCensus>
-ORBIT_RASTER_FN uint32_t sky_shade_pixel(const OrbitFragmentsShadeSky &js, uint32_t x, uint32_t y, size_t p, uint32_t slice, float *color,
-                                         uint32_t &n, uint32_t &marks, ShadowPixel &sp, SkyPixel &k, const Census &census = Census()) {
-    const OrbitFragmentsShadeShadowed &j = js.shadowed;
-    const OrbitFragmentsShade &b = j.shade;
-    n = 0u, marks = 0u;
-    for (int i = 0; i < 4; i++) color[i] = 0.0f;
-    shadow_pixel_begin(1.0f, sp);
-    k.roughness = 0.0f, k.ao = 1.0f, k.evaluations = 0u, k.bad = 0u;
-    const uint32_t material = b.material[p];
-    const uint32_t verdict = shade_material_verdict(b, material);
-    if (verdict != kShadeWritten) return verdict;
-    const ShadeCluster c = shade_cluster(b, x, y, slice);
-    if (c.stale) return kShadeStale;
-    const uint32_t *walk = shade_indices(b) + c.offset;
-    const OrbitMaterialData m = shade_load_row(b.materials, material);
-    ShadePixel px;
-    float wp[4], nrm[3];
-    __builtin_memcpy(wp, b.world_pos + 4u * p, 16);
-    __builtin_memcpy(nrm, b.normal + 3u * p, 12);
-    shade_pixel_begin(b, m, wp, nrm, px);
-    sp.w = wp[3];
-    if (ENV && sky_env_given(js)) sky_pixel_begin(js, m.roughness_factor, p, k, census); // (ao has no other reader)
-    for (uint32_t i = 0; i < c.n; i++) {
-        const uint32_t index = walk[i];
-        if (index >= b.light_count) return kShadeStale;
-        if (b.render_mode != 0u) {
-            if (!shadow_light_checked(j, b.lights[index].light_type, b.lights[index].shadow_data_index)) return kShadeStale;
-            continue;
-        }
-        ShadeLight l;
-        shade_light_row(shade_load_row(b.lights, index), l);
-        if (!shadow_light_checked(j, l.type, l.shadow)) return kShadeStale;
-        sky_pixel_light<ENV>(js, l, x, y, px, sp, k, census);
-        if (sp.stale) return kShadeStale;
+struct SkyTier {
+    using Job = OrbitFragmentsShadeSky;
+    using Extra = SkyExtra;
+    Census census;
+    ORBIT_RASTER_FN static const OrbitFragmentsShade &base(const Job &j) { return j.shadowed.shade; }
+    ORBIT_RASTER_FN static void reset(Extra &e) {
+        shadow_pixel_begin(1.0f, e.sp);
+        e.k.roughness = 0.0f, e.k.ao = 1.0f, e.k.evaluations = 0u, e.k.bad = 0u;
     }
-    n = c.n;
-    marks = (c.outside ? kShadeOutside : 0u) | (px.textured ? kShadeTextured : 0u);
-    if (b.render_mode == 0u) {
-        if (shade_pixel_end(px, color)) marks |= kShadeDegenerate;
-        if (px.unserved) marks |= kShadeUnserved;
-        finite_or_zero(sp.factor);
-    } else {
-        shade_heat(n, color);
+    ORBIT_RASTER_FN void begin(const Job &j, const OrbitMaterialData &m, const float *wp, size_t p, Extra &e) const {
+        e.sp.w = wp[3];
+        if (ENV && sky_env_given(j)) sky_pixel_begin(j, m.roughness_factor, p, e.k, census); // (ao has no other reader)
     }
-    return kShadeWritten;
-}
+    ORBIT_RASTER_FN static bool light_checked(const Job &j, uint32_t type, uint32_t shadow) { return shadow_light_checked(j.shadowed, type, shadow); }
+    ORBIT_RASTER_FN void light(const Job &j, const ShadeLight &l, uint32_t x, uint32_t y, ShadePixel &px, Extra &e) const {
+        sky_pixel_light<ENV>(j, l, x, y, px, e.sp, e.k, census);
+    }
+    ORBIT_RASTER_FN static bool stale(const Extra &e) { return e.sp.stale; }
+    ORBIT_RASTER_FN static void end(Extra &e) { finite_or_zero(e.sp.factor); }
+};
 
 // K9 of uncovered pixel (x, y) -> the direction was good
 template <class Census = EnvNoCensus>

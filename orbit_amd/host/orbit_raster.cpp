@@ -463,154 +463,126 @@ static void check_fragments_shade(const OrbitFragmentsShade &j) {
         throw Panic("fragments_shade: NULL argument");
 }
 
-void fragments_shade(const OrbitFragmentsShade &j, int32_t *status) {
-    check_fragments_shade(j);
-    const size_t pixels = (size_t)j.width * j.height;
-    if (j.flags & ORBIT_SHADE_CLEAR) { // L9
-        std::memset(j.color, 0, pixels * 16);
-        if (j.lights_walked) std::memset(j.lights_walked, 0, pixels * 4);
-    }
-    OrbitShadeStats st{};
-    for (size_t p = 0; p < pixels; p++) {
-        const uint64_t word = j.visibility[p];
-        if (word == 0) continue;
-        st.covered_pixels++;
-        const uint32_t x = (uint32_t)(p % j.width), y = (uint32_t)(p / j.width);
-        const uint32_t slice = shade_slice_canonical(j.z_near, bits_float((int32_t)(uint32_t)(word >> 32)), j.z_scale, j.z_bias); // L2
-        float color[4];
-        uint32_t n, marks;
-        const uint32_t verdict = shade_pixel(j, x, y, p, slice, color, n, marks);
-        if (verdict == kShadeUnshaded) st.unshaded_pixels++;
-        if (verdict == kShadeStale) st.stale_pixels++;
-        if (verdict != kShadeWritten) continue;
-        st.written_pixels++;
-        if (marks & kShadeOutside) st.outside_pixels++;
-        if (marks & kShadeDegenerate) st.degenerate_pixels++;
-        if (marks & kShadeTextured) st.textured_pixels++;
-        if (marks & kShadeUnserved) st.unserved_pixels++;
-        std::memcpy(j.color + 4 * p, color, 16);
-        if (j.lights_walked) j.lights_walked[p] = n;
-    }
-    if (j.stats) *j.stats = st;
-    if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
-}
-
-void fragments_shade_shadowed(const OrbitFragmentsShadeShadowed &j, int32_t *status) {
-    const OrbitFragmentsShade &b = j.shade;
-    check_fragments_shade(b);
-    if (j.shadow_count > 0u) {
-        if (!j.shadows || !j.shadow_maps) throw Panic("fragments_shade_shadowed: shadow_count > 0 with shadows or shadow_maps NULL");
-        if (j.shadow_resolution == 0u || j.shadow_resolution > ORBIT_RASTER_MAX_DIM) throw Panic("fragments_shade_shadowed: shadow_resolution");
-        if ((uint64_t)j.shadow_map_count * j.shadow_resolution * j.shadow_resolution > (1ull << 31))
-            throw Panic("fragments_shade_shadowed: shadow maps > 2^31 floats");
-    }
-    const size_t pixels = (size_t)b.width * b.height;
-    if (b.flags & ORBIT_SHADE_CLEAR) { // L9, H10
-        std::memset(b.color, 0, pixels * 16);
-        if (b.lights_walked) std::memset(b.lights_walked, 0, pixels * 4);
-        if (j.shadow_factor) std::fill(j.shadow_factor, j.shadow_factor + pixels, 1.0f);
-        if (j.cascade) std::fill(j.cascade, j.cascade + pixels, kNone);
-    }
+// The three shade mirrors' loop (L1-L9 with what the tier adds) is shade_mirror; a tier's host half is the overloads in
+// front of it: the planes L9 / H10 fill, what a written pixel counts and stores beside the base job's, the stats blocks.
+namespace {
+struct ShadeTally {
     OrbitShadeStats st{};
     OrbitShadowStats sh{};
-    for (size_t p = 0; p < pixels; p++) {
-        const uint64_t word = b.visibility[p];
-        if (word == 0) continue;
-        st.covered_pixels++;
-        const uint32_t x = (uint32_t)(p % b.width), y = (uint32_t)(p / b.width);
-        const uint32_t slice = shade_slice_canonical(b.z_near, bits_float((int32_t)(uint32_t)(word >> 32)), b.z_scale, b.z_bias); // L2
-        float color[4];
-        uint32_t n, marks;
-        ShadowPixel sp;
-        const uint32_t verdict = shadow_shade_pixel(j, x, y, p, slice, color, n, marks, sp);
-        if (verdict == kShadeUnshaded) st.unshaded_pixels++;
-        if (verdict == kShadeStale) st.stale_pixels++;
-        if (verdict != kShadeWritten) continue;
-        st.written_pixels++;
-        if (marks & kShadeOutside) st.outside_pixels++;
-        if (marks & kShadeDegenerate) st.degenerate_pixels++;
-        if (marks & kShadeTextured) st.textured_pixels++;
-        if (marks & kShadeUnserved) st.unserved_pixels++;
-        if (sp.marks & kShadowEvaluated) sh.shadowed_pixels++;
-        if (sp.marks & kShadowOutOfCascades) sh.no_cascade_pixels++;
-        if (sp.marks & kShadowEarlyOut) sh.early_out_pixels++;
-        sh.shadow_evaluations += sp.evaluations;
-        std::memcpy(b.color + 4 * p, color, 16);
-        if (b.lights_walked) b.lights_walked[p] = n;
-        if (j.shadow_factor) j.shadow_factor[p] = sp.factor;
-        if (j.cascade) j.cascade[p] = sp.cascade;
-    }
-    if (b.stats) *b.stats = st;
-    if (j.shadow_stats) *j.shadow_stats = sh;
-    if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
-}
-
-namespace {
+    OrbitSkyStats sky{};
+};
 struct SkyCounting { // sky_common.h's and the sampler's census hook: counts into the tests' block, or nowhere
     uint64_t *census;
     void operator()(uint32_t index) const {
         if (census) census[index]++;
     }
 };
-} // namespace
 
-void fragments_shade_sky(const OrbitFragmentsShadeSky &js, int32_t *status, uint64_t *census) {
-    if (const char *wrong = sky_check(js)) throw Panic(std::string("fragments_shade_sky: ") + wrong);
-    const OrbitFragmentsShadeShadowed &j = js.shadowed;
-    const OrbitFragmentsShade &b = j.shade;
-    const SkyCounting counting{census};
+void mirror_clear(const OrbitFragmentsShade &, size_t) {}
+void mirror_clear(const OrbitFragmentsShadeShadowed &j, size_t pixels) { // H10
+    if (j.shadow_factor) std::fill(j.shadow_factor, j.shadow_factor + pixels, 1.0f);
+    if (j.cascade) std::fill(j.cascade, j.cascade + pixels, kNone);
+}
+void mirror_clear(const OrbitFragmentsShadeSky &j, size_t pixels) { mirror_clear(j.shadowed, pixels); }
+
+void mirror_written(const OrbitFragmentsShade &, size_t, const ShadeTier::Extra &, ShadeTally &) {}
+void mirror_written(const OrbitFragmentsShadeShadowed &j, size_t p, const ShadowPixel &sp, ShadeTally &t) {
+    if (sp.marks & kShadowEvaluated) t.sh.shadowed_pixels++;
+    if (sp.marks & kShadowOutOfCascades) t.sh.no_cascade_pixels++;
+    if (sp.marks & kShadowEarlyOut) t.sh.early_out_pixels++;
+    t.sh.shadow_evaluations += sp.evaluations;
+    if (j.shadow_factor) j.shadow_factor[p] = sp.factor;
+    if (j.cascade) j.cascade[p] = sp.cascade;
+}
+void mirror_written(const OrbitFragmentsShadeSky &j, size_t p, const SkyExtra &e, ShadeTally &t) {
+    mirror_written(j.shadowed, p, e.sp, t);
+    if (e.k.evaluations != 0u) t.sky.sky_lit_pixels++;
+    t.sky.sky_evaluations += e.k.evaluations;
+    t.sky.bad_directions += e.k.bad;
+}
+
+void mirror_stats(const OrbitFragmentsShade &j, const ShadeTally &t) {
+    if (j.stats) *j.stats = t.st;
+}
+void mirror_stats(const OrbitFragmentsShadeShadowed &j, const ShadeTally &t) {
+    mirror_stats(j.shade, t);
+    if (j.shadow_stats) *j.shadow_stats = t.sh;
+}
+void mirror_stats(const OrbitFragmentsShadeSky &j, const ShadeTally &t) {
+    mirror_stats(j.shadowed, t);
+    if (j.sky_stats) *j.sky_stats = t.sky;
+}
+
+// uncovered(x, y, p, tally): what the call does with a pixel whose visibility word is 0
+template <class Tier, class Uncovered>
+void shade_mirror(const Tier &tier, const typename Tier::Job &j, int32_t *status, Uncovered uncovered) {
+    const OrbitFragmentsShade &b = Tier::base(j);
     const size_t pixels = (size_t)b.width * b.height;
-    if (b.flags & ORBIT_SHADE_CLEAR) { // L9, H10
+    if (b.flags & ORBIT_SHADE_CLEAR) { // L9
         std::memset(b.color, 0, pixels * 16);
         if (b.lights_walked) std::memset(b.lights_walked, 0, pixels * 4);
-        if (j.shadow_factor) std::fill(j.shadow_factor, j.shadow_factor + pixels, 1.0f);
-        if (j.cascade) std::fill(j.cascade, j.cascade + pixels, kNone);
+        mirror_clear(j, pixels);
     }
-    const bool box = sky_box_given(js);
-    OrbitShadeStats st{};
-    OrbitShadowStats sh{};
-    OrbitSkyStats sky{};
+    ShadeTally t;
     for (size_t p = 0; p < pixels; p++) {
         const uint64_t word = b.visibility[p];
         const uint32_t x = (uint32_t)(p % b.width), y = (uint32_t)(p / b.width);
-        float color[4];
         if (word == 0) {
-            if (!box) continue;
-            if (!sky_box_pixel(js, x, y, color, counting)) sky.bad_directions++; // K9
-            sky.skybox_pixels++;
-            std::memcpy(b.color + 4 * p, color, 16);
+            uncovered(x, y, p, t);
             continue;
         }
-        st.covered_pixels++;
+        t.st.covered_pixels++;
         const uint32_t slice = shade_slice_canonical(b.z_near, bits_float((int32_t)(uint32_t)(word >> 32)), b.z_scale, b.z_bias); // L2
+        float color[4];
         uint32_t n, marks;
-        ShadowPixel sp;
-        SkyPixel sk;
-        const uint32_t verdict = sky_shade_pixel<true>(js, x, y, p, slice, color, n, marks, sp, sk, counting);
-        if (verdict == kShadeUnshaded) st.unshaded_pixels++;
-        if (verdict == kShadeStale) st.stale_pixels++;
+        typename Tier::Extra e;
+        Tier::reset(e);
+        const uint32_t verdict = shade_walk_pixel(tier, j, x, y, p, slice, color, n, marks, e);
+        if (verdict == kShadeUnshaded) t.st.unshaded_pixels++;
+        if (verdict == kShadeStale) t.st.stale_pixels++;
         if (verdict != kShadeWritten) continue;
-        st.written_pixels++;
-        if (marks & kShadeOutside) st.outside_pixels++;
-        if (marks & kShadeDegenerate) st.degenerate_pixels++;
-        if (marks & kShadeTextured) st.textured_pixels++;
-        if (marks & kShadeUnserved) st.unserved_pixels++;
-        if (sp.marks & kShadowEvaluated) sh.shadowed_pixels++;
-        if (sp.marks & kShadowOutOfCascades) sh.no_cascade_pixels++;
-        if (sp.marks & kShadowEarlyOut) sh.early_out_pixels++;
-        sh.shadow_evaluations += sp.evaluations;
-        if (sk.evaluations != 0u) sky.sky_lit_pixels++;
-        sky.sky_evaluations += sk.evaluations;
-        sky.bad_directions += sk.bad;
+        t.st.written_pixels++;
+        if (marks & kShadeOutside) t.st.outside_pixels++;
+        if (marks & kShadeDegenerate) t.st.degenerate_pixels++;
+        if (marks & kShadeTextured) t.st.textured_pixels++;
+        if (marks & kShadeUnserved) t.st.unserved_pixels++;
         std::memcpy(b.color + 4 * p, color, 16);
         if (b.lights_walked) b.lights_walked[p] = n;
-        if (j.shadow_factor) j.shadow_factor[p] = sp.factor;
-        if (j.cascade) j.cascade[p] = sp.cascade;
+        mirror_written(j, p, e, t);
     }
-    if (b.stats) *b.stats = st;
-    if (j.shadow_stats) *j.shadow_stats = sh;
-    if (js.sky_stats) *js.sky_stats = sky;
-    if (status) *status = st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
+    mirror_stats(j, t);
+    if (status) *status = t.st.stale_pixels != 0 ? ORBIT_E_RANGE : ORBIT_OK;
+}
+const auto kUncoveredStays = [](uint32_t, uint32_t, size_t, ShadeTally &) {};
+} // namespace
+
+void fragments_shade(const OrbitFragmentsShade &j, int32_t *status) {
+    check_fragments_shade(j);
+    shade_mirror(ShadeTier{}, j, status, kUncoveredStays);
+}
+
+void fragments_shade_shadowed(const OrbitFragmentsShadeShadowed &j, int32_t *status) {
+    check_fragments_shade(j.shade);
+    if (j.shadow_count > 0u) {
+        if (!j.shadows || !j.shadow_maps) throw Panic("fragments_shade_shadowed: shadow_count > 0 with shadows or shadow_maps NULL");
+        if (j.shadow_resolution == 0u || j.shadow_resolution > ORBIT_RASTER_MAX_DIM) throw Panic("fragments_shade_shadowed: shadow_resolution");
+        if ((uint64_t)j.shadow_map_count * j.shadow_resolution * j.shadow_resolution > (1ull << 31))
+            throw Panic("fragments_shade_shadowed: shadow maps > 2^31 floats");
+    }
+    shade_mirror(ShadowedTier{}, j, status, kUncoveredStays);
+}
+
+void fragments_shade_sky(const OrbitFragmentsShadeSky &js, int32_t *status, uint64_t *census) {
+    if (const char *wrong = sky_check(js)) throw Panic(std::string("fragments_shade_sky: ") + wrong);
+    const SkyCounting counting{census};
+    const bool box = sky_box_given(js);
+    shade_mirror(SkyTier<true, SkyCounting>{counting}, js, status, [&](uint32_t x, uint32_t y, size_t p, ShadeTally &t) { // K9
+        if (!box) return;
+        float color[4];
+        if (!sky_box_pixel(js, x, y, color, counting)) t.sky.bad_directions++;
+        t.sky.skybox_pixels++;
+        std::memcpy(js.shadowed.shade.color + 4 * p, color, 16);
+    });
 }
 
 void shadow_rotation(uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float *theta, float *sine, float *cosine) {

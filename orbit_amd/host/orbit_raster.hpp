@@ -71,7 +71,7 @@ void fragments_shade(const OrbitFragmentsShade &job, int32_t *status);
 // pixels, each through ../csrc/shadow_common.h.  Throws Panic for ORBIT_E_INVALID (alignment and aliasing aside).
 void fragments_shade_shadowed(const OrbitFragmentsShadeShadowed &job, int32_t *status);
 // orbit_fragments_shade_sky (K1-K10 on H1-H10 and L1-L9, §4.31) on host buffers, as fragments_shade_shadowed: the obvious
-// loop over the pixels, the covered ones through ../csrc/sky_common.h's sky_shade_pixel, the uncovered ones through its
+// loop over the pixels, the covered ones through ../csrc/shade_common.h's walk in sky_common.h's SkyTier, the uncovered ones through its
 // sky_box_pixel.  Throws Panic for what sky_check names: everything the device answers with ORBIT_E_INVALID, alignment
 // and aliasing included.  census (may be null): ORBIT_HOST_SKY_CENSUS counters (orbit_host_c.h).
 void fragments_shade_sky(const OrbitFragmentsShadeSky &job, int32_t *status, uint64_t *census = nullptr);

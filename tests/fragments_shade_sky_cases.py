@@ -189,6 +189,14 @@ def list_cases(oracle):
     return out
 
 
+def stale_map_case(oracle):
+    """8 x 8, two slices whose walks hold the sun between or behind evaluated sky lights, the sun's row naming a map that is
+    not there (H3): every pixel lies inside a cascade, so every walk goes stale at the sun and nothing is written"""
+    s = base_case("sky_stale_map", oracle, 8, 8, 8, 85, ([SKY, SUN, SKY, 12], [13, SKY, SUN]), uncovered=0.0)
+    s.rows["shadow_map_indices"][1, :] = len(s.maps)
+    return SkyCase(s, make_env(86, 2, 2, 2, 2), None)
+
+
 def skybox_cases(oracle):
     """8 x 8: every pixel uncovered; none; a checkerboard; a basis whose rays run along an edge; one whose rays hit two corners; a
     zero basis (every direction bad)"""
@@ -224,7 +232,7 @@ def tile_case(oracle):
 
 def all_cases(oracle):
     return (shape_cases(oracle) + size_cases(oracle) + [direction_case(oracle, t) for t in (8, 4)] + list_cases(oracle) + skybox_cases(oracle)
-            + [tile_case(oracle)])
+            + [tile_case(oracle), stale_map_case(oracle)])
 
 
 DROP = ("form", "want_walked", "want_stats", "want_factor", "want_cascade", "want_shadow_stats", "want_sky_stats", "want_census", "over", "into")
